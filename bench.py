@@ -28,6 +28,8 @@ per fit: through torch.distributed (default) or, with ``--exchange rccl``, throu
 With N > 1 in the weak mode the line also carries a ``shard`` sub-record: after the weak timed region the same ranks time
 the STRONG config-4 cycle (262 144 candidates and the fit's restarts split N ways) - what the scaling curve of the weak
 mode, N independent cycles, cannot say.  ``--no-secondary``: timed cycles only (for kernel traces that read per cycle).
+``--dump-outputs DIR``: what the last timed cycle computed, as DIR/<name>.npy (inputs are seeded: two builds compare
+output for output).
 
 Prints ONE JSON line (rank 0).
 """
@@ -50,6 +52,7 @@ if ROOT not in sys.path:
 
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X fp64 matrix peak (AMD spec; = 256 CU x 4 SIMD x 32 FLOP/clk x 2.4 GHz)
 SHARD_TOTAL_CANDIDATES = 262144
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: all files together
 
 
 def parse(argv=None):
@@ -76,7 +79,31 @@ def parse(argv=None):
                          "(bobe_mgpu_*, include/bobe_gp.h)")
     ap.add_argument("--shard-candidates", type=int, default=SHARD_TOTAL_CANDIDATES,
                     help="total candidates of --config shard (tests use a smaller set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed cycle computed (rank 0) as DIR/<name>.npy, "
+                         "float64, at most 64 MB in all (see dump_outputs)")
     return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, fixed, per_candidate, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Writes every array of ``fixed`` and ``per_candidate`` as ``out_dir/<name>.npy`` in float64.  The per-candidate
+    arrays share their length; should the whole set exceed ``budget`` bytes, all of them are cut to the same fixed,
+    seeded sample of candidate rows (ascending), whose indices are written as ``candidate_rows.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    fixed = {k: np.asarray(v, dtype=np.float64) for k, v in fixed.items()}
+    cols = {k: np.asarray(v, dtype=np.float64) for k, v in per_candidate.items()}
+    room = budget - sum(a.nbytes for a in fixed.values()) - 256 * (len(fixed) + len(cols) + 1)   # (.npy headers)
+    if cols:
+        n = len(next(iter(cols.values())))
+        assert all(a.shape == (n,) for a in cols.values()), {k: a.shape for k, a in cols.items()}
+        if 8 * n * len(cols) > room:
+            k = max(0, room // (8 * (len(cols) + 1)))                   # (+1: the row indices themselves)
+            rows = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+            cols = {name: a[rows] for name, a in cols.items()}
+            fixed["candidate_rows"] = rows.astype(np.float64)
+    for name, a in {**fixed, **cols}.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted({**fixed, **cols})
 
 
 def free_port() -> int:
@@ -221,6 +248,7 @@ def main():
     mll = C.c_double()
     av, asd, mv, ms = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
     last = {}
+    last_theta = np.full(d + 1, np.nan)                 # the merged best theta of the last cycle (--dump-outputs)
 
     R_total = max(1, args.fit_concurrency)              # restarts of the fit (= evaluations in flight on one GPU)
     # restarts this rank runs: all of them (weak: its own fit), or its np.array_split share (strong: pool.py:298-326)
@@ -315,6 +343,7 @@ def main():
             print(f"[rank {rank}] restarts {restarts} local best {best[0]!r} merged {bmll!r} mll_b {np.round(mll_b, 3).tolist()}",
                   file=sys.stderr, flush=True)
         last.update(best_mll=float(bmll), argmin=int(gidx), min_wipstd=float(gmin))
+        last_theta[:] = np.asarray(bth, dtype=np.float64)
 
     def barrier():
         if world > 1:
@@ -339,6 +368,14 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed cycle handed its caller: every evaluation's value + gradient, the merged best fit, the
+        # sweep's four per-candidate vectors of this rank's candidates and its argmins / minima (local and merged)
+        dump_outputs(args.dump_outputs,
+                     {"fit_mll": mll_b, "fit_grad": grad_b, "best_mll": [last["best_mll"]], "best_theta": last_theta,
+                      "sweep_argmin": [av.value, asd.value], "sweep_min": [mv.value, ms.value],
+                      "merged_argmin_wipstd": [last["argmin"]], "merged_min_wipstd": [last["min_wipstd"]]},
+                     {k: work[k][:Cn].cpu().numpy() for k in ("mean", "var", "wipv", "wipstd")} if Cn else {})
 
     # ---- N > 1, weak mode: the same ranks now time the STRONG config-4 cycle (candidates and restarts split N ways)
     shard_rec = None

@@ -55,3 +55,33 @@ def test_cpu_port_of_the_baseline_matches_the_numpy_oracle():
     assert np.allclose(a["wipv"], b["wipv"], rtol=1e-8) and np.allclose(a["wipstd"], b["wipstd"], rtol=1e-8)
     assert np.allclose(a["mean"], b["mean"], atol=1e-8) and a["argmin_s"] == b["argmin_s"]
     assert P.host_description()["threads"] >= 1
+
+
+def test_dump_outputs_writes_float64_within_the_budget(tmp_path):
+    """--dump-outputs: one .npy per output in float64; past the budget the per-candidate vectors are cut to one fixed,
+    seeded sample of rows, the same for every vector and from run to run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    fixed = {"fit_mll": rng.standard_normal(20), "fit_grad": rng.standard_normal((20, 9)), "sweep_argmin": [7, 11]}
+    cols = {k: rng.standard_normal(5000) for k in ("mean", "var", "wipv", "wipstd")}
+    names = bench.dump_outputs(str(tmp_path / "all"), fixed, cols)
+    assert names == sorted(list(fixed) + list(cols))
+    for k, v in {**fixed, **cols}.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, np.asarray(v, dtype=np.float64))
+    budget = 64 << 10
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), fixed, cols, budget=budget)
+        assert sum(p.stat().st_size for p in (tmp_path / run).iterdir()) <= budget
+    rows = np.load(tmp_path / "a" / "candidate_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 5000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "candidate_rows.npy"))
+    for k, v in cols.items():
+        a = np.load(tmp_path / "a" / (k + ".npy"))
+        assert np.array_equal(a, v[rows.astype(np.int64)]) and np.array_equal(a, np.load(tmp_path / "b" / (k + ".npy")))
+    assert np.array_equal(np.load(tmp_path / "a" / "fit_grad.npy"), fixed["fit_grad"])
+    a = bench.parse(["--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    assert a.dump_outputs == "out" and a.steps == 7 and a.warmup == 2
+    assert bench.parse([]).dump_outputs is None

@@ -246,7 +246,9 @@ def test_c_restatement_under_address_sanitizer():
     asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True, check=True).stdout.strip()
     if not os.path.isabs(asan):
         pytest.skip("no libasan in this toolchain")
-    env = dict(os.environ, LD_PRELOAD=asan, BOBE_ORACLE_C_LIB=os.path.join(odir, "libbobe_oracle_c_asan.so"),
+    # (first in the list, as the runtime requires; whatever the environment already preloads stays after it)
+    preload = " ".join(p for p in (asan, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, BOBE_ORACLE_C_LIB=os.path.join(odir, "libbobe_oracle_c_asan.so"),
                BOBE_ORACLE_XP_LIB=os.path.join(odir, "libbobe_oracle_xp_asan.so"), BOBE_XP_SKIP_QUAD="1",
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", os.path.abspath(__file__), "-k",
