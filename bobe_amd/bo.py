@@ -164,7 +164,8 @@ class BOBE:
         initial fit (bo.py:239) and, with the run state beside it, every ``save_step`` iterations;
         ``resume=True, resume_file=<save_dir>/<likelihood_name>`` continues from those files instead of drawing and
         evaluating an initial design (bo.py:205-206, 327-381; a file that cannot be loaded falls back to a fresh start, as
-        there); ``use_clf`` selects ``GPwithClassifier`` (SVM) with the thresholds derived from ``clf_nsigma_threshold``."""
+        there); ``use_clf`` selects ``GPwithClassifier`` (``clf_type`` 'svm' or 'ellipsoid') with the thresholds derived from
+        ``clf_nsigma_threshold``; its checkpoints carry the classifier's parameters (the ellipsoid's centre included)."""
         import logging
         if not logging.getLogger("bobe_amd").handlers and not logging.getLogger().handlers:
             setup_logging(verbosity)              # (the reference installs its handlers when the package is imported,

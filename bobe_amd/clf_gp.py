@@ -4,12 +4,14 @@ All GP arithmetic is inherited (``super()`` calls into libbobe_gp.so, as in the 
 this class adds what the reference adds: a second, larger data set for a feasibility classifier, the GP
 trained only on points within ``gp_threshold`` of the best value (clf_gp.py:86-93, 238-244), and the gating of
 the predictions — mean -> ``minus_inf`` and variance -> 1e-12 where the classifier says "infeasible"
-(clf_gp.py:173-205).  Only the SVM classifier is provided: scikit-learn's ``SVC`` is TRAINED on the host, as in the
-reference (clf.py:36-69); its RBF decision function (clf.py:188-213) and the gate are evaluated ON THE DEVICE
-(``bobe_gp_set_gate``: inside ``bobe_gp_predict`` / ``_predict_grad`` / ``_acq_ei`` and the HMC kernels).  This file
-holds no classifier arithmetic: it hands the trained parameters to the library and replaces the library's mark for a
-gated mean (-inf) by ``minus_inf``.  The Flax MLP / ellipsoid classifiers are optional extras of the reference and are
-not built.
+(clf_gp.py:173-205).  Two classifier types are built (``clf_type``, case-insensitive):
+ - 'svm': scikit-learn's ``SVC`` is TRAINED on the host, as in the reference (clf.py:36-69);
+ - 'ellipsoid': the learned Mahalanobis ball around the best point (clf.py:375-472), TRAINED on the device (all AdamW
+   restarts in one launch), warm-started from the previous parameters as in the reference.
+Either decision function and the gate are evaluated ON THE DEVICE (``bobe_gp_set_gate`` /
+``bobe_gp_set_gate_ellipsoid``: inside ``bobe_gp_predict`` / ``_predict_grad`` / ``_acq_ei``, the HMC and random-walk
+kernels).  This file holds no classifier arithmetic: it hands the trained parameters to the library and replaces the
+library's mark for a gated mean (-inf) by ``minus_inf``.  The Flax MLP ('nn') of the reference is not built.
 """
 from __future__ import annotations
 
@@ -17,12 +19,40 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .clf import (CLASSIFIER_REGISTRY, _DeviceSVM, gate_eval, get_svm_predict_proba_fn, install_gate,  # noqa: F401
-                  train_svm_classifier)
+from .clf import (CLASSIFIER_REGISTRY, MAX_ELLIPSOID_DIM, EllipsoidClassifier, _DeviceSVM, gate_eval,  # noqa: F401
+                  gate_proba, get_ellipsoid_predict_proba_fn, get_svm_predict_proba_fn, install_ellipsoid_gate,
+                  install_gate, train_ellipsoid_classifier, train_svm_classifier)
 from .gp import GP, safe_noise_floor
 from .utils import get_logger, get_numpy_rng
 
 log = get_logger("clf_gp")
+
+
+def _install_svm(gp, params):
+    install_gate(gp._lib, gp._h, params, gp.probability_threshold, gp.minus_inf)
+
+
+def _install_ellipsoid(gp, params):
+    install_ellipsoid_gate(gp._lib, gp._h, params, None, gp.probability_threshold, gp.minus_inf)
+
+
+def _train_svm(gp, labels):
+    return train_svm_classifier(gp.train_x_clf, labels, gp.clf_settings)
+
+
+def _train_ellipsoid(gp, labels):
+    best_pt = gp.train_x_clf[int(np.argmax(gp.train_y_clf))]                   # clf_gp.py:161-163
+    return train_ellipsoid_classifier(gp.train_x_clf, labels, gp.clf_settings, init_params=gp.clf_params,
+                                      best_pt=best_pt, handle=(gp._lib, gp._h), device=gp.device)
+
+
+# The classifier kinds GPwithClassifier dispatches (the public CLASSIFIER_REGISTRY of clf.py lists the SVM only): how to
+# train one from the labels and how to hand its parameters to the library's gate.  A further kind adds a row here and a
+# decision function in the library's Gate (gp_types.hpp).
+_CLF_KINDS = {
+    "svm": {"train": _train_svm, "install": _install_svm},
+    "ellipsoid": {"train": _train_ellipsoid, "install": _install_ellipsoid},
+}
 
 
 class GPwithClassifier(GP):
@@ -34,12 +64,16 @@ class GPwithClassifier(GP):
                  kernel_variance=1.0, param_names=None, train_clf_on_init=True, device: int = 0,
                  pivot_floor_ulp: Optional[float] = None):
         """Same keywords as clf_gp.py:15-30 (+ ``device``, ``pivot_floor_ulp``: see ``GP``)."""
-        if clf_type.lower() != "svm":
-            raise ValueError(f"Unsupported classifier type: {clf_type} (only 'svm' is built)")
+        kind = str(clf_type).lower()
+        if kind not in _CLF_KINDS:
+            raise ValueError(f"Unsupported classifier type: {clf_type} (built: {', '.join(sorted(_CLF_KINDS))})")
+        ndim = np.asarray(train_x).reshape(len(train_x), -1).shape[1]
+        if kind == "ellipsoid" and ndim > MAX_ELLIPSOID_DIM:
+            raise ValueError(f"clf_type='ellipsoid' supports d <= {MAX_ELLIPSOID_DIM} (got d = {ndim})")
         self.train_x_clf = np.array(train_x, dtype=np.float64)
         self.train_y_clf = np.array(train_y, dtype=np.float64).reshape(-1, 1)
         self.clf_use_size, self.clf_update_step = clf_use_size, clf_update_step
-        self.clf_type, self.clf_settings = "svm", (clf_settings or {})
+        self.clf_type, self.clf_settings = kind, (clf_settings or {})
         self.clf_params, self.clf_metrics = None, {}
         self.probability_threshold, self.minus_inf = probability_threshold, minus_inf
         self.clf_threshold, self.gp_threshold = clf_threshold, gp_threshold
@@ -78,18 +112,20 @@ class GPwithClassifier(GP):
         if not hasattr(self, "_h") or not self._h.value:
             return                                          # (before GP.__init__ created the handle)
         if want:
-            install_gate(self._lib, self._h, self.clf_params, self.probability_threshold, self.minus_inf)
+            _CLF_KINDS[self.clf_type]["install"](self, self.clf_params)
             self._clf_predict_func = self._device_proba
         elif self._gate_installed:
             install_gate(self._lib, self._h, None, self.probability_threshold, self.minus_inf)
         self._gate_installed = want
 
     def _device_proba(self, x):
-        """``svm_predict_proba`` (clf.py:210-213) of the trained classifier, on the device."""
-        return gate_eval(self._lib, self._h, x, self.ndim)[1]
+        """The trained classifier's probability (``svm_predict_proba``, clf.py:210-213, or the ellipsoid's
+        sigmoid(logit), clf.py:134-136), on the device."""
+        return gate_proba(self._lib, self._h, x, self.ndim)
 
     def clf_decision(self, x):
-        """``svm_predict`` (clf.py:188-208): the decision values of the trained classifier, on the device."""
+        """The decision values of the trained classifier, on the device: ``svm_predict`` (clf.py:188-208) or the
+        ellipsoid's logit."""
         return gate_eval(self._lib, self._h, x, self.ndim)[0]
 
     def train_classifier(self):
@@ -102,7 +138,7 @@ class GPwithClassifier(GP):
         if np.all(labels == labels[0]):               # one class only: do not use the classifier for the moment
             self.use_clf = False
             return
-        self.clf_params, self.clf_metrics, _ = train_svm_classifier(self.train_x_clf, labels, self.clf_settings)
+        self.clf_params, self.clf_metrics, _ = _CLF_KINDS[self.clf_type]["train"](self, labels)
         self._sync_gate()
 
     def _gated(self) -> bool:

@@ -25,18 +25,29 @@ __device__ __forceinline__ double log_ei_helper(double u) {
 }
 
 // ---- the classifier gate of GPwithClassifier (clf_gp.py:173-205) ---------------------------------------------------
-// SVM-RBF decision function of clf.py:188-213 by DIRECT DIFFERENCES, as the reference computes it:
-//   diff = support_vectors - x;  norm_sq = sum_j diff_j^2;  decision = sum_i dual_i exp(-gamma norm_sq_i) + intercept.
-// One 256-thread workgroup per point, ONE summation order everywhere (the batch kernel and the HMC kernels share
-// gate_partial / gate_combine): thread t adds the vectors t, t + 256, ... in ascending order, lanes by chain_wave_sum, then the
-// four waves ((r0 + r1) + r2) + r3, then + intercept.  A point near the boundary is therefore classified the same way by
-// every entry point.  x: the point's d raw (unit-cube) coordinates, readable by every thread.
+// One 256-thread workgroup per point, ONE summation order everywhere (the batch kernel and the HMC / random-walk kernels
+// share gate_partial / gate_combine): gate_partial's per-thread value, lanes by chain_wave_sum, then the four waves
+// ((r0 + r1) + r2) + r3 in gate_combine.  A point near the boundary is therefore classified the same way by every entry
+// point.  x: the point's d raw (unit-cube) coordinates, readable by every thread.
+//   GATE_SVM        (clf.py:188-213, by DIRECT DIFFERENCES, as the reference computes it: diff = support_vectors - x;
+//                   norm_sq = sum_j diff_j^2; decision = sum_i dual_i exp(-gamma norm_sq_i) + intercept): thread t adds
+//                   the vectors t, t + 256, ... in ascending order; + intercept after the waves.
+//   GATE_ELLIPSOID  (clf.py:377-412): thread t < d computes u_t = sum_{i >= t} L[i][t] (x_i - mu_i) in ascending i and
+//                   contributes u_t^2 (md2 = |L^T diff|^2 = diff^T L L^T diff); logit = -alpha md2 + beta after the waves.
 template <int DCAP>
 __device__ __forceinline__ double gate_partial(const Gate& gt, const double* x, int d, int t) {
+  double s = 0.0;
+  if (gt.kind == GATE_ELLIPSOID) {
+    if (t < d) {
+      double u = 0.0;
+      for (int i = t; i < d; ++i) u = fma(gt.Lt[i * d + t], x[i] - gt.mu[i], u);
+      s = u * u;
+    }
+    return chain_wave_sum(s);
+  }
   double xr[DCAP];
 #pragma unroll
   for (int j = 0; j < DCAP; ++j) xr[j] = (j < d) ? x[j] : 0.0;
-  double s = 0.0;
   for (int i = t; i < gt.n_sv; i += 256) {
     double r2 = 0.0;
 #pragma unroll
@@ -50,23 +61,30 @@ __device__ __forceinline__ double gate_partial(const Gate& gt, const double* x, 
   }
   return chain_wave_sum(s);
 }
-// red[4]: the four waves' sums (written by lane 0 of each wave, followed by a barrier)
+// red[4]: the four waves' sums (written by lane 0 of each wave, followed by a barrier) -> the decision value (the SVM's
+// decision function, the ellipsoid's logit)
 __device__ __forceinline__ double gate_combine(const Gate& gt, const double* red) {
-  return (((red[0] + red[1]) + red[2]) + red[3]) + gt.intercept;
+  const double r = ((red[0] + red[1]) + red[2]) + red[3];
+  if (gt.kind == GATE_ELLIPSOID) return fma(-gt.alpha, r, gt.beta);
+  return r + gt.intercept;
 }
-// svm_predict_proba (clf.py:210-213) against the probability threshold (clf_gp.py:179): NaN decisions are infeasible
+// the classifier's probability: svm_predict_proba (clf.py:210-213) or sigmoid(logit) (clf.py:134-136)
+__device__ __forceinline__ double gate_proba(const Gate& gt, double decision) {
+  if (gt.kind == GATE_ELLIPSOID) return 1.0 / (1.0 + exp(-decision));
+  return (decision >= 0.0) ? 1.0 : 0.0;
+}
+// ... against the probability threshold (clf_gp.py:179): NaN decisions are infeasible (a NaN probability compares false)
 __device__ __forceinline__ bool gate_feasible(const Gate& gt, double decision) {
-  const double proba = (decision >= 0.0) ? 1.0 : 0.0;
-  return proba >= gt.threshold;
+  return gate_proba(gt, decision) >= gt.threshold;
 }
 
-// decision / feasibility of C points (xq: C x d row-major, raw coordinates); optionally the gating of a prediction in
+// decision / feasibility / probability of C points (xq: C x d row-major, raw coordinates); optionally the gating of a prediction in
 // place: mean -> -inf (the wrapper's sentinel for minus_inf, bobe_gp.h), var -> 1e-12 (clf_gp.py:189, 203), gradients -> 0
 template <int DCAP>
 __global__ __launch_bounds__(256) void k_gate(Gate gt, const double* __restrict__ xq, int d, double* __restrict__ decision,
                                               double* __restrict__ feasible, double* __restrict__ mean,
                                               double* __restrict__ var, double* __restrict__ dmean,
-                                              double* __restrict__ dvar) {
+                                              double* __restrict__ dvar, double* __restrict__ proba) {
   __shared__ double red[4];
   const int t = threadIdx.x;
   const int64_t c = blockIdx.x;
@@ -78,6 +96,7 @@ __global__ __launch_bounds__(256) void k_gate(Gate gt, const double* __restrict_
   if (t == 0) {
     if (decision) decision[c] = dec;
     if (feasible) feasible[c] = ok ? 1.0 : 0.0;
+    if (proba) proba[c] = gate_proba(gt, dec);
     if (!ok) {
       if (mean) mean[c] = -INFINITY;
       if (var) var[c] = NOISE_FLOOR;
@@ -153,12 +172,12 @@ __global__ __launch_bounds__(256) void k_hmc_leapfrog(const double* __restrict__
       }
     }
     // classifier gate (clf_gp.py:173-205): an infeasible point has mean = minus_inf and no mean gradient
-    if (gt.n_sv > 0) {
+    if (gate_on(gt)) {
       const double gs = gate_partial<DCAP>(gt, x, d, t);
       if (lane == 0) gred[wave] = gs;
     }
     __syncthreads();
-    const bool ok = gt.n_sv > 0 ? gate_feasible(gt, gate_combine(gt, gred)) : true;
+    const bool ok = gate_on(gt) ? gate_feasible(gt, gate_combine(gt, gred)) : true;
     if (t < d) {
       const double dm = ok ? (((red[0][t] + red[1][t]) + red[2][t]) + red[3][t]) / h.ls[t] : 0.0;
       const double xv = x[t];
@@ -361,12 +380,12 @@ __global__ __launch_bounds__(256) void k_hmc_run(const double* __restrict__ XsT,
       }
       // classifier gate (clf_gp.py:173-205): an infeasible point has mean = minus_inf and no mean gradient - its
       // trajectory ends in a state that the Metropolis test never accepts
-      if (gt.n_sv > 0) {                                       // (the gate's 256 partial sums: k_gate's order)
+      if (gate_on(gt)) {                                       // (the gate's 256 partial sums: k_gate's order)
         const double gs = gate_partial<DCAP>(gt, x, d, t);
         if (lane == 0) gred[wave] = gs;
       }
       __syncthreads();
-      const bool ok = gt.n_sv > 0 ? gate_feasible(gt, gate_combine(gt, gred)) : true;
+      const bool ok = gate_on(gt) ? gate_feasible(gt, gate_combine(gt, gred)) : true;
       // (the waves' sums in wave order: ((r0 + r1) + r2) + r3)
       auto wsum = [&](int j) {
         double sres = red[0][j];
@@ -573,7 +592,7 @@ __global__ __launch_bounds__(256) void k_rwalk(const double* __restrict__ XsT, i
       }
       ms = chain_wave_sum(ms);
       if (lane == 0) red[wave] = ms;
-      if (gt.n_sv > 0) {
+      if (gate_on(gt)) {
         const double gs = gate_partial<DCAP>(gt, xp, d, t);
         if (lane == 0) gred[wave] = gs;
       }
@@ -583,7 +602,7 @@ __global__ __launch_bounds__(256) void k_rwalk(const double* __restrict__ XsT, i
 #pragma unroll
         for (int w_ = 1; w_ < NW; ++w_) m += red[w_];
         m = m * ystd + ymean;
-        if (gt.n_sv > 0 && !gate_feasible(gt, gate_combine(gt, gred))) m = gt.minus_inf;
+        if (gate_on(gt) && !gate_feasible(gt, gate_combine(gt, gred))) m = gt.minus_inf;
         const int acc = m > lstar;
         inside_s = acc;                                                    // (reused: accepted)
         if (acc) {
@@ -621,6 +640,186 @@ __global__ void k_ei(const double* __restrict__ mu, const double* __restrict__ v
   if (m == -INFINITY) m = minus_inf;
   const double u = (m - zeta - best_y) / sigma;
   out[i] = mode ? (log_ei_helper(u) + log(sigma)) : (ei_helper(u) * sigma);
+}
+
+// ---- training of the ellipsoid classifier (clf.py:415-472): every restart's whole AdamW run in ONE launch ----------
+// One 256-thread workgroup = one restart (blockIdx.x).  Parameters theta = [flat_L (T = d(d+1)/2, tril_indices order:
+// (0,0), (1,0), (1,1), (2,0), ...), alpha, beta], P = T + 2 <= 530: thread t owns theta[t], theta[t + 256], theta[t + 512]
+// and their Adam moments in registers; the transformed L (diagonal softplus + 1e-4) lives in LDS, dense [i][j].
+// Per step (batch b of B rows, rows perm[...]; B = min(batch, N)), in chunks of 64 rows:
+//   A  gather diff = x - mu of the chunk's rows into LDS
+//   B  wave q, lane b: u_j = sum_{i >= j} L[i][j] diff_i (ascending i) for j = q, q + 4, ...; the wave's sum of u_j^2
+//   C  thread b: md2 = ((s0 + s1) + s2) + s3, logit = -alpha md2 + beta, g_b = (sigmoid(logit) - y_b) / B
+//      (the gradient of optax.sigmoid_binary_cross_entropy(logit, y).mean())
+//   D  thread of theta_p: accumulate over the chunk's rows in ascending order
+//        dL[i][j] = sum_b g_b u_bj diff_bi (x -2 alpha, x sigmoid(flat) on the diagonal), dalpha = -sum_b g_b md2_b,
+//        dbeta = sum_b g_b
+// then optax.adamw (b1 0.9, b2 0.999, eps 1e-8, eps_root 0, decay on every parameter) in optax's order of operations.
+// At the end: the parameters and the full-data loss (rows t, t + 256, ... per thread, then the waves in order).
+//   perm  [R][n_epochs][steps * B] int32 row indices (the host's RandomState permutations; validated by the host)
+//   init  [R][P]   starting parameters;   params_out [R][P];   loss_out [R]
+constexpr int ELL_NT = 256, ELL_ROWS = 64, ELL_DS = MAX_D + 1;
+__global__ __launch_bounds__(256) void k_ellipsoid_train(const double* __restrict__ X, const double* __restrict__ y,
+                                                         int64_t N, int d, const double* __restrict__ mu,
+                                                         const double* __restrict__ init, const int* __restrict__ perm,
+                                                         int n_epochs, int steps, int B, double lr, double wd,
+                                                         double* __restrict__ params_out, double* __restrict__ loss_out) {
+  __shared__ double sL[MAX_D * MAX_D], smu[MAX_D], sdiff[ELL_ROWS * ELL_DS], su[ELL_ROWS * ELL_DS],
+      spart[4][ELL_ROWS], sy[ELL_ROWS], sg[ELL_ROWS], sgm[ELL_ROWS], red[4], s_ab[2];
+  constexpr int KP = 3;                                   // ceil(530 / 256)
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int r = blockIdx.x;
+  const int T = d * (d + 1) / 2, P = T + 2;
+  const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
+  double pv[KP], mv[KP], vv[KP], G[KP];
+  int pi[KP], pj[KP];
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const int p = t + ELL_NT * k;
+    pv[k] = p < P ? init[(int64_t)r * P + p] : 0.0;
+    mv[k] = vv[k] = G[k] = 0.0;
+    int i = 0;
+    while ((i + 1) * (i + 2) / 2 <= p) ++i;             // row of tril index p (only meaningful for p < T)
+    pi[k] = i;
+    pj[k] = p - i * (i + 1) / 2;
+  }
+  for (int e = t; e < MAX_D * MAX_D; e += ELL_NT) sL[e] = 0.0;
+  if (t < d) smu[t] = mu[t];
+  __syncthreads();
+  auto publish = [&]() {                                 // theta -> the LDS copy the forward pass reads
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      const int p = t + ELL_NT * k;
+      if (p < T) {
+        const double v = pv[k];
+        sL[pi[k] * MAX_D + pj[k]] = (pi[k] == pj[k]) ? fmax(v, 0.0) + log1p(exp(-fabs(v))) + 1e-4 : v;
+      } else if (p < P) {
+        s_ab[p - T] = pv[k];
+      }
+    }
+  };
+  publish();
+  __syncthreads();
+  const int R = steps * B;
+  int64_t count = 0;
+  for (int ep = 0; ep < n_epochs; ++ep) {
+    for (int st = 0; st < steps; ++st) {
+      const int* pr = perm + ((int64_t)r * n_epochs + ep) * R + (int64_t)st * B;
+      const double alpha = s_ab[0], beta = s_ab[1];
+#pragma unroll
+      for (int k = 0; k < KP; ++k) G[k] = 0.0;
+      for (int b0 = 0; b0 < B; b0 += ELL_ROWS) {
+        const int nb = min(ELL_ROWS, B - b0);
+        // A: the chunk's rows
+        for (int e = t; e < nb * d; e += ELL_NT) {
+          const int b = e / d, i = e - b * d;
+          const int64_t row = pr[b0 + b];
+          sdiff[b * ELL_DS + i] = X[row * d + i] - smu[i];
+          if (i == 0) sy[b] = y[row];
+        }
+        __syncthreads();
+        // B: u = L^T diff, split over the waves by column
+        if (lane < nb) {
+          double part = 0.0;
+          for (int j = wave; j < d; j += 4) {
+            double u = 0.0;
+            for (int i = j; i < d; ++i) u = fma(sL[i * MAX_D + j], sdiff[lane * ELL_DS + i], u);
+            su[lane * ELL_DS + j] = u;
+            part = fma(u, u, part);
+          }
+          spart[wave][lane] = part;
+        }
+        __syncthreads();
+        // C: the loss gradient per row
+        if (t < nb) {
+          const double md2 = ((spart[0][t] + spart[1][t]) + spart[2][t]) + spart[3][t];
+          const double logit = fma(-alpha, md2, beta);
+          const double g = (1.0 / (1.0 + exp(-logit)) - sy[t]) / (double)B;
+          sg[t] = g;
+          sgm[t] = g * md2;
+        }
+        __syncthreads();
+        // D: the parameter gradients, rows in ascending order
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          const int p = t + ELL_NT * k;
+          double acc = G[k];
+          if (p < T) {
+            const int i = pi[k], j = pj[k];
+            for (int b = 0; b < nb; ++b) acc = fma(sdiff[b * ELL_DS + i], sg[b] * su[b * ELL_DS + j], acc);
+          } else if (p == T) {
+            for (int b = 0; b < nb; ++b) acc += sgm[b];
+          } else if (p == T + 1) {
+            for (int b = 0; b < nb; ++b) acc += sg[b];
+          }
+          G[k] = acc;
+        }
+        if (b0 + ELL_ROWS < B) __syncthreads();         // (the next chunk overwrites the rows)
+      }
+      // AdamW (optax.adamw: scale_by_adam, add_decayed_weights, scale_by_learning_rate, apply_updates)
+      ++count;
+      const double bc1 = 1.0 - pow(b1, (double)count), bc2 = 1.0 - pow(b2, (double)count);
+#pragma unroll
+      for (int k = 0; k < KP; ++k) {
+        const int p = t + ELL_NT * k;
+        if (p < P) {
+          double g = G[k];
+          if (p < T) {
+            g *= -2.0 * alpha;
+            if (pi[k] == pj[k]) g *= 1.0 / (1.0 + exp(-pv[k]));
+          } else if (p == T) {
+            g = -g;
+          }
+          mv[k] = (1.0 - b1) * g + b1 * mv[k];
+          vv[k] = (1.0 - b2) * (g * g) + b2 * vv[k];
+          const double mh = mv[k] / bc1, vh = vv[k] / bc2;
+          const double upd = mh / (sqrt(vh) + eps) + wd * pv[k];
+          pv[k] = pv[k] + (-lr) * upd;
+        }
+      }
+      publish();
+      __syncthreads();
+    }
+  }
+  // full-data loss: optax.sigmoid_binary_cross_entropy(logit, y).mean(), log_sigmoid(z) = -softplus(-z); the rows in
+  // chunks of 64 through phases A / B (thread b sums rows b, b + 64, ...), then the four waves in order
+  const double alpha = s_ab[0], beta = s_ab[1];
+  double ls = 0.0;
+  for (int64_t b0 = 0; b0 < N; b0 += ELL_ROWS) {
+    const int nb = (int)min<int64_t>(ELL_ROWS, N - b0);
+    __syncthreads();
+    for (int e = t; e < nb * d; e += ELL_NT) {
+      const int b = e / d, i = e - b * d;
+      sdiff[b * ELL_DS + i] = X[(b0 + b) * d + i] - smu[i];
+    }
+    __syncthreads();
+    if (lane < nb) {
+      double part = 0.0;
+      for (int j = wave; j < d; j += 4) {
+        double u = 0.0;
+        for (int i = j; i < d; ++i) u = fma(sL[i * MAX_D + j], sdiff[lane * ELL_DS + i], u);
+        part = fma(u, u, part);
+      }
+      spart[wave][lane] = part;
+    }
+    __syncthreads();
+    if (t < nb) {
+      const double md2 = ((spart[0][t] + spart[1][t]) + spart[2][t]) + spart[3][t];
+      const double l = fma(-alpha, md2, beta), yn = y[b0 + t];
+      const double sp_neg = fmax(-l, 0.0) + log1p(exp(-fabs(l)));     // softplus(-l) = -log_sigmoid(l)
+      const double sp_pos = fmax(l, 0.0) + log1p(exp(-fabs(l)));      // softplus(l)  = -log_sigmoid(-l)
+      ls += yn * sp_neg + (1.0 - yn) * sp_pos;
+    }
+  }
+  ls = wave_sum(ls);
+  if (lane == 0) red[wave] = ls;
+  __syncthreads();
+  if (t == 0) loss_out[r] = (((red[0] + red[1]) + red[2]) + red[3]) / (double)N;
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const int p = t + ELL_NT * k;
+    if (p < P) params_out[(int64_t)r * P + p] = pv[k];
+  }
 }
 
 }  // namespace bobe

@@ -349,6 +349,36 @@ int bobe_gp_gate_eval(bobe_gp_t* g, const double* Xq, int64_t C, double* decisio
   API_END
 }
 
+int bobe_gp_set_gate_ellipsoid(bobe_gp_t* g, const double* flat_L, const double* mu, double alpha, double beta,
+                               double probability_threshold, double minus_inf) {
+  API_BEGIN
+  NEED(g && flat_L && mu, "NULL argument");
+  g->set_gate_ellipsoid(flat_L, mu, alpha, beta, probability_threshold, minus_inf);
+  return BOBE_OK;
+  API_END
+}
+
+int bobe_gp_gate_proba(bobe_gp_t* g, const double* Xq, int64_t C, double* proba) {
+  API_BEGIN
+  NEED(g && Xq && proba, "NULL argument");
+  g->gate_proba(Xq, C, proba);
+  return BOBE_OK;
+  API_END
+}
+
+int bobe_gp_train_ellipsoid(bobe_gp_t* g, const double* X, const double* y, int64_t N, const double* mu, int n_restarts,
+                            const double* init, const int32_t* perm, int n_epochs, int batch, double lr, double wd,
+                            double* params_out, double* loss_out) {
+  API_BEGIN
+  NEED(g && X && y && mu && init && perm && params_out && loss_out, "NULL argument");
+  NEED(!is_device_ptr(X) && !is_device_ptr(y) && !is_device_ptr(mu) && !is_device_ptr(init) && !is_device_ptr(perm) &&
+           !is_device_ptr(params_out) && !is_device_ptr(loss_out),
+       "bobe_gp_train_ellipsoid takes host pointers");
+  g->train_ellipsoid(X, y, N, mu, n_restarts, init, perm, n_epochs, batch, lr, wd, params_out, loss_out);
+  return BOBE_OK;
+  API_END
+}
+
 int bobe_gp_kernel(bobe_gp_t* g, const double* A, int64_t nA, const double* B, int64_t nB, const double* ls,
                    double kvar, double noise, int include_noise, double* out) {
   API_BEGIN

@@ -28,7 +28,7 @@ void bobe_gp::set_gate(const double* sv, int64_t n_sv, const double* dual, doubl
   use();
   sync();
   if (!sv || n_sv <= 0) {                      // clear
-    gate = Gate{nullptr, nullptr, 0, 0, 0.0, 0.0, threshold, minus_inf};
+    gate = Gate{nullptr, nullptr, 0, 0, 0.0, 0.0, threshold, minus_inf, GATE_NONE, nullptr, nullptr, 0.0, 0.0};
     return;
   }
   if (!dual) throw Err(BOBE_ERR_ARG, "dual_coef is NULL");
@@ -47,15 +47,75 @@ void bobe_gp::set_gate(const double* sv, int64_t n_sv, const double* dual, doubl
   HIPCHK(hipMemcpy(gate_sv.p, svt.data(), svt.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(gate_dual.p, dual, (size_t)n_sv * sizeof(double),
                    is_device_ptr(dual) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-  gate = Gate{gate_sv.d(), gate_dual.d(), n_sv, (int)n_sv, intercept, gamma, threshold, minus_inf};
+  gate = Gate{gate_sv.d(), gate_dual.d(), n_sv, (int)n_sv, intercept, gamma, threshold, minus_inf, GATE_SVM, nullptr,
+              nullptr, 0.0, 0.0};
+}
+
+// the reference's raw flat_L (tril_indices order) -> L with softplus(.) + 1e-4 on the diagonal, once, dense row-major
+void bobe_gp::set_gate_ellipsoid(const double* flat_L, const double* mu, double alpha, double beta, double threshold,
+                                 double minus_inf) {
+  if (!flat_L || !mu) throw Err(BOBE_ERR_ARG, "flat_L / mu is NULL");
+  use();
+  sync();
+  const int T = d * (d + 1) / 2;
+  std::vector<double> fl(T), m(d), buf((size_t)d * d + d, 0.0);
+  HIPCHK(hipMemcpy(fl.data(), flat_L, T * sizeof(double), is_device_ptr(flat_L) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+  HIPCHK(hipMemcpy(m.data(), mu, d * sizeof(double), is_device_ptr(mu) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+  for (int i = 0, p = 0; i < d; ++i)
+    for (int j = 0; j <= i; ++j, ++p) {
+      const double v = fl[p];
+      buf[(size_t)i * d + j] = (i == j) ? std::fmax(v, 0.0) + std::log1p(std::exp(-std::fabs(v))) + 1e-4 : v;
+    }
+  for (int j = 0; j < d; ++j) buf[(size_t)d * d + j] = m[j];
+  gate_ell.ensure(buf.size() * sizeof(double));
+  HIPCHK(hipMemcpy(gate_ell.p, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
+  gate = Gate{nullptr, nullptr, 0, 0, 0.0, 0.0, threshold, minus_inf, GATE_ELLIPSOID, gate_ell.d(), gate_ell.d() + (size_t)d * d,
+              alpha, beta};
+}
+
+void bobe_gp::train_ellipsoid(const double* X, const double* yv, int64_t N, const double* mu, int n_restarts,
+                              const double* init, const int32_t* perm, int n_epochs, int batch, double lr, double wd,
+                              double* params_out, double* loss_out) {
+  if (N < 1 || n_restarts < 1 || n_epochs < 0 || batch < 1) throw Err(BOBE_ERR_ARG, "bad argument");
+  if (N > INT_MAX) throw Err(BOBE_ERR_ARG, "N too large");
+  const int B = (int)std::min<int64_t>(batch, N);
+  const int steps = (int)std::max<int64_t>(1, N / batch);
+  const int P = d * (d + 1) / 2 + 2;
+  const size_t np = (size_t)n_restarts * n_epochs * steps * B;
+  for (size_t i = 0; i < np; ++i)                       // (every row index the kernel will read must exist)
+    if ((uint32_t)perm[i] >= (uint32_t)N) throw Err(BOBE_ERR_ARG, "perm holds a row index outside [0, N)");
+  use();
+  // workspace: X (N d) | y (N) | mu (d) | init (R P) | params_out (R P) | loss_out (R)
+  const size_t nx = (size_t)N * d, ni = (size_t)n_restarts * P;
+  ell_ws.ensure((nx + N + d + 2 * ni + n_restarts) * sizeof(double));
+  double* dX = ell_ws.d();
+  double* dy = dX + nx;
+  double* dmu = dy + N;
+  double* dinit = dmu + d;
+  double* dout = dinit + ni;
+  double* dloss = dout + ni;
+  ell_perm.ensure(std::max<size_t>(np, 1) * sizeof(int32_t));
+  HIPCHK(hipMemcpyAsync(dX, X, nx * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(dy, yv, N * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(dmu, mu, d * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(dinit, init, ni * sizeof(double), hipMemcpyHostToDevice, stream));
+  if (np) HIPCHK(hipMemcpyAsync(ell_perm.p, perm, np * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_ellipsoid_train, dim3((unsigned)n_restarts), dim3(ELL_NT), 0, stream, (const double*)dX,
+                     (const double*)dy, N, d, (const double*)dmu, (const double*)dinit, (const int*)ell_perm.p, n_epochs,
+                     steps, B, lr, wd, dout, dloss);
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(params_out, dout, ni * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(loss_out, dloss, n_restarts * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
 }
 
 void bobe_gp::gate_apply(const double* xq_dev, int64_t C, double* decision, double* feasible, double* mean, double* var,
-                         double* dmean, double* dvar) {
-  if (gate.n_sv <= 0) throw Err(BOBE_ERR_STATE, "no classifier gate is set (bobe_gp_set_gate)");
+                         double* dmean, double* dvar, double* proba) {
+  if (!gate_on(gate)) throw Err(BOBE_ERR_STATE, "no classifier gate is set (bobe_gp_set_gate)");
   const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
 #define GT(DC) \
-  hipLaunchKernelGGL((k_gate<DC>), dim3((unsigned)C), dim3(256), 0, stream, gate, xq_dev, d, decision, feasible, mean, var, dmean, dvar)
+  hipLaunchKernelGGL((k_gate<DC>), dim3((unsigned)C), dim3(256), 0, stream, gate, xq_dev, d, decision, feasible, mean, var, dmean, dvar, \
+                     proba)
   if (dcap == 8) GT(8); else if (dcap == 16) GT(16); else GT(32);
 #undef GT
   LAUNCH_CHECK();
@@ -70,6 +130,16 @@ void bobe_gp::gate_eval(const double* Xq, int64_t C, double* decision, double* f
   gate_apply(cin, C, d_dec, d_fe, nullptr, nullptr, nullptr, nullptr);
   out_finish(decision, C, o_mean);
   out_finish(feasible, C, o_var);
+  sync();
+}
+
+void bobe_gp::gate_proba(const double* Xq, int64_t C, double* proba) {
+  if (C <= 0) throw Err(BOBE_ERR_ARG, "C must be positive");
+  use();
+  const double* cin = fetch(Xq, (size_t)C * d, in_stage);
+  double* d_p = out_dev(proba, C, o_mean);
+  gate_apply(cin, C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_p);
+  out_finish(proba, C, o_mean);
   sync();
 }
 
@@ -309,7 +379,8 @@ void bobe_gp::release_all() {
   if (stream) (void)hipStreamSynchronize(stream);
   DBuf* bufs[] = {&X, &y, &XsT, &XsT2, &A, &Linv, &A2, &Linv2, &Tmp, &alpha, &w, &alpha2, &w2, &part, &gpart, &res, &info,
                   &probs, &flags, &diag, &in_stage, &z_stage, &CsT, &ZsT, &kXC, &kXZ, &VZ, &WZ, &basez, &sc, &qpart, &pv,
-                  &ps, &o_mean, &o_var, &o_wipv, &o_wipstd, &o_misc, &kin_a, &kin_b, &kout, &wg_ws, &gate_sv, &gate_dual, &vxc, &vxc2};
+                  &ps, &o_mean, &o_var, &o_wipv, &o_wipstd, &o_misc, &kin_a, &kin_b, &kout, &wg_ws, &gate_sv, &gate_dual, &gate_ell, &ell_ws, &ell_perm,
+                  &vxc, &vxc2};
   for (DBuf* b : bufs) b->release();
   for (auto& pr : prof_events) {
     (void)hipEventDestroy(pr.first);

@@ -195,16 +195,25 @@ struct bobe_gp {
   double* h_res = nullptr;  // pinned, 128 doubles
   double* h_in = nullptr;   // pinned, 16 x MAX_D doubles: host coordinates of bobe_gp_wip_grad's few-candidate path
 
-  // ---- classifier gate (gp_consumers.hip): support vectors SoA + dual coefficients on the device
-  DBuf gate_sv, gate_dual;
+  // ---- classifier gate (gp_consumers.hip): support vectors SoA + dual coefficients (SVM) or the transformed L and the
+  // centre (ellipsoid) on the device
+  DBuf gate_sv, gate_dual, gate_ell;
   bobe::Gate gate{nullptr, nullptr, 0, 0, 0.0, 0.0, 0.5, -1e5};
   void set_gate(const double* sv, int64_t n_sv, const double* dual, double intercept, double gamma, double threshold,
                 double minus_inf);
+  void set_gate_ellipsoid(const double* flat_L, const double* mu, double alpha, double beta, double threshold,
+                          double minus_inf);
+  // k_ellipsoid_train: n_restarts AdamW runs in one launch (host arrays; see bobe_gp.h)
+  DBuf ell_ws, ell_perm;
+  void train_ellipsoid(const double* X, const double* y, int64_t N, const double* mu, int n_restarts, const double* init,
+                       const int32_t* perm, int n_epochs, int batch, double lr, double wd, double* params_out,
+                       double* loss_out);
   // decision / feasibility of C device-resident query points (row-major C x d); with mean / var / dmean / dvar (device,
   // any may be null) the gated entries are overwritten: mean = -inf, var = 1e-12, gradients 0
   void gate_apply(const double* xq_dev, int64_t C, double* decision, double* feasible, double* mean, double* var,
-                  double* dmean, double* dvar);
+                  double* dmean, double* dvar, double* proba = nullptr);
   void gate_eval(const double* Xq, int64_t C, double* decision, double* feasible);
+  void gate_proba(const double* Xq, int64_t C, double* proba);
 
   // ---- launch plan of a factorisation (potrf): which panel launch carries which deferred update tiles, and from which
   // panel on every block column still has to be updated by each separate update launch.  Host logic only (a function of

@@ -257,7 +257,7 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
     }
   }
   // the classifier gate of the predict family (clf_gp.py:173-205): gated points get mean = -inf, var = 1e-12
-  if (gated && gate.n_sv > 0 && (d_mean || d_var)) gate_apply(cin, C, nullptr, nullptr, d_mean, d_var, nullptr, nullptr);
+  if (gated && gate_on(gate) && (d_mean || d_var)) gate_apply(cin, C, nullptr, nullptr, d_mean, d_var, nullptr, nullptr);
   o_misc.ensure(8 * sizeof(double));
   double* m_val = o_misc.d();                                        // [0],[1]
   int64_t* m_idx = reinterpret_cast<int64_t*>(o_misc.d() + 2);       // [2],[3]
@@ -464,7 +464,7 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
       LAUNCH_CHECK();
     }
     // (classifier gate, clf_gp.py:173-205: gated points carry mean = -inf and a zero gradient)
-    if (gate.n_sv > 0) gate_apply(cin, C, nullptr, nullptr, d_mean, nullptr, d_dm, nullptr);
+    if (gate_on(gate)) gate_apply(cin, C, nullptr, nullptr, d_mean, nullptr, d_dm, nullptr);
     out_finish(mean, C, o_mean);
     out_finish(dmean, (size_t)C * d, o_wipv);
     sync();
@@ -511,7 +511,7 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
 #undef PG
     LAUNCH_CHECK();
   }
-  if (gate.n_sv > 0) gate_apply(cin, C, nullptr, nullptr, d_mean, d_var, d_dm, d_dv);
+  if (gate_on(gate)) gate_apply(cin, C, nullptr, nullptr, d_mean, d_var, d_dm, d_dv);
   out_finish(mean, C, o_mean);
   out_finish(var, C, o_var);
   out_finish(dmean, (size_t)C * d, o_wipv);

@@ -1,5 +1,6 @@
 // Plain types shared by the kernels and the host side of libbobe_gp.so.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace bobe {
@@ -25,15 +26,27 @@ struct TriProb { int lo, mid, hi, off; };
 enum { FILL_TWIN = 1 };
 struct FillJob { int ti, tj, k0, k1, flags, pad0; };
 
-// The classifier gate of GPwithClassifier (clf_gp.py:173-205) with the SVM-RBF decision function of clf.py:188-213:
-//   decision(x) = sum_i dual[i] exp(-gamma |sv_i - x|^2) + intercept,  proba = decision >= 0,  feasible = proba >= threshold.
-// svT: support vectors SoA, coordinate j of vector i at svT[j * ld + i] (unit-cube coordinates, not scaled).  n_sv = 0: no gate.
+// The classifier gate of GPwithClassifier (clf_gp.py:173-205).  `kind` selects the decision function:
+//   GATE_SVM        SVM-RBF of clf.py:188-213: decision(x) = sum_i dual[i] exp(-gamma |sv_i - x|^2) + intercept,
+//                   proba = decision >= 0.  svT: support vectors SoA, coordinate j of vector i at svT[j * ld + i]
+//                   (unit-cube coordinates, not scaled).
+//   GATE_ELLIPSOID  the learned Mahalanobis ball of clf.py:377-412: decision(x) = logit = -alpha |L^T (x - mu)|^2 + beta,
+//                   proba = sigmoid(logit).  Lt: L with its diagonal already through softplus + 1e-4, dense row-major
+//                   d x d (L[i][j] at Lt[i * d + j], zero above the diagonal); mu: the centre (d).
+// feasible = proba >= threshold.  GATE_NONE: no gate (gate_on).
+enum GateKind { GATE_NONE = 0, GATE_SVM = 1, GATE_ELLIPSOID = 2 };
 struct Gate {
   const double* svT;
   const double* dual;
   int64_t ld;
   int n_sv;
   double intercept, gamma, threshold, minus_inf;
+  int kind;
+  const double* Lt;
+  const double* mu;
+  double alpha, beta;
 };
+// "a gate is set" - the one test every entry point uses (host and device)
+__host__ __device__ inline bool gate_on(const Gate& g) { return g.kind != GATE_NONE; }
 
 }  // namespace bobe

@@ -226,13 +226,16 @@ int bobe_gp_hmc_run(bobe_gp_t* g, int64_t P, double* state, double* adapt, const
 int bobe_gp_rwalk(bobe_gp_t* gp, int64_t P, double* X, double* logl, const double* step, double lstar, int walks,
                   uint64_t seed, double y_std, double y_mean, int* n_accepted, int* n_inside, double* dbg);
 
-/* GPwithClassifier's gate (clf_gp.py:173-205) with the SVM-RBF decision function of clf.py:188-213, evaluated on the
- * device by direct differences, as the reference computes it:
- *   decision(x) = sum_i dual_coef[i] exp(-gamma |support_vectors[i] - x|^2) + intercept      (svm_predict)
- *   proba(x)    = decision >= 0 ? 1 : 0                                                      (svm_predict_proba)
- *   feasible(x) = proba >= probability_threshold                                             (clf_gp.py:179)
- * support_vectors: n_sv x d (unit-cube coordinates), dual_coef: n_sv; scikit-learn's SVC supplies them (clf.py:36-69);
- * support_vectors == NULL or n_sv == 0 clears the gate.  While a gate is set, an infeasible query point comes back as
+/* GPwithClassifier's gate (clf_gp.py:173-205), evaluated on the device.  One gate per handle, of one of two kinds:
+ *  - SVM-RBF (clf.py:188-213), by direct differences, as the reference computes it (bobe_gp_set_gate):
+ *      decision(x) = sum_i dual_coef[i] exp(-gamma |support_vectors[i] - x|^2) + intercept   (svm_predict)
+ *      proba(x)    = decision >= 0 ? 1 : 0                                                   (svm_predict_proba)
+ *    support_vectors: n_sv x d (unit-cube coordinates), dual_coef: n_sv; scikit-learn's SVC supplies them (clf.py:36-69).
+ *  - ellipsoid (clf.py:377-412; bobe_gp_set_gate_ellipsoid):
+ *      decision(x) = logit = -alpha (x - mu)^T L L^T (x - mu) + beta,   proba(x) = sigmoid(logit)
+ *  feasible(x) = proba >= probability_threshold                                                 (clf_gp.py:179)
+ * support_vectors == NULL or n_sv == 0 clears the gate, whatever its kind.  While a gate is set, an infeasible query point
+ * comes back as
  *   bobe_gp_predict / bobe_gp_predict_grad   mean = -INFINITY (the mark for the wrapper, which returns minus_inf in the
  *                                            units of the method at hand: clf_gp.py:179 physical, :203 standardised),
  *                                            var = 1e-12 (clf_gp.py:189, 204), dmean = dvar = 0
@@ -241,12 +244,32 @@ int bobe_gp_rwalk(bobe_gp_t* gp, int64_t P, double* X, double* logl, const doubl
  *   bobe_gp_hmc_leapfrog / bobe_gp_hmc_run   mean = minus_inf (physical units), no mean gradient: never accepted
  *   bobe_gp_rwalk                            mean = minus_inf: never accepted
  * bobe_gp_wip_sweep, bobe_gp_fantasy_var and bobe_gp_wip_grad are NOT gated (fantasy_var is not, clf_gp.py:207-212).
- * One summation order serves every entry point (256 lane-strided partial sums, a fixed tree), so a point near the
- * boundary falls on the same side everywhere.  The gate is not part of the state bobe_gp_clone_state copies. */
+ * One summation order serves every entry point (256 partial sums, a fixed tree), so a point near the boundary falls on
+ * the same side everywhere.  The gate is not part of the state bobe_gp_clone_state copies. */
 int bobe_gp_set_gate(bobe_gp_t* gp, const double* support_vectors, int64_t n_sv, const double* dual_coef, double intercept,
                      double gamma, double probability_threshold, double minus_inf);
-/* decision[c] (svm_predict) and feasible[c] (1.0 / 0.0) of C query points; either output may be NULL. */
+/* The ellipsoid gate of the reference's parameters: flat_L (d(d+1)/2, the lower triangle in tril_indices order
+ * (0,0), (1,0), (1,1), (2,0), ...; RAW: the library puts the diagonal through softplus(.) + 1e-4 once), the centre mu
+ * (d), alpha, beta.  Host or device pointers. */
+int bobe_gp_set_gate_ellipsoid(bobe_gp_t* gp, const double* flat_L, const double* mu, double alpha, double beta,
+                               double probability_threshold, double minus_inf);
+/* decision[c] (svm_predict, or the ellipsoid's logit) and feasible[c] (1.0 / 0.0) of C query points; either output may
+ * be NULL. */
 int bobe_gp_gate_eval(bobe_gp_t* gp, const double* Xq, int64_t C, double* decision, double* feasible);
+/* proba[c]: the gate's probability (SVM 0 / 1, ellipsoid sigmoid(logit)) of C query points. */
+int bobe_gp_gate_proba(bobe_gp_t* gp, const double* Xq, int64_t C, double* proba);
+
+/* Training of the ellipsoid classifier (clf.py:415-472): n_restarts independent AdamW runs in ONE launch, one workgroup
+ * each.  Loss optax.sigmoid_binary_cross_entropy(logit, y).mean() over batches of B = min(batch, N) rows,
+ * steps = max(1, N / batch) per epoch; optax.adamw(lr, b1 0.9, b2 0.999, eps 1e-8, weight_decay = wd on every parameter).
+ *   X [N][d], y [N] (labels 0 / 1), mu [d] (the centre, not trained)
+ *   init [n_restarts][P] starting parameters, P = d(d+1)/2 + 2: raw flat_L, alpha, beta
+ *   perm [n_restarts][n_epochs][steps * B] int32 rows of every batch, each in [0, N) (checked)
+ *   params_out [n_restarts][P] the final parameters, loss_out [n_restarts] each run's full-data loss
+ * Host pointers.  Uses the handle's device, stream and dimension only (no data need be set). */
+int bobe_gp_train_ellipsoid(bobe_gp_t* gp, const double* X, const double* y, int64_t N, const double* mu, int n_restarts,
+                            const double* init, const int32_t* perm, int n_epochs, int batch, double lr, double wd,
+                            double* params_out, double* loss_out);
 
 /* GP.copy (gp.py:740-750) without leaving the device: dst (created with the same kernel, d and device) receives
  * src's training data, hyper-parameters and factorised state by device-to-device copies - no host round trip of the
