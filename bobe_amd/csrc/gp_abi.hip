@@ -556,6 +556,8 @@ int bobe_debug_time_potrf_lockstep(bobe_gp_t* g, int B, int reps, double* ms) {
   API_END
 }
 
+int bobe_debug_factor_source(bobe_gp_t* g) { return g ? g->factor_source : -1; }
+
 int bobe_gp_profile_select(bobe_gp_t* g, int tag) {
   API_BEGIN
   NEED(g, "gp is NULL");

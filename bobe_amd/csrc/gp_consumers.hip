@@ -342,6 +342,9 @@ void bobe_gp::clone_from(bobe_gp& src) {
   src.use();
   src.sync();
   sync();
+  ++data_gen;
+  forget_evals();
+  factor_source = -1;
   N = src.N;
   hyp = src.hyp;
   pivot_ulp = src.pivot_ulp;

@@ -54,7 +54,7 @@ void configure_factor_kernels() {
 
 const Tuning& tuning() {
   static Tuning t = [] {
-    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false};
+    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false, true};
     auto geti = [](const char* name, int& dst) {
       const char* e = std::getenv(name);
       if (e) dst = std::atoi(e);
@@ -69,6 +69,9 @@ const Tuning& tuning() {
     geti("BOBE_XCD_SHARES", v.xcd_shares);
     geti("BOBE_FILL", v.fill);
     v.trace = std::getenv("BOBE_TRACE") != nullptr;
+    int reuse = 1;
+    geti("BOBE_FACTOR_REUSE", reuse);
+    v.factor_reuse = reuse != 0;
     return v;
   }();
   return t;
@@ -178,6 +181,7 @@ void bobe_gp::alloc_for_n() {
   diag.ensure((size_t)nb * TILE * TILE * sizeof(double));
   build_probs();
   build_plans();
+  forget_evals();
 }
 
 void bobe_gp::scale(const double* in, int64_t n, int64_t npad, const Hyper& h, double* out, int64_t ldo,
@@ -684,6 +688,12 @@ void bobe_gp::mll_enqueue_body(const Hyper& h, bool want_grad, const Hyper* hdev
 }
 
 void bobe_gp::mll_enqueue(const Hyper& h, bool want_grad) {
+  tag2.clear();                             // (the workspace's factor is being overwritten; armed once the pipeline is queued)
+  mll_enqueue_pipeline(h, want_grad);
+  tag2.arm(h, data_gen, Np);
+}
+
+void bobe_gp::mll_enqueue_pipeline(const Hyper& h, bool want_grad) {
   const Tuning& tu = tuning();
   h_res[110] = pivot_floor(h);              // (host side of the pinned block, beyond what the device copy writes: read at collect)
   // Up to graph_max_n points an evaluation is tens of kernels of a few microseconds each, and with several slots
@@ -730,6 +740,7 @@ int bobe_gp::slot_collect(Slot& sl, double* mll, double* grad) {
   // touches only the slot's own stream and pinned results: safe while another thread submits to another slot
   HIPCHK(hipStreamSynchronize(sl.stream));
   const double* hr = sl.h_res;
+  sl.tag.collected(hr);
   int inf;
   std::memcpy(&inf, hr + 100, sizeof(int));
   if (inf != 0x7f7f7f7f || !pivots_resolved(hr[101], hr[110])) {
@@ -747,6 +758,7 @@ int bobe_gp::slot_collect(Slot& sl, double* mll, double* grad) {
 
 int bobe_gp::mll_collect(double* mll, double* grad) {
   sync();
+  tag2.collected(h_res);
   int inf;
   std::memcpy(&inf, h_res + 100, sizeof(int));
   if (inf != 0x7f7f7f7f || !pivots_resolved(h_res[101], h_res[110])) {
@@ -769,6 +781,8 @@ void bobe_gp::ensure_batch(int B) {
   }
   const size_t mat = (size_t)Np * Np * sizeof(double), vec = (size_t)Np * sizeof(double);
   const size_t nB = (size_t)B;
+  if (B > bw.cap || Np != bw.Np)          // (buffers reallocated or their slot stride changed)
+    for (bobe::EvalTag& t : bw.tag) t.clear();
   bw.A.ensure(nB * mat); bw.Linv.ensure(nB * mat); bw.Tmp.ensure(nB * mat);
   bw.XsT.ensure(nB * d * vec); bw.w.ensure(nB * vec); bw.alpha.ensure(nB * vec);
   bw.part.ensure(nB * nb * vec);
@@ -787,6 +801,7 @@ void bobe_gp::ensure_batch(int B) {
 void bobe_gp::mll_lockstep_enqueue(int B, const Hyper* hs, bool want_grad) {
   ensure_batch(B);
   const int64_t mat = Np * Np, vec = Np, xs = (int64_t)d * Np, prt = (int64_t)nb * Np, gps = gpart_stride();
+  for (int b = 0; b < B; ++b) bw.tag[b].clear();
   for (int b = 0; b < B; ++b) bw.h_hyp[b] = hs[b];
   HIPCHK(hipMemcpyAsync(bw.hyp.p, bw.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
   const Hyper* hdev = static_cast<const Hyper*>(bw.hyp.p);
@@ -810,6 +825,7 @@ void bobe_gp::mll_lockstep_enqueue(int B, const Hyper* hs, bool want_grad) {
   }
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(bw.h_res, bw.res.p, (size_t)B * 128 * sizeof(double), hipMemcpyDeviceToHost, stream));
+  for (int b = 0; b < B; ++b) bw.tag[b].arm(hs[b], data_gen, Np);
 }
 
 int bobe_gp::mll_lockstep_collect(int B, double* mll, double* grad, int* status) {
@@ -817,6 +833,7 @@ int bobe_gp::mll_lockstep_collect(int B, double* mll, double* grad, int* status)
   int worst = BOBE_OK;
   for (int b = 0; b < B; ++b) {
     const double* hr = bw.h_res + (size_t)b * 128;
+    bw.tag[b].collected(hr);
     double* gb = grad ? grad + (size_t)b * (d + 1) : nullptr;
     int st = BOBE_OK;
     int inf_b;
@@ -846,6 +863,8 @@ void bobe_gp::fill(double* p, int64_t n, double v) {
 void bobe_gp::set_data(const double* Xin, const double* ys, int64_t n) {
   use();
   sync();
+  ++data_gen;
+  forget_evals();
   const int64_t np_new = round_up(n, TILE);
   N = n;
   if (np_new != Np) {
@@ -865,18 +884,79 @@ void bobe_gp::set_data(const double* Xin, const double* ys, int64_t n) {
   forget_z();
 }
 
+void bobe_gp::forget_evals() {
+  tag2.clear();
+  for (Slot* sl : slots) sl->tag.clear();
+  for (bobe::EvalTag& t : bw.tag) t.clear();
+}
+
+// The fit has usually just evaluated the hyper-parameters bobe_gp_factor is asked for (the best restart's last iterate; the
+// benchmark's last theta): its workspace still holds L, Linv, alpha, w and the scaled coordinates, the bits factor_into would
+// compute again (2 ms at N = 4096).  A workspace whose record matches hyp bit for bit, the data generation and Np is copied
+// into the handle's buffers instead (k_copy_factor: the lower tiles, ~0.1 ms); anything else factorises.
+const bobe::EvalTag* bobe_gp::adopt_factor() {
+  if (!tuning().factor_reuse || in_slot) return nullptr;
+  auto match = [&](const bobe::EvalTag& t) { return t.valid && t.gen == data_gen && t.Np == Np && bobe::same_hyper(t.h, hyp); };
+  const size_t mat = (size_t)Np * Np, vec = (size_t)Np, xs = (size_t)d * Np;
+  const bobe::EvalTag* tag = nullptr;
+  const double *sA = nullptr, *sL = nullptr, *sal = nullptr, *sw = nullptr, *sx = nullptr;
+  int src = 0;
+  if (bw.Np == Np)
+    for (int b = 0; b < bw.cap && b < BOBE_MAX_MLL_SLOTS && !tag; ++b) {
+      const size_t b1 = (size_t)b + 1;
+      if (!match(bw.tag[b]) || bw.A.bytes < b1 * mat * 8 || bw.Linv.bytes < b1 * mat * 8 || bw.alpha.bytes < b1 * vec * 8 ||
+          bw.w.bytes < b1 * vec * 8 || bw.XsT.bytes < b1 * xs * 8)
+        continue;
+      tag = &bw.tag[b];
+      sA = bw.A.d() + b * mat; sL = bw.Linv.d() + b * mat; sal = bw.alpha.d() + b * vec; sw = bw.w.d() + b * vec;
+      sx = bw.XsT.d() + b * xs;
+      src = 1;
+    }
+  if (!tag) {
+    std::lock_guard<std::mutex> lock(submit_mutex);      // (the slot table grows under this mutex)
+    for (Slot* sl : slots)
+      if (!sl->busy && match(sl->tag)) {
+        tag = &sl->tag;
+        sA = sl->A2.d(); sL = sl->Linv2.d(); sal = sl->alpha2.d(); sw = sl->w2.d(); sx = sl->XsT2.d();
+        src = 2;
+        break;
+      }
+  }
+  if (!tag && match(tag2)) {
+    tag = &tag2;
+    sA = A2.d(); sL = Linv2.d(); sal = alpha2.d(); sw = w2.d(); sx = XsT2.d();
+    src = 3;
+  }
+  if (!tag) return nullptr;
+  const int vgroups = (int)std::min<int64_t>(64, ((int64_t)xs + 255) / 256);
+  hipLaunchKernelGGL(k_copy_factor, dim3((unsigned)(nb * (nb + 1) + vgroups)), dim3(256), 0, stream, sA, A.d(), sL, Linv.d(),
+                     nb, sal, alpha.d(), sw, w.d(), sx, XsT.d(), Np, (int64_t)xs);
+  LAUNCH_CHECK();
+  sync();
+  factor_source = src;
+  if (tuning().trace) std::fprintf(stderr, "[bobe] factor: adopted the factor of an evaluation (source %d)\n", src);
+  return tag;
+}
+
 int bobe_gp::factor_state() {
   use();
-  factor_into(hyp, XsT.d(), A.d(), Linv.d(), w.d(), alpha.d());
-  // the info word and the smallest pivot's root in one copy (k_mll_terms: res[100], res[101])
-  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w.d(), (const double*)A.d(), Np, Np, res.d(),
-                     (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(h_res, res.p, 102 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  sync();
   int inf;
-  std::memcpy(&inf, h_res + 100, sizeof(int));
-  const double min_diag = h_res[101];
+  double min_diag;
+  if (const bobe::EvalTag* t = adopt_factor()) {
+    inf = t->info;
+    min_diag = t->min_diag;
+  } else {
+    factor_into(hyp, XsT.d(), A.d(), Linv.d(), w.d(), alpha.d());
+    // the info word and the smallest pivot's root in one copy (k_mll_terms: res[100], res[101])
+    hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w.d(), (const double*)A.d(), Np, Np, res.d(),
+                       (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
+    LAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(h_res, res.p, 102 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    sync();
+    std::memcpy(&inf, h_res + 100, sizeof(int));
+    min_diag = h_res[101];
+    factor_source = 0;
+  }
   factored = true;
   forget_z();
   not_pd = (inf != 0x7f7f7f7f) || !pivots_resolved(min_diag, pivot_floor(hyp));
@@ -1050,6 +1130,9 @@ void bobe_gp::get_chol(double* L, double* alpha_out) {
 void bobe_gp::set_chol(const double* L, const double* alpha_in) {
   if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
   use();
+  ++data_gen;
+  forget_evals();
+  factor_source = -1;
   const double* l_in = fetch(L, (size_t)N * N, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, l_in, N,
                      A.d(), Np, Np);
@@ -1084,6 +1167,7 @@ double bobe_gp::min_pivot_root() {
 void bobe_gp::size_workspace(int64_t n) {
   if (have_data && n != N) throw Err(BOBE_ERR_STATE, "the handle holds training data of another size (use a data-less handle)");
   if (have_data) return;
+  ++data_gen;
   const int64_t np_new = round_up(n, TILE);
   N = n;
   if (np_new != Np) {
@@ -1099,6 +1183,7 @@ int bobe_gp::mll_from_k(const double* K, int64_t n, const double* yv, double* ml
   use();
   sync();
   size_workspace(n);
+  forget_evals();                                  // (A2 / Linv2 / w2 / alpha2 hold this matrix's factor from here on)
   const double* k_in = fetch(K, (size_t)n * n, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, k_in, n,
                      A2.d(), Np, Np, 1);
@@ -1131,6 +1216,7 @@ void bobe_gp::chol_row_update(const double* L, int64_t n, const double* k, doubl
   use();
   sync();
   size_workspace(n);
+  forget_evals();
   const double* l_in = fetch(L, (size_t)n * n, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, l_in, n,
                      A2.d(), Np, Np, 0);
@@ -1194,6 +1280,7 @@ struct EventPair {
 double bobe_gp::time_potrf(int reps) {
   if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
   use();
+  forget_evals();                                              // (the timers factorise into the evaluation workspaces)
   EventPair ev;
   double total = 0.0;
   scale(X.d(), N, Np, hyp, XsT2.d(), Np);
@@ -1214,6 +1301,7 @@ double bobe_gp::time_potrf(int reps) {
 double bobe_gp::time_potrf_batch(int B, int reps) {
   if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
   use();
+  forget_evals();
   ensure_slots(B);
   const std::vector<hipStream_t>& sts = slot_stream_set();
   EventPair ev;
@@ -1256,6 +1344,7 @@ double bobe_gp::time_potrf_batch(int B, int reps) {
 double bobe_gp::time_potrf_lockstep(int B, int reps) {
   if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
   use();
+  forget_evals();
   ensure_batch(B);
   const int64_t mat = Np * Np, xs = (int64_t)d * Np;
   for (int b = 0; b < B; ++b) bw.h_hyp[b] = hyp;

@@ -114,9 +114,10 @@ void allow_big_lds(K kernel, int bytes) {
 //   BOBE_XCD_SHARES     0: row-major tile order on every XCD (1)
 //   BOBE_FILL           deferred trailing updates in the panel launches: 0 off, 1 where they pay (potrf), 2 everywhere
 //   BOBE_TRACE          print launch plans and batch timings to stderr
+//   BOBE_FACTOR_REUSE   0: bobe_gp_factor always factorises, never adopts an evaluation's factor (1; for A/B runs)
 struct Tuning {
   int syrk32_below, trtri64_below, pair_min, lockstep_min_n, mll_slots, graph_max_n, xcd_shares, fill;
-  bool mll_slots_set, trace;
+  bool mll_slots_set, trace, factor_reuse;
 };
 const Tuning& tuning();
 
@@ -143,6 +144,43 @@ void configure_consumer_kernels();
 
 struct Depth { int first, count, nblocks; };
 
+// What an evaluation workspace (a lock-step batch slot, an evaluation slot, the single evaluation's own A2 / Linv2 / ...)
+// holds once its evaluation was collected: the factor of `h` on data generation `gen` at padded size `Np`, and the
+// factorisation's info word and smallest pivot root (res[100], res[101]).  The pipeline of an evaluation is factor_into's
+// on the same data (same bits in every form), and what follows it - lauum, k_mll_grad_reduce / k_mll_terms - writes only
+// Tmp, gpart and res: L (with its diagonal blocks back in place), Linv, alpha, w and the scaled coordinates stay intact
+// until the workspace is used again.  bobe_gp_factor adopts such a factor instead of recomputing it (factor_state).
+struct EvalTag {
+  bool pending = false;     // enqueued, not collected yet
+  bool valid = false;       // collected: info / min_diag are known
+  Hyper h;
+  uint64_t gen = 0;
+  int64_t Np = 0;
+  int info = 0;
+  double min_diag = 0.0;
+  void arm(const Hyper& hh, uint64_t g, int64_t np) {
+    valid = false;
+    pending = true;
+    h = hh;
+    gen = g;
+    Np = np;
+  }
+  void collected(const double* hr) {     // hr: the evaluation's pinned results ([100] info word, [101] min L_jj)
+    if (!pending) return;
+    pending = false;
+    valid = true;
+    std::memcpy(&info, hr + 100, sizeof(int));
+    min_diag = hr[101];
+  }
+  void clear() { pending = valid = false; }
+};
+// the same factor bit for bit: every field an evaluation's pipeline reads (ls[0..d), kvar, noise, d, kern)
+inline bool same_hyper(const Hyper& a, const Hyper& b) {
+  if (a.d != b.d || a.kern != b.kern || a.d < 0 || a.d > MAX_D) return false;
+  return std::memcmp(a.ls, b.ls, (size_t)a.d * sizeof(double)) == 0 && std::memcmp(&a.kvar, &b.kvar, sizeof(double)) == 0 &&
+         std::memcmp(&a.noise, &b.noise, sizeof(double)) == 0;
+}
+
 }  // namespace bobe
 
 struct bobe_gp {
@@ -156,6 +194,9 @@ struct bobe_gp {
   int64_t N = 0, Np = 0;
   int nb = 0;
   Hyper hyp;
+  // bumped by everything that changes X, y or N (set_data, append, set_chol, clone, a data-less workspace): an evaluation's
+  // factor of an older generation is never adopted
+  uint64_t data_gen = 0;
   double pivot_ulp = bobe::default_pivot_floor_ulp();     // the rank test's factor (0: sign test only, as dpotrf)
   double pivot_floor(const Hyper& h) const { return bobe::pivot_floor(h, pivot_ulp); }
   bool have_data = false, factored = false, not_pd = false;
@@ -262,8 +303,10 @@ struct bobe_gp {
     double* h_res = nullptr;
     hipEvent_t ev = nullptr;
     bool busy = false, want_grad = false;
+    bobe::EvalTag tag;
   };
   EvalGraph eg;                    // of the handle's own workspace (swapped with a slot's like the buffers)
+  bobe::EvalTag tag2;              // what the handle's own A2 / Linv2 / alpha2 / w2 / XsT2 hold (swapped like them)
   std::array<const void*, 16> eval_signature() const {
     return {XsT2.p, A2.p, Linv2.p, Tmp.p, w2.p, alpha2.p, part.p, gpart.p, res.p, info.p, X.p, y.p, probs.p,
             static_cast<const void*>(h_res), reinterpret_cast<const void*>(static_cast<uintptr_t>(N)),
@@ -282,6 +325,7 @@ struct bobe_gp {
     std::swap(res, s.res); std::swap(info, s.info); std::swap(flags, s.flags); std::swap(diag, s.diag);
     std::swap(h_res, s.h_res);
     std::swap(eg, s.eg);
+    std::swap(tag2, s.tag);
     in_slot = !in_slot;
   }
   // Lock-step batch workspace (bobe_gp_mll_batch; from BOBE_LOCKSTEP_MIN_N points up when that is set): the B evaluations of a batch go
@@ -293,6 +337,7 @@ struct bobe_gp {
     DBuf A, Linv, Tmp, XsT, w, alpha, part, gpart, res, info, hyp, diag;
     Hyper* h_hyp = nullptr;      // pinned [BOBE_MAX_MLL_SLOTS]
     double* h_res = nullptr;     // pinned [BOBE_MAX_MLL_SLOTS][128]
+    std::array<bobe::EvalTag, BOBE_MAX_MLL_SLOTS> tag;
   } bw;
   int64_t gpart_stride() const { return (int64_t)(2 * nb) * (2 * nb + 1) / 2 * (bobe::MAX_D + 1); }
   void ensure_batch(int B);
@@ -300,7 +345,8 @@ struct bobe_gp {
   int mll_lockstep_collect(int B, double* mll, double* grad, int* status);
   std::mutex submit_mutex;          // serialises bobe_gp_mll_submit (the slot swap is not re-entrant)
   void ensure_slots(int n);
-  void mll_enqueue(const Hyper& h, bool want_grad);
+  void mll_enqueue(const Hyper& h, bool want_grad);   // (records what the current workspace will hold: tag2)
+  void mll_enqueue_pipeline(const Hyper& h, bool want_grad);
   int slot_collect(Slot& sl, double* mll, double* grad);
   int mll_collect(double* mll, double* grad);
   int mll_batch(int64_t B, const double* ls, const double* kvar, double* mll, double* grad, int* status);
@@ -390,6 +436,13 @@ struct bobe_gp {
   int mll_from_k(const double* K, int64_t n, const double* yv, double* mll);
   void chol_row_update(const double* L, int64_t n, const double* k, double k_self, double* v, double* diag_out);
   int factor_state();                                  // bobe_gp_factor
+  // Adoption of an evaluation's factor by factor_state: forget_evals() drops every workspace's record (the data changed, a
+  // workspace was reallocated or used for something else); adopt_factor() copies a matching one into A / Linv / alpha / w /
+  // XsT and returns its tag (nullptr: none matches).  factor_source: where the installed factor came from
+  // (bobe_debug_factor_source: -1 none yet, 0 factorised, 1 lock-step batch slot, 2 evaluation slot, 3 single evaluation)
+  void forget_evals();
+  const bobe::EvalTag* adopt_factor();
+  int factor_source = -1;
   void copy_out_matrix(const double* src, double* dst, int lower_only);
   void get_chol(double* L, double* alpha_out);
   void set_chol(const double* L, const double* alpha_in);

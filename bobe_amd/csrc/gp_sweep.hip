@@ -531,6 +531,9 @@ int bobe_gp::append(const double* X_new, int64_t b, const double* y_all) {
   factored = false;
   have_data = false;
   forget_z();
+  ++data_gen;                           // (no evaluation's factor belongs to the grown data)
+  forget_evals();
+  factor_source = -1;
   DBuf nx, oa, ol;
   try {
   // ---- training data: X gains b rows, every y changes (the caller re-standardised them, gp.py:520-536)

@@ -374,6 +374,40 @@ static __global__ void k_fill(double* __restrict__ p, int64_t n, double v) {
   if (i < n) p[i] = v;
 }
 
+// An evaluation's factor into the handle's buffers (bobe_gp::adopt_factor), one launch: workgroups [0, 2T) copy the T =
+// nb (nb + 1) / 2 lower 128 x 128 tiles of L (sA -> dA) and then of Linv (sL -> dL) - every element a factorisation writes;
+// the rest stride over alpha and w (np each) and the scaled coordinates (nx).  ld = np, a multiple of 128.
+static __global__ __launch_bounds__(256) void k_copy_factor(const double* __restrict__ sA, double* __restrict__ dA,
+                                                            const double* __restrict__ sL, double* __restrict__ dL, int nb,
+                                                            const double* __restrict__ sal, double* __restrict__ dal,
+                                                            const double* __restrict__ sw, double* __restrict__ dw,
+                                                            const double* __restrict__ sx, double* __restrict__ dx, int64_t np,
+                                                            int64_t nx) {
+  const int T = nb * (nb + 1) / 2;
+  int t = (int)blockIdx.x;
+  if (t < 2 * T) {
+    const double* s = t < T ? sA : sL;
+    double* o = t < T ? dA : dL;
+    t = t < T ? t : t - T;
+    int ti = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);       // tile (ti, tj), tj <= ti, row-major over the lower triangle
+    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    while (ti * (ti + 1) / 2 > t) --ti;
+    const int tj = t - ti * (ti + 1) / 2;
+    const int64_t base = (int64_t)ti * TILE * np + (int64_t)tj * TILE;
+    for (int e = threadIdx.x; e < TILE * TILE / 2; e += 256) {   // 128 rows of 64 double2
+      const int64_t off = base + (int64_t)(e / (TILE / 2)) * np + 2 * (e % (TILE / 2));
+      *reinterpret_cast<double2*>(o + off) = *reinterpret_cast<const double2*>(s + off);
+    }
+    return;
+  }
+  const int64_t stride = (int64_t)(gridDim.x - 2 * T) * 256;
+  for (int64_t i = (int64_t)(blockIdx.x - 2 * T) * 256 + threadIdx.x; i < np; i += stride) {
+    dal[i] = sal[i];
+    dw[i] = sw[i];
+  }
+  for (int64_t i = (int64_t)(blockIdx.x - 2 * T) * 256 + threadIdx.x; i < nx; i += stride) dx[i] = sx[i];
+}
+
 // dst[i*ldd + j] = (lower_only && j > i) ? 0 : src[i*lds + j]  for i < rows, j < cols
 static __global__ void k_copy2d(const double* __restrict__ src, int64_t lds, double* __restrict__ dst, int64_t ldd, int64_t rows,
                          int64_t cols, int lower_only) {

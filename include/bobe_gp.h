@@ -327,6 +327,10 @@ int bobe_debug_time_potrf(bobe_gp_t* gp, int reps, double* ms);
 int bobe_debug_time_potrf_batch(bobe_gp_t* gp, int B, int reps, double* ms);
 /* the same B factorisations advancing in lock step through one batched launch sequence on the handle's stream */
 int bobe_debug_time_potrf_lockstep(bobe_gp_t* gp, int B, int reps, double* ms);
+/* where the factor of the last bobe_gp_factor came from: 0 factorised; adopted from the workspace of an evaluation at the
+ * same hyper-parameters and data - 1 a lock-step batch slot (bobe_gp_mll_batch), 2 an evaluation slot (bobe_gp_mll_submit),
+ * 3 the single evaluation's (bobe_gp_mll); -1 no bobe_gp_factor since the data or the factor was last set otherwise */
+int bobe_debug_factor_source(bobe_gp_t* gp);
 /* Per-kernel-class device timing with HIP events recorded on the handle's stream around every launch
  * of the selected class (0 = off).  read() synchronises, returns the summed milliseconds and the
  * number of launches since the last select()/read(), and resets the counters. */
