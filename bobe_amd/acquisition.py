@@ -215,9 +215,10 @@ class WIPStd(WeightedIntegratedPosteriorBase):
 
 
 def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, method="NUTS", num_chains=4,
-                   np_rng=None, rng_key=None):
+                   np_rng=None, rng_key=None, *, sampler="hmc"):
     """BOBE/acquisition.py:468-482: 'NUTS' (Hamiltonian Monte Carlo on the surrogate, batched on the GPU), 'NS'
-    (nested sampling on the surrogate) or 'uniform' (scrambled Sobol)."""
+    (nested sampling on the surrogate) or 'uniform' (scrambled Sobol).  ``sampler`` picks the chains of 'NUTS':
+    'hmc' (the default) or 'nuts' (No-U-Turn transitions on the device, ``sample_GP_NUTS``)."""
     if method == "uniform":
         return {"x": qmc.Sobol(gp.ndim, scramble=True, seed=np_rng).random(num_samples)}
     if method == "NS":                                   # acquisition.py:473-475, batched on the GPU GP
@@ -229,7 +230,7 @@ def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, metho
         from .samplers import sample_GP_NUTS
         rng = np_rng if isinstance(np_rng, np.random.Generator) else np.random.default_rng(np_rng)
         return sample_GP_NUTS(gp, np_rng=rng, rng_key=rng_key, num_chains=num_chains, warmup_steps=warmup_steps,
-                              num_samples=num_samples, thinning=thinning)
+                              num_samples=num_samples, thinning=thinning, sampler=sampler)
     raise ValueError(f"Unknown method {method} for sampling GP")          # acquisition.py:481
 
 

@@ -206,7 +206,7 @@ class BOBE:
         self.convergence_n_iters, self.ei_goal_log, self.do_final_ns = 1, float(np.log(1e-10)), False
         self.num_hmc_warmup, self.num_hmc_samples, self.mc_points_size = 512, 512, 64
         self.hmc_thinning, self.hmc_num_chains, self.mc_points_method, self.zeta_ei = 4, 4, "NUTS", 0.01
-        self.num_mc_samples, self.acq_threshold, self.verbose = 1024, None, False
+        self.num_mc_samples, self.acq_threshold, self.verbose, self.mc_sampler = 1024, None, False, "hmc"
         self.min_delta_seen = np.inf
         self.current_iteration = 0
         self.start_iteration = 0
@@ -551,10 +551,12 @@ class BOBE:
             do_final_ns: bool = False, fit_n_points: int = 10, batch_size: int = 4, ns_n_points: int = 10,
             num_hmc_warmup: int = 512, num_hmc_samples: int = 512, mc_points_size: int = 64, thinning: int = 4,
             num_chains: int = 4, mc_points_method: str = "NUTS", zeta_ei: float = 0.01, *,
-            num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False) -> dict:
+            num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
+            mc_sampler: str = "hmc") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
-        optional ``acq_threshold`` stop, ``verbose``.  ``acq`` may be a tuple of stages, run one after the other on the
+        optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
+        'hmc' (default) or 'nuts' (``sample_GP_NUTS(sampler="nuts")``).  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -577,6 +579,9 @@ class BOBE:
         self.hmc_thinning, self.hmc_num_chains, self.mc_points_method = thinning, num_chains, mc_points_method
         self.zeta_ei = zeta_ei
         self.num_mc_samples, self.acq_threshold, self.verbose = num_mc_samples, acq_threshold, verbose
+        if mc_sampler not in ("hmc", "nuts"):
+            raise ValueError(f"mc_sampler must be 'hmc' or 'nuts', not {mc_sampler!r}")
+        self.mc_sampler = mc_sampler
         self.converged, self.convergence_counter = False, 0
         self.min_delta_seen = np.inf
         self.termination_reason = "Max evaluation budget reached"          # bo.py:1118
@@ -687,7 +692,7 @@ class BOBE:
         if self.mc_points_method == "NUTS":
             mc = get_mc_samples(self.gp, warmup_steps=self.num_hmc_warmup, num_samples=self.num_hmc_samples,
                                 thinning=self.hmc_thinning, method="NUTS", num_chains=self.hmc_num_chains,
-                                np_rng=self.np_rng)
+                                np_rng=self.np_rng, sampler=self.mc_sampler)
         else:
             mc = get_mc_samples(self.gp, num_samples=self.num_mc_samples, method=self.mc_points_method,
                                 np_rng=self.np_rng)
@@ -785,7 +790,7 @@ class BOBE:
         else:
             t0 = time.time()
             hm = get_mc_samples(self.gp, warmup_steps=512, num_samples=2000 * self.ndim, thinning=4, method="NUTS",
-                                np_rng=self.np_rng)
+                                np_rng=self.np_rng, sampler=self.mc_sampler)
             self.timing["MCMC Sampling"] += time.time() - t0
             x_u = hm["x"]
             weights = hm["weights"] if "weights" in hm else np.ones(hm["x"].shape[0])

@@ -235,14 +235,15 @@ struct ChainRows {
   static constexpr int HMC = DCAP == 8 ? 14 : (DCAP == 16 ? 6 : 2);
   static constexpr int WALK = DCAP == 8 ? 16 : (DCAP == 16 ? 8 : 4);
   static constexpr int STREAM = DCAP == 32 ? 1 : 2;      // streamed rows in flight per thread
+  static constexpr int NUTS = DCAP == 8 ? 10 : (DCAP == 16 ? 3 : 1);   // (k_nuts_run: its tree needs ~50 more registers)
 };
 // ... and as many more as the CU's LDS holds next to them: groups of 256 rows of d coordinates + alpha, [d + 1][rows]
 // (a lane reads consecutive doubles: no bank conflicts).  Host side: the group count for n points and `resident` register rows.
 constexpr int CHAIN_LDS_BYTES = 148 * 1024;                            // (of 160 KB: the kernels' static arrays stay below 10 KB)
-inline int chain_lds_groups(int64_t n, int d, int resident) {
+inline int chain_lds_groups(int64_t n, int d, int resident, int bytes = CHAIN_LDS_BYTES) {
   const int64_t left = n - 256 * (int64_t)resident;
   if (left <= 0) return 0;
-  const int64_t cap = CHAIN_LDS_BYTES / (8 * (int64_t)(d + 1)) / 256;
+  const int64_t cap = bytes / (8 * (int64_t)(d + 1)) / 256;
   const int64_t want = (left + 255) / 256;
   return (int)(want < cap ? want : cap);
 }
@@ -484,6 +485,362 @@ __global__ __launch_bounds__(256) void k_hmc_run(const double* __restrict__ XsT,
   }
 }
 
+// ---- No-U-Turn sampling on the device (NumPyro's NUTS, the reference's sampler: samplers.py:216-330) ---------------
+// `niter` NUTS transitions of every chain in ONE launch, one 256-thread workgroup per chain; the target, the state layout
+// and the one-point evaluation (training points in registers / LDS / streamed, the mean and gradient reduction order, the
+// gate) are those of k_hmc_run.  The code is duplicated rather than shared, so that k_hmc_run's instruction stream stays
+// exactly what it was.
+//
+// Contract (tests/nuts_restatement.py restates it in NumPy):
+//   Metric.  Sigma = the d x d inverse metric, C = lower Cholesky factor of M = Sigma^-1 (both from the host).  Momentum
+//     p = C z, z ~ N(0, I); kinetic energy K(p) = 1/2 p^T Sigma p; velocity Sigma p.  H = -logp + K, H0 at the start.
+//   Leaf.  One velocity-Verlet step of signed size e (+eps going right, -eps going left) from the tree's edge in that
+//     direction (from the previous leaf inside a subtree): p' = p + e/2 g(u); u += e Sigma p'; p = p' + e/2 g(u).
+//     dH = H - H0 (NaN -> +inf); log weight w = -dH; acceptance min(1, exp(-dH)); divergent if dH > 1000 or dH is not
+//     finite (a gated leaf has mean minus_inf: at the default -1e5 it is divergent).
+//   Tree (iterative_build_tree of NumPyro, Betancourt 2017 appendix A).  Start: one node, the current state, weight 0,
+//     rho = p0.  Doubling j = 0, 1, ... while j < max_tree_depth and the tree neither turned nor diverged:
+//     direction bit b_j; a subtree of up to 2^j leaves k = 0, 1, ... is built leaf by leaf:
+//       - progressive sampling: leaf 0 is the subtree's proposal; leaf k > 0 replaces it when its uniform is below
+//         exp(w_k - logaddexp(W_sub, w_k)); then W_sub = logaddexp(W_sub, w_k), rho_sub += p_k;
+//       - checkpoints (Stan / NumPyro): at even k, slot popcount(k >> 1) keeps p_k, Sigma p_k and rho_sub; at odd k the
+//         completed sub-subtrees ending at k are checked, slots i = popcount(k >> 1) down to that minus (trailing ones of
+//         k) + 1: with r = rho_sub - rho_ck[i] + p_ck[i] - (p_ck[i] + p_k) / 2, the subtree turned if
+//         (Sigma p_ck[i]) . r <= 0 or (Sigma p_k) . r <= 0;
+//       - the subtree stops at 2^j leaves, at a turned check or at a divergent leaf.
+//     Merge: unless the subtree turned or diverged, its proposal replaces the tree's when the merge uniform is below
+//     min(1, exp(W_sub - W)) (biased progressive sampling); W = logaddexp(W, W_sub), rho += rho_sub, the edge in direction
+//     b_j becomes the subtree's last leaf, depth = j + 1; the whole tree turned if the subtree did or, with
+//     r = rho - (p_left + p_right) / 2, (Sigma p_left) . r <= 0 or (Sigma p_right) . r <= 0.
+//   Transition: the tree's proposal is the next state.  Acceptance statistic = mean over all leaves built of
+//     min(1, exp(-dH)); it drives k_hmc_run's per-chain dual averaging (target 0.8) while adapting.
+//   Random numbers: ikey = ckey + ((it0 + iteration) << 14), ckey as in k_hmc_run; index 2t, 2t + 1 -> Box-Muller normal
+//     z_t; 64 + j -> direction of doubling j (top bit: 1 = right); 128 + 1024 j -> the merge uniform of doubling j;
+//     128 + 1024 j + k -> the selection uniform of leaf k >= 1 of subtree j.
+// Control flow: every lane of wave 0 (which holds the d <= 32 coordinate threads) computes the same scalars from the same
+// wave sums and decides; thread 0 publishes "stop" through LDS, and every barrier sits under a loop condition read from
+// there, i.e. a workgroup-uniform one.
+//   metric [2][d][d]  Sigma, then C (row-major, C lower)
+//   stats  [niter][P][4]  tree depth, leapfrog steps, divergent flag, acceptance statistic        (may be null)
+//   dbg    [P][d]         last transition's momentum draw p0                                       (may be null)
+//   S, adapt, hist, keep as k_hmc_run.
+constexpr int NUTS_MAX_DEPTH = 10;
+constexpr int NUTS_LDS_BYTES = 138 * 1024;             // (the static arrays: Sigma, checkpoints, ... stay below 22 KB)
+
+__device__ __forceinline__ double nuts_logaddexp(double a, double b) {
+  const double hi = a > b ? a : b, lo = a > b ? b : a;
+  if (hi == -INFINITY) return hi;
+  return hi + log1p(exp(lo - hi));
+}
+
+template <int KERN, int DCAP>
+__global__ __launch_bounds__(256) void k_nuts_run(const double* __restrict__ XsT, int64_t ldx, int64_t n,
+                                                  const double* __restrict__ alpha, Hyper h, int64_t P,
+                                                  double* __restrict__ S, double* __restrict__ adapt,
+                                                  const double* __restrict__ metric, int max_depth,
+                                                  unsigned long long seed, int64_t it0, int niter, int do_adapt,
+                                                  double ystd, double ymean, double temp, int hist_from,
+                                                  double* __restrict__ hist, int thin, double* __restrict__ keep,
+                                                  double* __restrict__ stats, double* __restrict__ dbg, Gate gt,
+                                                  int lgroups) {
+  constexpr int NT = 256, NW = NT / 64, SLD = DCAP + 1;
+  extern __shared__ double lrows[];            // [d + 1][256 lgroups]: training points resident in LDS (chain_lds_groups)
+  __shared__ double x[DCAP], xs[DCAP], red[NW][DCAP + 1], gred[4];
+  __shared__ double sig[DCAP * SLD], zb[DCAP], pv[DCAP], phs[DCAP];
+  __shared__ double ck_p[NUTS_MAX_DEPTH][DCAP], ck_v[NUTS_MAX_DEPTH][DCAP], ck_r[NUTS_MAX_DEPTH][DCAP];
+  __shared__ int stop_leaf, stop_tree;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t c = blockIdx.x;
+  const int d = h.d, sw = 3 * d + 2;
+  const bool own = t < d;                      // coordinate thread (all of them in wave 0)
+  double* Sc = S + c * sw;
+  double* ad = adapt + c * 5;
+  for (int i = t; i < d * d; i += NT) sig[(i / d) * SLD + i % d] = metric[i];
+  const double* Crow = metric + (int64_t)d * d + (int64_t)(own ? t : 0) * d;
+  // chain state: coordinates in the registers of their thread, scalars in every lane of wave 0
+  double u0 = 0.0, g0 = 0.0, x0 = 0.0, lp0 = 0.0, mean0 = 0.0;
+  double a_eps = 0.0, a_mu = 0.0, a_hbar = 0.0, a_leb = 0.0, a_m = 0.0;
+  if (own) {
+    u0 = Sc[t];
+    g0 = Sc[d + t];
+    x0 = Sc[2 * d + t];
+  }
+  if (wave == 0) {
+    lp0 = Sc[3 * d];
+    mean0 = Sc[3 * d + 1];
+    a_eps = ad[0];
+    a_mu = ad[1];
+    a_hbar = ad[2];
+    a_leb = ad[3];
+    a_m = ad[4];
+  }
+  const unsigned long long ckey = hmc_mix64(seed ^ hmc_mix64((unsigned long long)c));
+  constexpr int RMAX = ChainRows<DCAP>::NUTS, UNR = ChainRows<DCAP>::STREAM;
+  const int nrow = (int)((n + NT - 1) / NT);
+  const int lld = NT * lgroups;
+  double cx[RMAX][DCAP], ca[RMAX];
+#pragma unroll
+  for (int r = 0; r < RMAX; ++r) {
+    const int64_t i = t + NT * r;
+    ca[r] = (i < n) ? alpha[i] : 0.0;
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) cx[r][j] = (j < d && i < n) ? XsT[j * ldx + i] : 0.0;
+  }
+  for (int q = 0; q < lgroups; ++q) {
+    const int64_t i = t + (int64_t)NT * (RMAX + q);
+    for (int j = 0; j < d; ++j) lrows[j * lld + q * NT + t] = (i < n) ? XsT[j * ldx + i] : 0.0;
+    lrows[d * lld + q * NT + t] = (i < n) ? alpha[i] : 0.0;
+  }
+  __syncthreads();
+  const double inv_ls = own ? 1.0 / h.ls[t] : 0.0;
+  auto sig_dot = [&](const double* vec) {                    // row t of Sigma against a vector in LDS
+    double s = 0.0;
+    for (int q = 0; q < d; ++q) s = fma(sig[t * SLD + q], vec[q], s);
+    return s;
+  };
+  // the surrogate at x / xs (LDS): every thread's training points, then the waves' sums (k_hmc_run's arithmetic and
+  // order); ends with a barrier, after which wsum() / the gate's decision can be read
+  auto evaluate = [&]() {
+    double ms = 0.0, gm[DCAP];
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) gm[j] = 0.0;
+    auto point = [&](const double (&xr)[DCAP], double a) {
+      double r2 = 0.0;
+#pragma unroll
+      for (int j = 0; j < DCAP; ++j) {
+        const double df = (j < d) ? xr[j] - xs[j] : 0.0;
+        r2 += df * df;
+      }
+      const double kv = kern_eval<KERN>(r2, h.kvar);
+      const double ag = a * kern_grad_factor<KERN>(r2, h.kvar, kv);
+      ms += a * kv;
+#pragma unroll
+      for (int j = 0; j < DCAP; ++j) gm[j] += ag * ((j < d) ? xr[j] - xs[j] : 0.0);
+    };
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r)
+      if (r < nrow) point(cx[r], ca[r]);
+    for (int q = 0; q < lgroups; ++q) {
+      double xr[DCAP];
+#pragma unroll
+      for (int j = 0; j < DCAP; ++j) xr[j] = (j < d) ? lrows[j * lld + q * NT + t] : 0.0;
+      point(xr, lrows[d * lld + q * NT + t]);
+    }
+    for (int64_t i = t + (int64_t)NT * (RMAX + lgroups); i < n; i += UNR * NT) {
+      double xr[UNR][DCAP], ar[UNR];
+#pragma unroll
+      for (int q = 0; q < UNR; ++q) {
+        const int64_t iq = i + q * NT;
+        ar[q] = (iq < n) ? alpha[iq] : 0.0;
+#pragma unroll
+        for (int j = 0; j < DCAP; ++j) xr[q][j] = (j < d && iq < n) ? XsT[j * ldx + iq] : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < UNR; ++q) point(xr[q], ar[q]);
+    }
+    ms = chain_wave_sum(ms);
+    if (lane == 0) red[wave][DCAP] = ms;
+    {
+      const double v = wave_sum_components<DCAP>(gm, lane);
+      if ((lane & (64 / DCAP - 1)) == 0) red[wave][lane / (64 / DCAP)] = v;
+    }
+    if (gate_on(gt)) {
+      const double gs = gate_partial<DCAP>(gt, x, d, t);
+      if (lane == 0) gred[wave] = gs;
+    }
+    __syncthreads();
+  };
+  auto wsum = [&](int j) {
+    double sres = red[0][j];
+#pragma unroll
+    for (int w_ = 1; w_ < NW; ++w_) sres += red[w_][j];
+    return sres;
+  };
+  for (int it = 0; it < niter; ++it) {
+    const unsigned long long ikey = ckey + ((unsigned long long)(it0 + it) << 14);
+    const double eps = a_eps;
+    // momentum p0 = C z and its velocity
+    if (own) {
+      const double a = hmc_u01(hmc_mix64(ikey + 2 * t)), b = hmc_u01(hmc_mix64(ikey + 2 * t + 1));
+      zb[t] = sqrt(-2.0 * log(a)) * cos(6.283185307179586 * b);
+    }
+    __syncthreads();
+    double p0 = 0.0;
+    if (own) {
+      for (int q = 0; q <= t; ++q) p0 = fma(Crow[q], zb[q], p0);
+      pv[t] = p0;
+    }
+    __syncthreads();
+    // the tree (wave 0): edges, momentum sum, proposal; scalars identical in every lane of wave 0
+    double v0 = own ? sig_dot(pv) : 0.0;
+    double H0 = 0.0;
+    if (wave == 0) H0 = -lp0 + 0.5 * chain_wave_sum(p0 * v0);
+    double uL = u0, pL = p0, gL = g0, vL = v0, uR = u0, pR = p0, gR = g0, vR = v0, rho = p0;
+    double uP = u0, gP = g0, xP = x0, lpP = lp0, meanP = mean0;
+    double W = 0.0, sum_acc = 0.0;
+    int nleap = 0, depth = 0;
+    bool diverged = false;
+    double u = 0.0, p = 0.0, g = 0.0, xv = 0.0, v = 0.0;
+    for (int j = 0; j < max_depth; ++j) {
+      const bool right = (hmc_mix64(ikey + 64 + (unsigned long long)j) >> 63) != 0;
+      const double e = right ? eps : -eps;
+      const int nleaf = 1 << j;
+      double rs = 0.0, uS = 0.0, gS = 0.0, xS = 0.0, lpS = 0.0, meanS = 0.0, Ws = -INFINITY;
+      bool tsub = false;
+      if (own) {
+        u = right ? uR : uL;
+        p = right ? pR : pL;
+        g = right ? gR : gL;
+        phs[t] = p + 0.5 * e * g;
+      }
+      __syncthreads();
+      for (int k = 0; k < nleaf; ++k) {
+        if (own) {                                             // position half of the leapfrog step
+          u += e * sig_dot(phs);
+          double xx = 1.0 / (1.0 + exp(-u));
+          xx = xx < 1e-12 ? 1e-12 : (xx > 1.0 - 1e-12 ? 1.0 - 1e-12 : xx);
+          xv = xx;
+          x[t] = xx;
+          xs[t] = xx * inv_ls;
+        }
+        __syncthreads();
+        evaluate();
+        const bool ok = gate_on(gt) ? gate_feasible(gt, gate_combine(gt, gred)) : true;
+        if (own) {                                             // gradient and momentum
+          const double dm = ok ? wsum(t) * inv_ls : 0.0;
+          g = dm * ystd / temp * (xv * (1.0 - xv)) + (1.0 - 2.0 * xv);
+          p = phs[t] + 0.5 * e * g;
+          pv[t] = p;
+        }
+        __syncthreads();
+        if (wave == 0) {
+          v = own ? sig_dot(pv) : 0.0;
+          const double kin = chain_wave_sum(p * v);
+          const double jl = chain_wave_sum(own ? log(xv) + log1p(-xv) : 0.0);
+          const double m = ok ? wsum(DCAP) * ystd + ymean : gt.minus_inf;
+          const double lp = m / temp + jl;
+          double dH = (0.5 * kin - lp) - H0;
+          if (dH != dH) dH = INFINITY;
+          const double w = -dH;
+          const bool dvg = !isfinite(dH) || dH > 1000.0;
+          sum_acc += dH <= 0.0 ? 1.0 : exp(-dH);
+          ++nleap;
+          bool take = k == 0;
+          if (k == 0) {
+            Ws = w;
+          } else {
+            const double Wn = nuts_logaddexp(Ws, w);
+            take = hmc_u01(hmc_mix64(ikey + 128 + 1024 * (unsigned long long)j + k)) < exp(w - Wn);
+            Ws = Wn;
+          }
+          if (take) {
+            uS = u;
+            gS = g;
+            xS = xv;
+            lpS = lp;
+            meanS = m;
+          }
+          rs += p;
+          const int imax = __popc((unsigned)k >> 1);
+          if ((k & 1) == 0) {
+            if (own) {
+              ck_p[imax][t] = p;
+              ck_v[imax][t] = v;
+              ck_r[imax][t] = rs;
+            }
+          } else {
+            const int imin = imax - __builtin_ctz(~(unsigned)k) + 1;
+            for (int i = imax; i >= imin && !tsub; --i) {      // (a lane reads back only its own coordinate)
+              const double r = own ? rs - ck_r[i][t] + ck_p[i][t] - 0.5 * (ck_p[i][t] + p) : 0.0;
+              const double a = chain_wave_sum(own ? ck_v[i][t] * r : 0.0), b = chain_wave_sum(v * r);
+              tsub = a <= 0.0 || b <= 0.0;
+            }
+          }
+          diverged = dvg;
+          if (t == 0) stop_leaf = dvg || tsub;
+          if (own) phs[t] = p + 0.5 * e * g;                   // the next leaf starts here
+        }
+        __syncthreads();
+        if (stop_leaf) break;
+      }
+      if (wave == 0) {                                         // merge the subtree into the tree
+        const bool usable = !tsub && !diverged;
+        const double pr = usable ? (Ws >= W ? 1.0 : exp(Ws - W)) : 0.0;
+        if (hmc_u01(hmc_mix64(ikey + 128 + 1024 * (unsigned long long)j)) < pr) {
+          uP = uS;
+          gP = gS;
+          xP = xS;
+          lpP = lpS;
+          meanP = meanS;
+        }
+        W = nuts_logaddexp(W, Ws);
+        rho += rs;
+        if (right) {
+          uR = u; pR = p; gR = g; vR = v;
+        } else {
+          uL = u; pL = p; gL = g; vL = v;
+        }
+        depth = j + 1;
+        const double r = own ? rho - 0.5 * (pL + pR) : 0.0;
+        const double a = chain_wave_sum(vL * r), b = chain_wave_sum(vR * r);
+        const bool turned = tsub || a <= 0.0 || b <= 0.0;
+        if (t == 0) stop_tree = turned || diverged;
+      }
+      __syncthreads();
+      if (stop_tree) break;
+    }
+    if (wave == 0) {                                           // the transition and the chain's step-size update
+      u0 = uP;
+      g0 = gP;
+      x0 = xP;
+      lp0 = lpP;
+      mean0 = meanP;
+      const double ap = sum_acc / (double)nleap;
+      if (do_adapt) {
+        constexpr double t0 = 10.0, gamma = 0.05, kappa = 0.75, target = 0.8;
+        const double m = a_m + 1.0;
+        const double hbar = (1.0 - 1.0 / (m + t0)) * a_hbar + (target - ap) / (m + t0);
+        const double le = a_mu - sqrt(m) / gamma * hbar;
+        const double eta = pow(m, -kappa);
+        a_hbar = hbar;
+        a_leb = eta * le + (1.0 - eta) * a_leb;
+        a_m = m;
+        double e = exp(le);
+        e = e < 1e-4 ? 1e-4 : (e > 2.0 ? 2.0 : e);
+        a_eps = e;
+      }
+      if (t == 0 && stats) {
+        double* sc = stats + ((int64_t)it * P + c) * 4;
+        sc[0] = (double)depth;
+        sc[1] = (double)nleap;
+        sc[2] = diverged ? 1.0 : 0.0;
+        sc[3] = ap;
+      }
+      if (own) {
+        if (dbg && it == niter - 1) dbg[c * d + t] = p0;
+        if (hist && it >= hist_from) hist[((int64_t)(it - hist_from) * P + c) * d + t] = u0;
+        if (keep && (it + 1) % thin == 0) keep[((int64_t)((it + 1) / thin - 1) * P + c) * (d + 1) + t] = x0;
+      }
+      if (t == 0 && keep && (it + 1) % thin == 0) keep[((int64_t)((it + 1) / thin - 1) * P + c) * (d + 1) + d] = mean0;
+    }
+    // (no barrier here: zb is next written after every reader has passed two barriers, pv / phs after one more)
+  }
+  if (own) {
+    Sc[t] = u0;
+    Sc[d + t] = g0;
+    Sc[2 * d + t] = x0;
+  }
+  if (t == 0) {
+    Sc[3 * d] = lp0;
+    Sc[3 * d + 1] = mean0;
+    if (do_adapt) {
+      ad[0] = a_eps;
+      ad[2] = a_hbar;
+      ad[3] = a_leb;
+      ad[4] = a_m;
+    }
+  }
+}
 
 // ---- constrained random walks for nested sampling, whole walks on the device -----------------------------------------
 // The replacement search of a nested-sampling iteration (dynesty's 'rwalk', the reference's choice: samplers.py:64, 152):

@@ -319,6 +319,21 @@ int bobe_gp_hmc_run(bobe_gp_t* g, int64_t P, double* state, double* adapt, const
   API_END
 }
 
+int bobe_gp_nuts_run(bobe_gp_t* g, int64_t P, double* state, double* adapt, const double* inv_metric, int max_tree_depth,
+                     uint64_t seed, int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp,
+                     int hist_from, double* hist, int thin, double* keep, double* stats, double* dbg) {
+  API_BEGIN
+  NEED(g && state && adapt && inv_metric, "NULL argument");
+  NEED(!is_device_ptr(state) && !is_device_ptr(adapt) && !is_device_ptr(inv_metric) && !is_device_ptr(hist) &&
+           !is_device_ptr(keep) && !is_device_ptr(stats) && !is_device_ptr(dbg),
+       "bobe_gp_nuts_run takes host pointers");
+  NEED(max_tree_depth >= 1 && max_tree_depth <= 10, "max_tree_depth must be in [1, 10]");
+  g->nuts_run(P, state, adapt, inv_metric, max_tree_depth, seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from, hist,
+              thin, keep, stats, dbg);
+  return BOBE_OK;
+  API_END
+}
+
 int bobe_gp_rwalk(bobe_gp_t* g, int64_t P, double* X, double* logl, const double* step, double lstar, int walks,
                   uint64_t seed, double y_std, double y_mean, int* n_accepted, int* n_inside, double* dbg) {
   API_BEGIN

@@ -15,7 +15,8 @@ void configure_consumer_kernels() {       // (the chain kernels keep training po
   if (dev < 0 || dev >= 64 || done[dev]) return;
 #define BIG(KE, DC)                                         \
   allow_big_lds((k_hmc_run<KE, DC>), CHAIN_LDS_BYTES);      \
-  allow_big_lds((k_rwalk<KE, DC>), CHAIN_LDS_BYTES)
+  allow_big_lds((k_rwalk<KE, DC>), CHAIN_LDS_BYTES);        \
+  allow_big_lds((k_nuts_run<KE, DC>), NUTS_LDS_BYTES)
   BIG(0, 8); BIG(0, 16); BIG(0, 32); BIG(1, 8); BIG(1, 16); BIG(1, 32);
 #undef BIG
   done[dev] = true;
@@ -243,6 +244,104 @@ void bobe_gp::hmc_run(int64_t P, double* state, double* adapt, const double* inv
   HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
   if (hist) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, stream));
   if (keep) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (dbg) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
+}
+
+// Host side of k_nuts_run: checks the inverse metric (symmetric, positive definite, its inverse too) and passes it with
+// the lower Cholesky factor C of its inverse, C C^T = Sigma^-1, from which the kernel draws momenta p = C z.
+void bobe_gp::nuts_run(int64_t P, double* state, double* adapt, const double* inv_metric, int max_depth, uint64_t seed,
+                       int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp, int hist_from,
+                       double* hist, int thin, double* keep, double* stats, double* dbg) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  if (P <= 0 || niter < 1 || it0 < 0 || !(temp > 0.0) || thin < 1 || hist_from < 0 || hist_from > niter)
+    throw Err(BOBE_ERR_ARG, "bad argument");
+  if (max_depth < 1 || max_depth > NUTS_MAX_DEPTH) throw Err(BOBE_ERR_ARG, "max_tree_depth must be in [1, 10]");
+  const int dd = d;
+  std::vector<double> met(2 * (size_t)dd * dd, 0.0), Ls((size_t)dd * dd, 0.0), Li((size_t)dd * dd, 0.0);
+  for (int i = 0; i < dd; ++i)
+    for (int j = 0; j < dd; ++j) {
+      const double a = inv_metric[i * dd + j], b = inv_metric[j * dd + i];
+      if (!std::isfinite(a) || std::fabs(a - b) > 1e-12 * (std::fabs(a) + std::fabs(b)))
+        throw Err(BOBE_ERR_ARG, "inv_metric is not symmetric");
+      met[(size_t)i * dd + j] = a;
+    }
+  // Cholesky factorisation (lower, in place); false when a pivot is not positive
+  auto chol = [dd](std::vector<double>& A) {
+    for (int j = 0; j < dd; ++j) {
+      double s = A[(size_t)j * dd + j];
+      for (int k = 0; k < j; ++k) s -= A[(size_t)j * dd + k] * A[(size_t)j * dd + k];
+      if (!(s > 0.0) || !std::isfinite(s)) return false;
+      const double r = std::sqrt(s);
+      A[(size_t)j * dd + j] = r;
+      for (int i = j + 1; i < dd; ++i) {
+        double t = A[(size_t)i * dd + j];
+        for (int k = 0; k < j; ++k) t -= A[(size_t)i * dd + k] * A[(size_t)j * dd + k];
+        A[(size_t)i * dd + j] = t / r;
+      }
+      for (int i = 0; i < j; ++i) A[(size_t)i * dd + j] = 0.0;
+    }
+    return true;
+  };
+  for (int i = 0; i < dd * dd; ++i) Ls[i] = met[i];
+  if (!chol(Ls)) throw Err(BOBE_ERR_ARG, "inv_metric is not positive definite");
+  // M = Sigma^-1 = Ls^-T Ls^-1: Li = Ls^-1 by forward substitution, then M = Li^T Li, then C = chol(M)
+  for (int c = 0; c < dd; ++c)
+    for (int i = c; i < dd; ++i) {
+      double s = (i == c) ? 1.0 : 0.0;
+      for (int k = c; k < i; ++k) s -= Ls[(size_t)i * dd + k] * Li[(size_t)k * dd + c];
+      Li[(size_t)i * dd + c] = s / Ls[(size_t)i * dd + i];
+    }
+  double* Cm = met.data() + (size_t)dd * dd;
+  for (int i = 0; i < dd; ++i)
+    for (int j = 0; j < dd; ++j) {
+      double s = 0.0;
+      for (int k = (i > j ? i : j); k < dd; ++k) s += Li[(size_t)k * dd + i] * Li[(size_t)k * dd + j];
+      Cm[(size_t)i * dd + j] = s;
+    }
+  std::vector<double> Cv(Cm, Cm + (size_t)dd * dd);
+  if (!chol(Cv)) throw Err(BOBE_ERR_ARG, "the inverse of inv_metric is not positive definite");
+  std::copy(Cv.begin(), Cv.end(), Cm);
+  use();
+  const size_t sw = 3 * (size_t)d + 2, ns = (size_t)P * sw, na = (size_t)P * 5, nm = 2 * (size_t)d * d;
+  const size_t nh = hist ? (size_t)(niter - hist_from) * P * d : 0;
+  const size_t nk = keep ? (size_t)(niter / thin) * P * (d + 1) : 0;
+  const size_t nt = stats ? (size_t)niter * P * 4 : 0;
+  const size_t nd = dbg ? (size_t)P * d : 0;
+  // staging: state | adapt | metric | hist | keep | stats | dbg
+  in_stage.ensure((ns + na + nm + nh + nk + nt + nd) * sizeof(double));
+  double* dS = in_stage.d();
+  double* dA = dS + ns;
+  double* dM = dA + na;
+  double* dH = dM + nm;
+  double* dK = dH + nh;
+  double* dT = dK + nk;
+  double* dD = dT + nt;
+  HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(dM, met.data(), nm * sizeof(double), hipMemcpyHostToDevice, stream));
+  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
+#define HN(KE, DC)                                                                                                  \
+  do {                                                                                                              \
+    const int lg = chain_lds_groups(N, d, ChainRows<DC>::NUTS, NUTS_LDS_BYTES);                                      \
+    hipLaunchKernelGGL((k_nuts_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double), \
+                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA,             \
+                       (const double*)dM, max_depth, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, \
+                       temp, hist_from, hist ? dH : nullptr, thin, keep ? dK : nullptr, stats ? dT : nullptr,       \
+                       dbg ? dD : nullptr, gate, lg);                                                               \
+  } while (0)
+  if (hyp.kern == 0) {
+    if (dcap == 8) HN(0, 8); else if (dcap == 16) HN(0, 16); else HN(0, 32);
+  } else {
+    if (dcap == 8) HN(1, 8); else if (dcap == 16) HN(1, 16); else HN(1, 32);
+  }
+#undef HN
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (hist) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (keep) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (stats) HIPCHK(hipMemcpyAsync(stats, dT, nt * sizeof(double), hipMemcpyDeviceToHost, stream));
   if (dbg) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, stream));
   sync();
 }

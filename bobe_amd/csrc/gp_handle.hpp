@@ -471,6 +471,9 @@ struct bobe_gp {
   void hmc_run(int64_t P, double* state, double* adapt, const double* inv_mass, uint64_t seed, int64_t it0, int niter,
                int do_adapt, double y_std, double y_mean, double temp, int hist_from, double* hist, int thin, double* keep,
                double* dbg);
+  void nuts_run(int64_t P, double* state, double* adapt, const double* inv_metric, int max_depth, uint64_t seed,
+                int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp, int hist_from, double* hist,
+                int thin, double* keep, double* stats, double* dbg);
   void rwalk(int64_t P, double* Xw, double* logl, const double* step, double lstar, int walks, uint64_t seed, double y_std,
              double y_mean, int* nacc, int* nin, double* dbg);
   // sqdist: the squared distances of the rows as they are (dist_sq, gp.py:80-96) instead of kernel values

@@ -721,6 +721,31 @@ class GP:
                                              _lib.ptr(dbg) if dbg is not None else None), "bobe_gp_hmc_run")
         return hist, keep, dbg
 
+    def nuts_run(self, state, adapt, inv_metric, max_tree_depth: int, seed: int, it0: int, niter: int, do_adapt: bool,
+                 temp: float = 1.0, hist_from: Optional[int] = None, thin: int = 0, stats: bool = False,
+                 debug: bool = False):
+        """``niter`` No-U-Turn transitions of every chain in ONE GPU launch (``bobe_gp_nuts_run``; the reference's NUTS,
+        samplers.py:216-330): ``state`` (P, 3d+2) and ``adapt`` (P, 5) as in ``hmc_run``, updated in place;
+        ``inv_metric`` the (d, d) inverse metric.  Returns (hist, keep, stats, dbg): u after the iterations >=
+        ``hist_from`` (niter - hist_from, P, d), [x, mean] after every ``thin``-th iteration (niter // thin, P, d+1), per
+        transition [tree depth, leapfrog steps, divergent, acceptance statistic] (niter, P, 4) and the last transition's
+        momentum draw (P, d) - each None unless asked for."""
+        P, d = state.shape[0], self.ndim
+        assert state.shape == (P, 3 * d + 2) and adapt.shape == (P, 5) and state.flags.c_contiguous and adapt.flags.c_contiguous
+        im = np.ascontiguousarray(_lib.as_f64(inv_metric).reshape(d, d))
+        hist = np.empty((niter - hist_from, P, d)) if hist_from is not None else None
+        keep = np.empty((niter // thin, P, d + 1)) if thin else None
+        st = np.empty((niter, P, 4)) if stats else None
+        dbg = np.empty((P, d)) if debug else None
+        _lib.check(self._lib.bobe_gp_nuts_run(self._h, P, _lib.ptr(state), _lib.ptr(adapt), _lib.ptr(im),
+                                              int(max_tree_depth), int(seed), int(it0), int(niter), int(bool(do_adapt)),
+                                              float(self.y_std), float(self.y_mean), float(temp), int(hist_from or 0),
+                                              _lib.ptr(hist) if hist is not None else None, int(thin) if thin else 1,
+                                              _lib.ptr(keep) if keep is not None else None,
+                                              _lib.ptr(st) if st is not None else None,
+                                              _lib.ptr(dbg) if dbg is not None else None), "bobe_gp_nuts_run")
+        return hist, keep, st, dbg
+
     def rwalk(self, x, logl, step, lstar: float, walks: int, seed: int, debug: bool = False):
         """Constrained random walks of P walkers on the surrogate's mean in ONE GPU launch (``bobe_gp_rwalk``): the
         replacement search of nested sampling (dynesty's 'rwalk', samplers.py:64, 152).  ``x`` (P, d) start points with

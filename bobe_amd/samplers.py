@@ -10,7 +10,8 @@ ellipsoid of the live points (clipped to the unit cube), a few thousand at a tim
     variance estimate (samplers.py:178-183);  the BO loop's convergence test is (upper-lower)/2 < threshold
     (bo.py:886-891);
   * result dictionaries with the reference's keys (samplers.py:184-194).
-dynesty and NumPyro themselves are not re-implemented (no multi-ellipsoid decomposition, no NUTS).
+dynesty is not re-implemented (no multi-ellipsoid decomposition); NumPyro's NUTS is, on the device, as the opt-in
+``sample_GP_NUTS(sampler="nuts")``.
 """
 from __future__ import annotations
 
@@ -309,7 +310,48 @@ def get_hmc_settings(ndim, warmup_steps=None, num_samples=None, thinning=None):
     return warmup_steps, num_samples, thinning
 
 
-def sample_GP_NUTS(gp, np_rng=None, rng_key=None, num_chains: int = 4, temp: float = 1.0, **kwargs):
+def adaptation_schedule(num_steps: int):
+    """Stan's windowed warm-up, the rule of NumPyro's ``build_adaptation_schedule``: inclusive (start, end) windows - an
+    initial fast window (75 steps), slow windows of 25, 50, 100, ... steps (the last one stretched to the terminal
+    buffer when three times its size would overrun it) and a terminal fast window (50 steps).  Below 150 steps the
+    buffers are 15 % / 10 % of the steps around one slow window; below 20 steps there is one window."""
+    n = int(num_steps)
+    if n <= 0:
+        return []
+    if n < 20:
+        return [(0, n - 1)]
+    init_buffer, term_buffer, base_window = 75, 50, 25
+    if n < init_buffer + term_buffer + base_window:
+        init_buffer, term_buffer = int(0.15 * n), int(0.1 * n)
+        base_window = n - init_buffer - term_buffer
+    schedule = [(0, init_buffer - 1)]
+    end_window_start = n - term_buffer
+    next_size, next_start = base_window, init_buffer
+    while next_start < end_window_start:
+        cur_start, cur_size = next_start, next_size
+        if 3 * cur_size <= end_window_start - cur_start:
+            next_size = 2 * cur_size
+        else:
+            cur_size = end_window_start - cur_start
+        next_start = cur_start + cur_size
+        schedule.append((cur_start, next_start - 1))
+    schedule.append((end_window_start, n - 1))
+    return schedule
+
+
+def window_metric(draws: np.ndarray, dense: bool = True) -> np.ndarray:
+    """The inverse metric at the end of a slow window (Stan's regularised estimate, NumPyro's welford_covariance):
+    Sigma = n / (n + 5) S + 1e-3 * 5 / (n + 5) I from the n draws (rows) of the window; ``dense=False`` keeps the
+    diagonal."""
+    n, d = draws.shape
+    cov = np.cov(draws, rowvar=False).reshape(d, d) if n > 1 else np.zeros((d, d))
+    cov = 0.5 * (cov + cov.T)
+    if not dense:
+        cov = np.diag(np.diag(cov))
+    return n / (n + 5.0) * cov + 1e-3 * 5.0 / (n + 5.0) * np.eye(d)
+
+
+def sample_GP_NUTS(gp, np_rng=None, rng_key=None, num_chains: int = 4, temp: float = 1.0, sampler: str = "hmc", **kwargs):
     """Samples of the posterior whose log-density is the GP mean / ``temp`` over the unit cube — the target, keywords
     and return dict of samplers.py:216-360 (``'x'`` of shape (num_chains * num_samples / thinning, d), ``'logp'``,
     ``'best'``, ``'method'``).
@@ -326,7 +368,21 @@ def sample_GP_NUTS(gp, np_rng=None, rng_key=None, num_chains: int = 4, temp: flo
     spread of the chains.  Chains start at the best training point and at ``gp.get_random_point`` draws
     (samplers.py:296-300); a chain that is still tens of log units below the others at a warm-up window restarts from a
     healthy chain's state (``cull_lost_chains``, see the loop).  Works for ``GPwithClassifier`` too: infeasible points carry ``minus_inf`` and are never
-    accepted."""
+    accepted.
+
+    ``sampler="nuts"`` (opt-in; the default ``"hmc"`` is the path above) runs the reference's algorithm instead: NumPyro's
+    multinomial No-U-Turn sampler with the generalised U-turn criterion, ``max_tree_depth`` (default 6) doublings at most
+    and a dense metric (``dense_mass``, default True; False keeps its diagonal), whole transitions of the same chains in
+    ``bobe_gp_nuts_run`` launches.  Warm-up follows Stan's windowed schedule (``adaptation_schedule``, one launch per
+    window): per-chain dual averaging of the step size, and at the end of every slow window the regularised covariance of
+    the window's draws (``window_metric``) pooled over the healthy chains - NumPyro estimates it per chain - then a
+    restarted dual averaging.  NumPyro's ``find_reasonable_step_size`` is not run: the step size starts at 0.1 as on the
+    HMC path.  There is no host-stepped NUTS: ``device_chains=False`` or ``fused_trajectories=False`` with it raise
+    ``ValueError``."""
+    if sampler not in ("hmc", "nuts"):
+        raise ValueError(f"sampler must be 'hmc' or 'nuts', not {sampler!r}")
+    if sampler == "nuts" and not (kwargs.get("device_chains", True) and kwargs.get("fused_trajectories", True)):
+        raise ValueError("sampler='nuts' runs on the device only: device_chains and fused_trajectories must stay True")
     rng = np_rng if isinstance(np_rng, np.random.Generator) else np.random.default_rng(np_rng)
     d = gp.ndim
     warmup_steps, num_samples, thinning = get_hmc_settings(d, kwargs.get("warmup_steps"), kwargs.get("num_samples"),
@@ -364,6 +420,11 @@ def sample_GP_NUTS(gp, np_rng=None, rng_key=None, num_chains: int = 4, temp: flo
     lp, g, mean, X = logp_and_grad(U)
     inv_mass = np.ones(d)
     total = warmup_steps + keep_per_chain * thinning
+    if sampler == "nuts":
+        if not hasattr(gp, "nuts_run"):
+            raise ValueError("sampler='nuts' needs a surrogate with nuts_run (the GPU GP)")
+        return _nuts_chains(gp, rng, U, g, X, lp, mean, warmup_steps, keep_per_chain, n_keep_total, thinning, temp,
+                            int(kwargs.get("max_tree_depth", 6)), bool(kwargs.get("dense_mass", True)), kwargs)
     if on_device:
         # Whole chains on the device (bobe_gp_hmc_run): the host only cuts the warm-up at the mass-matrix windows and
         # pools the chains' spread there; every chain adapts its OWN step size (NumPyro does the same per chain).
@@ -461,4 +522,45 @@ def sample_GP_NUTS(gp, np_rng=None, rng_key=None, num_chains: int = 4, temp: flo
             lps.append(mean.copy())
     samples_x = np.concatenate(xs, axis=0)[:n_keep_total]
     logps = np.concatenate(lps, axis=0)[:n_keep_total]
+    return {"x": samples_x, "logp": logps, "best": samples_x[int(np.argmax(logps))], "method": "MCMC"}
+
+
+def _nuts_chains(gp, rng, U, g, X, lp, mean, warmup_steps, keep_per_chain, n_keep_total, thinning, temp, max_tree_depth,
+                 dense_mass, kwargs) -> Dict:
+    """The NUTS path of ``sample_GP_NUTS``: the chains of the HMC path, windowed warm-up, then the sampling launch."""
+    P, d = U.shape
+    state = np.ascontiguousarray(np.concatenate([U, g, X, lp[:, None], mean[:, None]], axis=1))
+    adapt = np.tile(np.array([0.1, math.log(1.0), 0.0, 0.0, 0.0]), (P, 1))
+    inv_metric = np.eye(d)
+    seed = int(rng.integers(0, 2 ** 62))
+    schedule = adaptation_schedule(warmup_steps)
+    for w, (start, end) in enumerate(schedule):
+        slow = 0 < w < len(schedule) - 1
+        hist, _, _, _ = gp.nuts_run(state, adapt, inv_metric, max_tree_depth, seed, start, end - start + 1, True, temp,
+                                    hist_from=0 if slow else None)
+        healthy = np.ones(P, dtype=bool)
+        if kwargs.get("cull_lost_chains", True):               # (as on the HMC path)
+            lp_now = state[:, 3 * d]
+            lost = ~(lp_now >= np.nanmax(lp_now) - (20.0 + 2.0 * d))
+            if lost.any() and not lost.all():
+                healthy = ~lost
+                src = rng.choice(np.flatnonzero(healthy), size=int(lost.sum()))
+                state[lost] = state[src]
+                adapt[lost] = adapt[src]
+        if slow:                                               # pooled metric, restarted dual averaging
+            inv_metric = window_metric(hist[:, healthy, :].reshape(-1, d), dense=dense_mass)
+            adapt[:, 1] = np.log(10.0 * adapt[:, 0])
+            adapt[:, 2:5] = 0.0
+    if warmup_steps > 0:                                       # the averaged step size of the warm-up
+        adapt[:, 0] = np.where(adapt[:, 3] != 0.0, np.clip(np.exp(adapt[:, 3]), 1e-4, 2.0), adapt[:, 0])
+    if isinstance(kwargs.get("diagnostics"), dict):
+        kwargs["diagnostics"].update(eps=adapt[:, 0].copy(), inv_metric=inv_metric.copy(), state=state.copy(),
+                                     adapt=adapt.copy(), seed=seed, it=warmup_steps, schedule=schedule)
+    _, keep, stats, _ = gp.nuts_run(state, adapt, inv_metric, max_tree_depth, seed, warmup_steps,
+                                    keep_per_chain * thinning, False, temp, thin=thinning,
+                                    stats=isinstance(kwargs.get("diagnostics"), dict))
+    if stats is not None:
+        kwargs["diagnostics"].update(stats=stats)
+    samples_x = keep[:, :, :d].reshape(-1, d)[:n_keep_total]
+    logps = keep[:, :, d].reshape(-1)[:n_keep_total]
     return {"x": samples_x, "logp": logps, "best": samples_x[int(np.argmax(logps))], "method": "MCMC"}

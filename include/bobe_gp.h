@@ -213,6 +213,23 @@ int bobe_gp_hmc_run(bobe_gp_t* g, int64_t P, double* state, double* adapt, const
                     int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp, int hist_from,
                     double* hist, int thin, double* keep, double* dbg);
 
+/* No-U-Turn sampling on the device: `niter` NUTS transitions of P chains in ONE launch - the sampler the reference's
+ * sample_GP_NUTS runs through NumPyro (BOBE/samplers.py:216-330): multinomial NUTS with the generalised U-turn criterion
+ * (NumPyro's iterative_build_tree), a dense inverse metric and - with do_adapt - the chain's own dual-averaging step-size
+ * update towards a mean acceptance statistic of 0.8.  Same target and state as bobe_gp_hmc_run.  All pointers are HOST
+ * memory (a device pointer is refused with BOBE_ERR_ARG).
+ *   state, adapt, hist, keep   as bobe_gp_hmc_run
+ *   inv_metric [d][d]  the inverse metric Sigma (symmetric positive definite: else BOBE_ERR_ARG); momenta are drawn from
+ *                      N(0, Sigma^-1), the kinetic energy is p^T Sigma p / 2
+ *   max_tree_depth     in [1, 10] (else BOBE_ERR_ARG): at most 2^max_tree_depth - 1 leapfrog steps per transition
+ *   stats [niter][P][4]  tree depth, leapfrog steps, divergent flag, acceptance statistic (NULL: not recorded)
+ *   dbg   [P][d]         the last transition's momentum draw (NULL: not recorded; tests replay it)
+ * Random numbers are a counter hash of (seed, chain, it0 + iteration, index); consumer_kernels.hpp (k_nuts_run) writes
+ * out the tree rule and the index layout. */
+int bobe_gp_nuts_run(bobe_gp_t* g, int64_t P, double* state, double* adapt, const double* inv_metric, int max_tree_depth,
+                     uint64_t seed, int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp,
+                     int hist_from, double* hist, int thin, double* keep, double* stats, double* dbg);
+
 /* The replacement search of nested sampling on the surrogate (the consumer behind nested_sampling_Dy, samplers.py:55-194,
  * which hands gp.predict_mean_single to dynesty's 'rwalk' sampler one point per call, samplers.py:112-115, 152): P walkers,
  * each `walks` constrained Metropolis steps x' = x + step z, z ~ N(0, I), accepted when x' lies in the unit cube and
@@ -242,6 +259,7 @@ int bobe_gp_rwalk(bobe_gp_t* gp, int64_t P, double* X, double* logl, const doubl
  *   bobe_gp_acq_ei                           EI / LogEI of (mean = minus_inf, var = 1e-12), i.e. what EI.fun computes from
  *                                            the gated predict_single (acquisition.py:246, 323)
  *   bobe_gp_hmc_leapfrog / bobe_gp_hmc_run   mean = minus_inf (physical units), no mean gradient: never accepted
+ *   bobe_gp_nuts_run                         mean = minus_inf: a divergent leaf at the default minus_inf, never chosen
  *   bobe_gp_rwalk                            mean = minus_inf: never accepted
  * bobe_gp_wip_sweep, bobe_gp_fantasy_var and bobe_gp_wip_grad are NOT gated (fantasy_var is not, clf_gp.py:207-212).
  * One summation order serves every entry point (256 partial sums, a fixed tree), so a point near the boundary falls on
