@@ -132,6 +132,67 @@ __device__ __forceinline__ void acc_zero(v4d (&acc)[FM][FN]) {
     for (int j = 0; j < FN; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
 }
 
+// ---- in-kernel stamps of the K loop (diagnostic build only: tools/gemm_stamps.hip defines BOBE_GEMM_STAMPS) --------------
+// Per wave: s_memtime / s_memrealtime around the loop and s_memtime sums of four segments per K-step,
+//   0 first-fragment wait    1 MFMA body    2 staging wait (+ ds_write on the register-staged loop)    3 barrier
+// written by lane 0 into g_stamps[((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8 + ...] with ordinary vector
+// stores; no output reads them.  Each stamp waits lgkmcnt(0), so the stamped build is slower than the product.
+#ifdef BOBE_GEMM_STAMPS
+__device__ unsigned long long* g_stamps;
+__device__ __forceinline__ unsigned long long stamp_time() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+__device__ __forceinline__ unsigned long long stamp_real() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+struct Stamps {
+  unsigned long long t0, r0, last, seg[4], steps;
+  __device__ __forceinline__ void begin() {
+    r0 = stamp_real();
+    t0 = last = stamp_time();
+    seg[0] = seg[1] = seg[2] = seg[3] = steps = 0;
+  }
+  __device__ __forceinline__ void mark(int i) {
+    const unsigned long long t = stamp_time();
+    seg[i] += t - last;
+    last = t;
+  }
+  __device__ __forceinline__ void end(int tid) {
+    const unsigned long long t1 = stamp_time(), r1 = stamp_real();
+    if ((tid & 63) == 0 && g_stamps) {
+      unsigned long long* o = g_stamps + ((blockIdx.y * gridDim.x + blockIdx.x) * 4 + (tid >> 6)) * 8;
+      o[0] = t1 - t0;
+      o[1] = r1 - r0;
+      o[2] = seg[0];
+      o[3] = seg[1];
+      o[4] = seg[2];
+      o[5] = seg[3];
+      o[6] = steps;
+      o[7] = 1;
+    }
+  }
+};
+#define BOBE_STAMPS_DECL Stamps st_; st_.begin();
+#define BOBE_STAMP(i) st_.mark(i)
+#define BOBE_STAMP_STEP() (++st_.steps)
+#define BOBE_STAMP_VMWAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define BOBE_STAMPS_END(tid) st_.end(tid)
+#else
+#define BOBE_STAMPS_DECL
+#define BOBE_STAMP(i)
+#define BOBE_STAMP_STEP()
+#define BOBE_STAMP_VMWAIT()
+#define BOBE_STAMPS_END(tid)
+#endif
+
 // acc += A(m0.., k) * B(n0.., k) for k in [kbeg, kend); (kend - kbeg) must be a multiple of BK
 // (K ranges are multiples of 128 for the 128x128 callers and of 64 for the 64x64 callers).
 // smem: gemm_smem_doubles<TM,TN,BK>() doubles.  All 256 threads must call.  `tid` (0..255) is the thread's index
@@ -171,6 +232,7 @@ __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const do
   stage_store<LA, TM, BK>(ra, smem, t);
   stage_store<LB, TN, BK>(rb, smem + IA, t);
   if (sy) sy->sync(); else wg_default.sync();
+  BOBE_STAMPS_DECL
   int buf = 0;
   // one K-step: next step's operands on their way, this step's MFMAs, next step's LDS image.  IN (a constant): the step
   // lies inside the closing diagonal block of a TRIL operand, `rel` = its first column there
@@ -194,6 +256,7 @@ __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const do
       }
 #pragma unroll
       for (int s = 0; s < FN; ++s) b[s] = frag_read<LB, TN, BK>(ib, wn, s, ks, lane);
+      if (ks == 0) BOBE_STAMP(0);
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
         if (IN && rel + 4 * ks > wmu + 16 * i + 15) continue;       // columns right of the fragment's rows: zeros
@@ -202,18 +265,164 @@ __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const do
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
       }
     }
+    BOBE_STAMP(1);
     if (more) {
       double* na = smem + (buf ^ 1) * (IA + IB);
       stage_store<LA, TM, BK>(ra, na, t);
       stage_store<LB, TN, BK>(rb, na + IA, t);
     }
+    BOBE_STAMP(2);
     if (sy) sy->sync(); else wg_default.sync();
+    BOBE_STAMP(3);
+    BOBE_STAMP_STEP();
     buf ^= 1;
   };
   const int64_t kd = TRIL ? (kend - TM > kbeg ? kend - TM : kbeg) : kend;      // start of the closing diagonal block
   for (int64_t k0 = kbeg; k0 < kd; k0 += BK) kstep(k0, std::false_type(), 0);
   if (TRIL)
     for (int64_t k0 = kd; k0 < kend; k0 += BK) kstep(k0, std::true_type(), (int)(k0 - (kend - TM)));
+  BOBE_STAMPS_END(t);
+}
+
+// ---- 128 x 128 tiles, BK = 16: operands straight into LDS, fragments one sub-step ahead -------------------------------
+// The same MFMAs as gemm_tile<LA, LB, 128, 128, 16, NEGA, WgSync, TRIL> in the same order for every accumulator, so the
+// same bits; what differs is how the operands get there.
+//   * Staging: buffer_load_dwordx4 ... lds (16 B per lane straight into LDS; the destination is the wave-uniform base +
+//     16 B x lane).  No staging registers (32 VGPRs at 128 x 16 x 2 operands) and no vmcnt-gated ds_write block at the end of a
+//     K-step: the next step's loads are issued at the top of the step and waited for by the barrier that closes it.
+//   * An RC image keeps gemm_tile's [BK][R + 16] layout: one k-row (128 doubles = 1 KiB) is one wave-instruction.
+//   * A KC image cannot keep the 2-double row pad (an instruction covers 8 rows of 128 B), so it is [128][16] unpadded
+//     with the 16-byte chunk c of row r stored at chunk c ^ ((r >> 1) & 7): each lane's SOURCE address carries the
+//     permutation, the fragment read applies it again (an involution).  A 32-lane ds_read_b64 group still hits 32
+//     distinct bank pairs: rows r and r + 1 differ by 32 banks, the eight row pairs by the chunk permutation.
+//   * Fragments are double-buffered: the reads of sub-step ks + 1 are issued ahead of the MFMAs of ks.  The barrier
+//     comes after the MFMAs of the third sub-step; the first sub-step of the next K-step is read right behind it, under
+//     the MFMAs of the fourth.  Every fragment read has the 16 MFMAs of one sub-step to land in.
+// One barrier per K-step (its fence drains the step's LDS loads with vmcnt(0)); 73,728 B of LDS or less, so two
+// workgroups per CU as before.  The last K-step reloads its own slice into the idle buffer rather than branching round
+// the loads (a branch there costs the fragment reads their counted waits).
+template <int L>
+struct Img128 {
+  static constexpr int doubles = (L == KC) ? 128 * 16 : 16 * (128 + 16);
+};
+template <int LA, int LB>
+constexpr int gemm128_smem_doubles() { return 2 * (Img128<LA>::doubles + Img128<LB>::doubles); }
+static_assert(gemm128_smem_doubles<RC, RC>() <= GEMM_SMEM_DOUBLES && gemm128_smem_doubles<KC, RC>() <= GEMM_SMEM_DOUBLES,
+              "the 128-tile LDS images must fit the launches' GEMM_SMEM_BYTES");
+
+// global -> LDS, one operand tile of 128 x 16: four wave-instructions per wave (wave w: KC rows 8g .. 8g + 7, RC k-row g,
+// g = w + 4i)
+template <int L>
+__device__ __forceinline__ void glds_stage128(const double* __restrict__ p, int64_t ld, int64_t r0, int64_t k0, double* img,
+                                              int wave, int lane) {
+  // (a buffer load into LDS rather than global_load_lds: the compiler treats the latter as a FLAT access that may return
+  // out of order and then waits lgkmcnt(0) for every fragment read; the resource is based at the tile's corner, so the
+  // 32-bit offsets stay below 128 x ld x 8 bytes)
+  const double* base = (L == KC) ? p + r0 * ld + k0 : p + k0 * ld + r0;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int g = wave + 4 * i;
+    unsigned off;
+    double* dst;
+    if (L == KC) {
+      const int r = 8 * g + (lane >> 3);
+      off = (unsigned)((r * ld + 2 * ((lane & 7) ^ ((r >> 1) & 7))) * 8);
+      dst = img + 128 * g;
+    } else {
+      off = (unsigned)((g * ld + 2 * lane) * 8);
+      dst = img + (128 + 16) * g;
+    }
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, off, 0, 0, 0);
+  }
+}
+
+// fragment read from a 128 x 16 image: 16-row sub-tile s of the wave's rows at woff, sub-step ks.  KC: the lane's row is
+// woff + 16 s + (lane & 15), its chunk 2 ks + (lane >> 5) (= 2 ks ^ (lane >> 5)), permuted by ((lane & 15) >> 1)
+template <int L>
+__device__ __forceinline__ double frag_read128(const double* img, int woff, int s, int ks, int lane) {
+  if (L == KC) {
+    const int h = (lane >> 5) ^ ((lane & 15) >> 1);
+    return img[(woff + 16 * s + (lane & 15)) * 16 + 2 * ((2 * ks) ^ h) + ((lane >> 4) & 1)];
+  } else {
+    return img[(4 * ks + (lane >> 4)) * (128 + 16) + woff + 16 * s + (lane & 15)];
+  }
+}
+
+template <int LA, int LB, bool NEGA = false, bool TRIL = false>
+__device__ __forceinline__ void gemm_tile128_glds(v4d (&acc)[4][4], const double* __restrict__ A, int64_t lda, int64_t m0,
+                                                  const double* __restrict__ B, int64_t ldb, int64_t n0, int64_t kbeg,
+                                                  int64_t kend, double* smem, int tid = threadIdx.x) {
+  constexpr int BK = 16, TM = 128;
+  constexpr int IA = Img128<LA>::doubles, IB = Img128<LB>::doubles;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = (wave >> 1) * 64;
+  const int wn = (wave & 1) * 64;
+  if (kend <= kbeg) return;
+  auto stage = [&](int64_t k0, int b) {
+    double* ia = smem + b * (IA + IB);
+    glds_stage128<LA>(A, lda, m0, k0, ia, wave, lane);
+    glds_stage128<LB>(B, ldb, n0, k0, ia + IA, wave, lane);
+  };
+  double fa[2][4], fb[2][4];
+  auto frags = [&](double (&a)[4], double (&b)[4], const double* ia, int ks) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      a[s] = frag_read128<LA>(ia, wm, s, ks, lane);
+      if (NEGA) a[s] = -a[s];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[s] = frag_read128<LB>(ia + IA, wn, s, ks, lane);
+  };
+  stage(kbeg, 0);
+  __syncthreads();
+  BOBE_STAMPS_DECL
+  frags(fa[0], fb[0], smem, 0);
+  BOBE_STAMP(0);
+  int buf = 0;
+  auto kstep = [&](int64_t k0, auto in_c, int rel) {
+    constexpr bool IN = decltype(in_c)::value;
+    const bool more = (k0 + BK) < kend;
+    auto mfmas = [&](int ks) {
+      const double(&a)[4] = fa[ks & 1];
+      const double(&b)[4] = fb[ks & 1];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (IN && rel + 4 * ks > wm + 16 * i + 15) continue;        // columns right of the fragment's rows: zeros
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+      }
+    };
+    stage(more ? k0 + BK : k0, buf ^ 1);
+    const double* ia = smem + buf * (IA + IB);
+    // (the phases are pinned: left alone, the scheduler sinks the reads of a sub-step behind the MFMAs that should hide them)
+#pragma unroll
+    for (int ks = 0; ks < BK / 4 - 1; ++ks) {
+      frags(fa[(ks + 1) & 1], fb[(ks + 1) & 1], ia, ks + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas(ks);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    BOBE_STAMP(1);
+    BOBE_STAMP_VMWAIT();
+    BOBE_STAMP(2);
+    __syncthreads();
+    BOBE_STAMP(3);
+    BOBE_STAMP_STEP();
+    buf ^= 1;
+    // the next step's first sub-step is read under the MFMAs of this step's last one (whose fragments are in set 1)
+    frags(fa[0], fb[0], smem + buf * (IA + IB), 0);
+    __builtin_amdgcn_sched_barrier(0);
+    mfmas(BK / 4 - 1);
+    __builtin_amdgcn_sched_barrier(0);
+    BOBE_STAMP(0);
+  };
+  const int64_t kd = TRIL ? (kend - TM > kbeg ? kend - TM : kbeg) : kend;
+  for (int64_t k0 = kbeg; k0 < kd; k0 += BK) kstep(k0, std::false_type(), 0);
+  if (TRIL)
+    for (int64_t k0 = kd; k0 < kend; k0 += BK) kstep(k0, std::true_type(), (int)(k0 - (kend - TM)));
+  BOBE_STAMPS_END(tid);
 }
 
 // Coordinates of accumulator element (i, j, r) of this lane inside the TM x TN tile.

@@ -54,7 +54,7 @@ void configure_factor_kernels() {
 
 const Tuning& tuning() {
   static Tuning t = [] {
-    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false, true};
+    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false, true, true};
     auto geti = [](const char* name, int& dst) {
       const char* e = std::getenv(name);
       if (e) dst = std::atoi(e);
@@ -72,6 +72,9 @@ const Tuning& tuning() {
     int reuse = 1;
     geti("BOBE_FACTOR_REUSE", reuse);
     v.factor_reuse = reuse != 0;
+    int glds = 1;
+    geti("BOBE_GEMM_GLDS", glds);
+    v.gemm_glds = glds != 0;
     return v;
   }();
   return t;

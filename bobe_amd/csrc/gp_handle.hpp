@@ -115,9 +115,11 @@ void allow_big_lds(K kernel, int bytes) {
 //   BOBE_FILL           deferred trailing updates in the panel launches: 0 off, 1 where they pay (potrf), 2 everywhere
 //   BOBE_TRACE          print launch plans and batch timings to stderr
 //   BOBE_FACTOR_REUSE   0: bobe_gp_factor always factorises, never adopts an evaluation's factor (1; for A/B runs)
+//   BOBE_GEMM_GLDS      0: the sweep's 128-tile GEMMs (k_trimul, k_cross_vv<128>) take the register-staged tile core
+//                       instead of gemm_tile128_glds (1; for A/B runs)
 struct Tuning {
   int syrk32_below, trtri64_below, pair_min, lockstep_min_n, mll_slots, graph_max_n, xcd_shares, fill;
-  bool mll_slots_set, trace, factor_reuse;
+  bool mll_slots_set, trace, factor_reuse, gemm_glds;
 };
 const Tuning& tuning();
 

@@ -12,15 +12,21 @@ void configure_sweep_kernels() {
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || done[dev]) return;
-  allow_big_lds(k_trimul, GEMM_SMEM_BYTES);
+  allow_big_lds(k_trimul<true>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_trimul<false>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul_t, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul_v64, GEMM64_SMEM_BYTES);
   allow_big_lds(k_trimul_t64, GEMM64_SMEM_BYTES);
   allow_big_lds(k_blk_step, GEMM_SMEM_BYTES);
-  allow_big_lds(k_cross_vv<128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_cross_vv<128, true>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_cross_vv<128, false>, GEMM_SMEM_BYTES);
   allow_big_lds(k_cross_vv<64>, GEMM64_SMEM_BYTES);
   done[dev] = true;
 }
+
+// the sweep's 128-tile GEMM kernels on the tile core BOBE_GEMM_GLDS selects (a function pointer: pass every argument)
+static auto trimul_kernel() { return tuning().gemm_glds ? k_trimul<true> : k_trimul<false>; }
+static auto cross_vv128_kernel() { return tuning().gemm_glds ? k_cross_vv<128, true> : k_cross_vv<128, false>; }
 }  // namespace bobe
 
 void bobe_gp::decide_refinement(double min_diag) {
@@ -30,9 +36,9 @@ void bobe_gp::decide_refinement(double min_diag) {
 
 void bobe_gp::solve_v(double* B, int64_t ldb, int64_t ncp, double* V, int64_t ldv, double* qp, int64_t ldq) {
   if (!refine_v) {
-    hipLaunchKernelGGL(k_trimul, dim3((unsigned)(ncp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
+    hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)(ncp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nb, (const double*)B, ldb, V, ldv, qp, ldq, (const double*)nullptr,
-                       (int64_t)0, 0, (double*)nullptr, (int64_t)0);
+                       (int64_t)0, 0, (double*)nullptr, (int64_t)0, (const double*)nullptr, (int64_t)0, 0, 1 << 30);
     return;
   }
   if (!V) throw Err(BOBE_ERR_STATE, "solve_v: the blocked substitution needs a buffer for V");
@@ -102,9 +108,10 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
     hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
                        (const double*)qpart.d(), Mp, nt, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
   } else {
-    hipLaunchKernelGGL(k_trimul, dim3((unsigned)(Mp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
+    hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)(Mp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nb, (const double*)kXZ.d(), Mp, VZ.d(), Mp, qpart.d(), Mp,
-                       (const double*)nullptr, (int64_t)0, 0, (double*)nullptr, (int64_t)0);
+                       (const double*)nullptr, (int64_t)0, 0, (double*)nullptr, (int64_t)0, (const double*)nullptr,
+                       (int64_t)0, 0, 1 << 30);
     hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
                        (const double*)qpart.d(), Mp, nb, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
   }
@@ -158,7 +165,7 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
     // cross-covariances from the two solved factors (sweep_kernels.hpp, k_cross_vv): crossT[z][c] = VZ[:, z] . V[:, c]
     prof_begin(BOBE_PROF_CROSSVV);
     if ((int64_t)nzt * (ncp_ / TILE) >= 2 * std::max(num_cus, 1))
-      hipLaunchKernelGGL(k_cross_vv<128>, dim3((unsigned)(ncp_ / TILE), (unsigned)nzt), dim3(256), GEMM_SMEM_BYTES, stream,
+      hipLaunchKernelGGL(cross_vv128_kernel(), dim3((unsigned)(ncp_ / TILE), (unsigned)nzt), dim3(256), GEMM_SMEM_BYTES, stream,
                          (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, SC);
     else
       hipLaunchKernelGGL(k_cross_vv<64>, dim3((unsigned)(ncp_ / 64), (unsigned)(Mp / 64)), dim3(256), GEMM64_SMEM_BYTES,
@@ -215,7 +222,7 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
         if (fuse_cross) {
           const int ncv = (int)(ncp / TILE), ncx = pend.valid ? (int)(pend.ncp / TILE) : 0;
           const int nz = pend.valid ? nzt : 0;
-          hipLaunchKernelGGL(k_trimul, dim3((unsigned)std::max(ncv, ncx), (unsigned)(nb + nz)), dim3(256), GEMM_SMEM_BYTES,
+          hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)std::max(ncv, ncx), (unsigned)(nb + nz)), dim3(256), GEMM_SMEM_BYTES,
                              stream, (const double*)Linv.d(), Np, nb, (const double*)kXC.d(), CH, vcur, CH, qpart.d(), CH,
                              (const double*)VZ.d(), Mp, nz, pend.cross, SC, pend.V, CH, ncx, ncv);
           pend = {true, vcur, ncp, pv.d() + c0};

@@ -14,6 +14,9 @@ namespace bobe {
 // solves the next chunk, where their full-K tiles fill the tails of the triangular ones, instead of a launch of their own
 // (2.62 ms per chunk of 8192 candidates at N = 4096, M = 512 against 2.17 + 0.59).  ncv / ncx: column tiles of the two
 // parts (the grid spans the larger; a chunk's last tiles may be missing in one of them).
+// GLDS: the tile core (gemm_f64.hpp): gemm_tile128_glds (true, the default) or the register-staged gemm_tile - same bits
+// (BOBE_GEMM_GLDS, gp_handle.hpp).
+template <bool GLDS>
 __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Linv, int64_t ldi, int nb,
                                                    const double* __restrict__ B, int64_t ldb, double* __restrict__ V,
                                                    int64_t ldv, double* __restrict__ qpart, int64_t ldq,
@@ -31,7 +34,10 @@ __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Li
   if ((int)blockIdx.y < nzt) {
     if (tc >= ncx) return;
     const int tz = blockIdx.y;
-    gemm_tile<RC, RC>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
+    if constexpr (GLDS)
+      gemm_tile128_glds<RC, RC>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
+    else
+      gemm_tile<RC, RC>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
     store_tile(acc, crossT, ldx, (int64_t)tz * TILE, (int64_t)tc * TILE, 1.0, 0.0);
     return;
   }
@@ -39,8 +45,12 @@ __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Li
   const int ti = nb - 1 - ((int)blockIdx.y - nzt);
   // (the K range of a row tile ends with its diagonal block of the lower-triangular Linv: the zeros above the diagonal are
   // skipped, 1.2 % of the launch)
-  gemm_tile<KC, RC, TILE, TILE, BK128, false, WgSync, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE, 0,
-                                                            (int64_t)(ti + 1) * TILE, smem);
+  if constexpr (GLDS)
+    gemm_tile128_glds<KC, RC, false, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE, 0,
+                                           (int64_t)(ti + 1) * TILE, smem);
+  else
+    gemm_tile<KC, RC, TILE, TILE, BK128, false, WgSync, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE,
+                                                              0, (int64_t)(ti + 1) * TILE, smem);
   if (V) store_tile(acc, V, ldv, (int64_t)ti * TILE, (int64_t)tc * TILE, 1.0, 0.0);
   if (qpart) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -170,8 +180,8 @@ __global__ __launch_bounds__(256) void k_colsq_tile_parts(const double* __restri
 // scores came out 1e-2 ... 1 (relative) off an extended-precision evaluation where the triangular-solve form is 1e-4 ...
 // 1e-1 off (profiles/r05_conditioning.txt, tests/test_gpu_conditioning.py).  Same 2 N M flops per candidate.
 // T = 128: grid (ncols / 128, Mp / 128); T = 64: grid (ncols / 64, Mp / 64) - few integration points fill the chip only
-// with the small tile.
-template <int T>
+// with the small tile.  GLDS: the 128-tile core as in k_trimul (no effect on T = 64).
+template <int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ VZ, int64_t ldz,
                                                      const double* __restrict__ V, int64_t ldv, int64_t kend,
                                                      double* __restrict__ crossT, int64_t ldx) {
@@ -180,7 +190,10 @@ __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ 
   v4d acc[T / 32][T / 32];
   acc_zero(acc);
   if constexpr (T == 128) {
-    gemm_tile<RC, RC>(acc, VZ, ldz, (int64_t)tz * TILE, V, ldv, (int64_t)tc * TILE, 0, kend, smem);
+    if constexpr (GLDS)
+      gemm_tile128_glds<RC, RC>(acc, VZ, ldz, (int64_t)tz * TILE, V, ldv, (int64_t)tc * TILE, 0, kend, smem);
+    else
+      gemm_tile<RC, RC>(acc, VZ, ldz, (int64_t)tz * TILE, V, ldv, (int64_t)tc * TILE, 0, kend, smem);
     store_tile(acc, crossT, ldx, (int64_t)tz * TILE, (int64_t)tc * TILE, 1.0, 0.0);
   } else {
     gemm_tile<RC, RC, 64, 64, BK64>(acc, VZ, ldz, (int64_t)tz * 64, V, ldv, (int64_t)tc * 64, 0, kend, smem);

@@ -41,6 +41,12 @@ for N, d, kern in SIZES:
         r = gp.wip_sweep(rs.uniform(size=(700, d)), rs.uniform(size=(96, d)), want_mean_var=True)
         gp._lib.bobe_gp_set_chunk(gp._h, 0)
         out[f"sw_{N}"] = np.concatenate([r["wipv"], r["wipstd"], r["mean"], r["var"], [r["argmin_v"], r["argmin_s"]]])
+    elif os.environ.get("BITS_BIG_SWEEP"):    # three chunks of 16384 candidates, 512 integration points: the fused cross
+        rs = np.random.default_rng(10_000 + N)  # tiles in k_trimul and a closing k_cross_vv<128>
+        gp._lib.bobe_gp_set_chunk(gp._h, 16384)
+        r = gp.wip_sweep(rs.uniform(size=(3 * 16384, d)), rs.uniform(size=(512, d)), want_mean_var=True)
+        gp._lib.bobe_gp_set_chunk(gp._h, 0)
+        out[f"sw_{N}"] = np.concatenate([r["wipv"], r["wipstd"], r["mean"], r["var"], [r["argmin_v"], r["argmin_s"]]])
 import hashlib
 import json
 out = {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in out.items()}
