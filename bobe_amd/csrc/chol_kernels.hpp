@@ -794,8 +794,12 @@ __global__ __launch_bounds__(256) void k_copy_diag(double* __restrict__ A, int64
 // colk0 / far_col (optional, 64x64 tiles only): block columns >= far_col read their first pending panel from colk0[column]
 // (deferred columns: the K range [colk0[c], k1) differs from column to column; colk0[c] >= k1 skips the column); columns
 // before far_col take the scalar k0 without touching memory.
-template <int T, int BK>
-__global__ __launch_bounds__(256) void k_syrk_trail(double* __restrict__ A, int64_t lda, int k0, int k1, int first,
+// GLDS (T = 64, BK = 16 only): the tile core gemm_tile64_glds instead of the register-staged gemm_tile - same bits
+// (BOBE_GEMM64_GLDS, gp_handle.hpp).  Its occupancy bound of two workgroups per CU caps the registers at 256, so the
+// MFMAs accumulate in VGPRs: with room for 512 the compiler takes the AGPR form and copies all 32 accumulator registers
+// out and back in every K-step of this loop.
+template <int T, int BK, bool GLDS = false>
+__global__ __launch_bounds__(256, GLDS ? 2 : 1) void k_syrk_trail(double* __restrict__ A, int64_t lda, int k0, int k1, int first,
                                                     int colmode, int n, int64_t bsA = 0, int per = 0,
                                                     const int* __restrict__ colk0 = nullptr, int far_col = 0, int ncol = 0) {
   extern __shared__ double smem[];
@@ -828,8 +832,12 @@ __global__ __launch_bounds__(256) void k_syrk_trail(double* __restrict__ A, int6
   const int64_t base = (int64_t)first * TILE;
   v4d acc[T / 32][T / 32];
   load_tile<T, T>(acc, A, lda, base + (int64_t)a * T, base + (int64_t)b * T);   // acc = C, then acc -= A B^T
-  gemm_tile<KC, KC, T, T, BK, true>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T,
-                                    (int64_t)k0 * TILE, (int64_t)k1 * TILE, smem);
+  if constexpr (GLDS && T == 64 && BK == 16)
+    gemm_tile64_glds<KC, KC, true>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T, (int64_t)k0 * TILE,
+                                   (int64_t)k1 * TILE, smem);
+  else
+    gemm_tile<KC, KC, T, T, BK, true>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T,
+                                      (int64_t)k0 * TILE, (int64_t)k1 * TILE, smem);
   store_tile<T, T>(acc, A, lda, base + (int64_t)a * T, base + (int64_t)b * T, 1.0, 0.0);
 }
 
@@ -858,7 +866,8 @@ __device__ __forceinline__ bool tri_find(const TriProb* __restrict__ probs, int 
   return false;
 }
 
-template <int T>
+// GLDS (T = 64 only): gemm_tile64_glds as in k_syrk_trail (k_trtri_R likewise)
+template <int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_trtri_T(const double* __restrict__ L, int64_t ldl,
                                                     const double* __restrict__ Linv, int64_t ldi,
                                                     double* __restrict__ Tmp, int64_t ldt,
@@ -883,12 +892,15 @@ __global__ __launch_bounds__(256, 2) void k_trtri_T(const double* __restrict__ L
     const int64_t m0 = (int64_t)p.mid * TILE + (int64_t)ti * T, n0 = (int64_t)p.lo * TILE + (int64_t)tj * T;
     v4d acc[T / 32][T / 32];
     acc_zero(acc);
-    gemm_tile<KC, RC, T, T, TileCfg<T>::bk>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
+    if constexpr (GLDS && T == 64)
+      gemm_tile64_glds<KC, RC>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
+    else
+      gemm_tile<KC, RC, T, T, TileCfg<T>::bk>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
     store_tile<T, T>(acc, Tmp, ldt, m0, n0, 1.0, 0.0);
   }
 }
 
-template <int T>
+template <int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_trtri_R(double* __restrict__ Linv, int64_t ldi,
                                                     const double* __restrict__ Tmp, int64_t ldt,
                                                     const TriProb* __restrict__ probs, int nprob, int64_t bsL = 0,
@@ -912,7 +924,10 @@ __global__ __launch_bounds__(256, 2) void k_trtri_R(double* __restrict__ Linv, i
     const int64_t m0 = (int64_t)p.mid * TILE + (int64_t)ti * T, n0 = (int64_t)p.lo * TILE + (int64_t)tj * T;
     v4d acc[T / 32][T / 32];
     acc_zero(acc);
-    gemm_tile<KC, RC, T, T, TileCfg<T>::bk>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
+    if constexpr (GLDS && T == 64)
+      gemm_tile64_glds<KC, RC>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
+    else
+      gemm_tile<KC, RC, T, T, TileCfg<T>::bk>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
     store_tile<T, T>(acc, Linv, ldi, m0, n0, -1.0, 0.0);
   }
 }
@@ -946,7 +961,8 @@ __global__ __launch_bounds__(256, 2) void k_lauum_tiles32(const double* __restri
 // off-diagonal tiles weighted x2.  Optionally stores Kinv (lower tiles) for tests.
 // from_kinv: the tiles of K^-1 are already in Kinv (k_lauum_tiles, slot stride bsK): only the gradient epilogue runs, each
 // thread on the elements it would own after the GEMM - the partial sums are the fused kernel's, bit for bit.
-template <int KERN, int DCAP, int T>
+// GLDS (T = 64 only): gemm_tile64_glds as in k_syrk_trail.
+template <int KERN, int DCAP, int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict__ Linv, int64_t ldi, int64_t np,
                                                        int64_t n, const double* __restrict__ alpha,
                                                        const double* __restrict__ XsT, int64_t ldx, Hyper h,
@@ -972,8 +988,11 @@ __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict_
     load_tile<T, T>(acc, Kinv + slot * bsK, ldk, (int64_t)ti * T, (int64_t)tj * T);
   } else {
     acc_zero(acc);
-    gemm_tile<RC, RC, T, T, TileCfg<T>::bk>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np,
-                                            smem);
+    if constexpr (GLDS && T == 64)
+      gemm_tile64_glds<RC, RC>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np, smem);
+    else
+      gemm_tile<RC, RC, T, T, TileCfg<T>::bk>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T,
+                                              np, smem);
     if (Kinv) store_tile<T, T>(acc, Kinv, ldk, (int64_t)ti * T, (int64_t)tj * T, 1.0, 0.0);
   }
   // stage coordinates and alpha in the (now free) GEMM LDS

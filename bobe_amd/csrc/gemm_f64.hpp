@@ -425,6 +425,108 @@ __device__ __forceinline__ void gemm_tile128_glds(v4d (&acc)[4][4], const double
   BOBE_STAMPS_END(tid);
 }
 
+// ---- 64 x 64 tiles, BK = 16: the same loop as gemm_tile128_glds --------------------------------------------------------
+// The same MFMAs as gemm_tile<LA, LB, 64, 64, 16, NEGA> in the same order for every accumulator (same bits).  An operand tile
+// of 64 x 16 is eight wave-instructions of 1 KiB, two per wave.
+//   * KC: [64][16] unpadded, chunk c of row r at c ^ ((r >> 1) & 7) - the 128 image's layout and read, on 64 rows.
+//   * RC: a 64-wide k-row is only 512 B, so one instruction carries k-rows 2g and 2g + 1 and the row pad cannot be kept.
+//     The image is [16][64] with the chunks of every ODD k-row stored at c ^ 8 (element (k, r) at k * 64 + (r ^ 16 (k & 1)));
+//     the source address carries the permutation, the read applies it again.  A 32-lane ds_read_b64 group reads k-rows
+//     4 ks and 4 ks + 1 at 16 consecutive r from a multiple of 16: 32 dwords each, which the XOR puts in opposite halves of
+//     the 64 banks (unpadded, k-rows k and k + 1 are 128 dwords apart: the same 32 banks, a two-way conflict).
+// 32,768 B of LDS (two buffers of two 8 KiB images), within GEMM64_SMEM_BYTES and k_syrk_trail's SYRK64_SMEM, so the
+// launches keep their occupancy.  No TRIL variant (no 64-tile caller skips a diagonal block).
+constexpr int IMG64_DOUBLES = 64 * 16;
+constexpr int GEMM64_GLDS_SMEM_DOUBLES = 4 * IMG64_DOUBLES;
+static_assert(GEMM64_GLDS_SMEM_DOUBLES * 8 <= GEMM64_SMEM_BYTES, "the 64-tile LDS images must fit GEMM64_SMEM_BYTES");
+
+template <int L>
+__device__ __forceinline__ void glds_stage64(const double* __restrict__ p, int64_t ld, int64_t r0, int64_t k0, double* img,
+                                             int wave, int lane) {
+  const double* base = (L == KC) ? p + r0 * ld + k0 : p + k0 * ld + r0;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int g = wave + 4 * i;
+    unsigned off;
+    if (L == KC) {
+      const int r = 8 * g + (lane >> 3);
+      off = (unsigned)((r * ld + 2 * ((lane & 7) ^ ((r >> 1) & 7))) * 8);
+    } else {
+      const int h = lane >> 5;                                     // k-row 2 g + h, LDS chunk lane & 31
+      off = (unsigned)(((2 * g + h) * ld + 2 * ((lane & 31) ^ (8 * h))) * 8);
+    }
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(img + 128 * g), 16, off, 0, 0, 0);
+  }
+}
+
+template <int L>
+__device__ __forceinline__ double frag_read64(const double* img, int woff, int s, int ks, int lane) {
+  if (L == KC) {
+    const int h = (lane >> 5) ^ ((lane & 15) >> 1);
+    return img[(woff + 16 * s + (lane & 15)) * 16 + 2 * ((2 * ks) ^ h) + ((lane >> 4) & 1)];
+  } else {
+    return img[(4 * ks + (lane >> 4)) * 64 + ((woff + 16 * s + (lane & 15)) ^ (((lane >> 4) & 1) << 4))];
+  }
+}
+
+template <int LA, int LB, bool NEGA = false>
+__device__ __forceinline__ void gemm_tile64_glds(v4d (&acc)[2][2], const double* __restrict__ A, int64_t lda, int64_t m0,
+                                                 const double* __restrict__ B, int64_t ldb, int64_t n0, int64_t kbeg,
+                                                 int64_t kend, double* smem, int tid = threadIdx.x) {
+  constexpr int BK = 16;
+  static_assert(BK64 == BK, "gemm_tile64_glds is the BK = 16 loop");
+  constexpr int IA = IMG64_DOUBLES, IB = IMG64_DOUBLES;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = (wave >> 1) * 32;
+  const int wn = (wave & 1) * 32;
+  if (kend <= kbeg) return;
+  auto stage = [&](int64_t k0, int b) {
+    double* ia = smem + b * (IA + IB);
+    glds_stage64<LA>(A, lda, m0, k0, ia, wave, lane);
+    glds_stage64<LB>(B, ldb, n0, k0, ia + IA, wave, lane);
+  };
+  double fa[2][2], fb[2][2];
+  auto frags = [&](double (&a)[2], double (&b)[2], const double* ia, int ks) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) a[s] = frag_read64<LA>(ia, wm, s, ks, lane);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) b[s] = frag_read64<LB>(ia + IA, wn, s, ks, lane);
+  };
+  // (NEGA negates A in the MFMA phase, a sub-step after its read: negated where it is read, every sub-step would wait
+  // for the reads it has just issued)
+  auto mfmas = [&](int ks) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const double a = NEGA ? -fa[ks & 1][i] : fa[ks & 1][i];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, fb[ks & 1][j], acc[i][j], 0, 0, 0);
+    }
+  };
+  stage(kbeg, 0);
+  __syncthreads();
+  frags(fa[0], fb[0], smem, 0);
+  int buf = 0;
+  for (int64_t k0 = kbeg; k0 < kend; k0 += BK) {
+    stage(k0 + BK < kend ? k0 + BK : k0, buf ^ 1);
+    const double* ia = smem + buf * (IA + IB);
+#pragma unroll
+    for (int ks = 0; ks < BK / 4 - 1; ++ks) {
+      frags(fa[(ks + 1) & 1], fb[(ks + 1) & 1], ia, ks + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas(ks);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+    buf ^= 1;
+    frags(fa[0], fb[0], smem + buf * (IA + IB), 0);
+    __builtin_amdgcn_sched_barrier(0);
+    mfmas(BK / 4 - 1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // Coordinates of accumulator element (i, j, r) of this lane inside the TM x TN tile.
 template <int TM = 128>
 __device__ __forceinline__ int acc_row(int i, int r, int tid = threadIdx.x) {

@@ -31,9 +31,12 @@ void configure_factor_kernels() {
   allow_big_lds(k_trtri_T<128>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trtri_R<128>, GEMM_SMEM_BYTES);
   allow_big_lds(k_syrk_trail<64, SYRK64_BK>, SYRK64_SMEM);
+  allow_big_lds(k_syrk_trail<64, SYRK64_BK, true>, SYRK64_SMEM);
   allow_big_lds(k_syrk_trail<32, SYRK32_BK>, SYRK32_SMEM);
   allow_big_lds(k_trtri_T<64>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_trtri_R<64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trtri_T<64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trtri_R<64, true>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_trtri_T<32>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_trtri_R<32>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_lauum_tiles32, GEMM32_SMEM_BYTES);
@@ -43,6 +46,12 @@ void configure_factor_kernels() {
   allow_big_lds(k_lauum_grad<1, 8, 64>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_lauum_grad<1, 16, 64>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_lauum_grad<1, 32, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_lauum_grad<0, 8, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_lauum_grad<0, 16, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_lauum_grad<0, 32, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_lauum_grad<1, 8, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_lauum_grad<1, 16, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_lauum_grad<1, 32, 64, true>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_lauum_grad<0, 8, 128>, GEMM_SMEM_BYTES);
   allow_big_lds(k_lauum_grad<0, 16, 128>, GEMM_SMEM_BYTES);
   allow_big_lds(k_lauum_grad<0, 32, 128>, GEMM_SMEM_BYTES);
@@ -54,7 +63,7 @@ void configure_factor_kernels() {
 
 const Tuning& tuning() {
   static Tuning t = [] {
-    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false, true, true};
+    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false, true, true, true};
     auto geti = [](const char* name, int& dst) {
       const char* e = std::getenv(name);
       if (e) dst = std::atoi(e);
@@ -75,6 +84,9 @@ const Tuning& tuning() {
     int glds = 1;
     geti("BOBE_GEMM_GLDS", glds);
     v.gemm_glds = glds != 0;
+    int glds64 = 1;
+    geti("BOBE_GEMM64_GLDS", glds64);
+    v.gemm64_glds = glds64 != 0;
     return v;
   }();
   return t;
@@ -267,8 +279,10 @@ void bobe_gp::syrk(double* a, int k0, int k1, int first, int colmode, int B, int
     return;
   }
   const TileGrid tg = colmode ? TileGrid{t64, 0} : tile_grid(t64);
-  hipLaunchKernelGGL((k_syrk_trail<64, SYRK64_BK>), dim3(tg.grid, B), dim3(256), SYRK64_SMEM, stream, a, Np, k0, k1, first,
-                     colmode, n64, bsA, tg.per, colk0, far_col, nc64);
+  // (the tile core BOBE_GEMM64_GLDS selects, through a function pointer: every argument is passed)
+  const auto k64 = tu.gemm64_glds ? k_syrk_trail<64, SYRK64_BK, true> : k_syrk_trail<64, SYRK64_BK, false>;
+  hipLaunchKernelGGL(k64, dim3(tg.grid, B), dim3(256), SYRK64_SMEM, stream, a, Np, k0, k1, first, colmode, n64, bsA, tg.per,
+                     colk0, far_col, nc64);
 }
 
 int bobe_gp::panel_strips(int B, int rr) const {
@@ -541,9 +555,11 @@ void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, in
                          (const double*)tmp, Np, pr, D.count, bsL, bsT, tg.per);
     } else if (D.nblocks < tu.trtri64_below) {
       const TileGrid tg = tile_grid(2 * D.nblocks);             // (tile pairs of complementary K: equal work)
-      hipLaunchKernelGGL(k_trtri_T<64>, dim3(tg.grid, B), dim3(256), GEMM64_SMEM_BYTES, stream, a, Np,
+      const auto kT = tu.gemm64_glds ? k_trtri_T<64, true> : k_trtri_T<64, false>;
+      const auto kR = tu.gemm64_glds ? k_trtri_R<64, true> : k_trtri_R<64, false>;
+      hipLaunchKernelGGL(kT, dim3(tg.grid, B), dim3(256), GEMM64_SMEM_BYTES, stream, a, Np,
                          (const double*)linv, Np, tmp, Np, pr, D.count, bsA, bsL, bsT, tg.per);
-      hipLaunchKernelGGL(k_trtri_R<64>, dim3(tg.grid, B), dim3(256), GEMM64_SMEM_BYTES, stream, linv, Np,
+      hipLaunchKernelGGL(kR, dim3(tg.grid, B), dim3(256), GEMM64_SMEM_BYTES, stream, linv, Np,
                          (const double*)tmp, Np, pr, D.count, bsL, bsT, tg.per);
     } else {
       hipLaunchKernelGGL(k_trtri_T<128>, dim3(D.nblocks, B), dim3(256), GEMM_SMEM_BYTES, stream, a, Np,
@@ -577,10 +593,11 @@ int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const d
     hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, linv, Np, Np, scratch, Np,
                        bsL, bsS, B);
   }
+  const bool g64 = tuning().gemm64_glds;       // (the 64-tile core; no effect on TT = 128)
 #define LG(KE, DC, TT)                                                                                          \
-  hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT>), dim3(ntiles * B), dim3(256),                                   \
-                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst, Np, h, \
-                     gpo, kio, Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK)
+  hipLaunchKernelGGL((g64 ? k_lauum_grad<KE, DC, TT, TT == 64> : k_lauum_grad<KE, DC, TT, false>), dim3(ntiles * B), \
+                     dim3(256), (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst,   \
+                     Np, h, gpo, kio, Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK)
 #define LGD(KE, TT)                                                                 \
   do {                                                                              \
     if (dcap == 8) LG(KE, 8, TT); else if (dcap == 16) LG(KE, 16, TT); else LG(KE, 32, TT); \

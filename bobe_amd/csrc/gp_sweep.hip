@@ -15,18 +15,25 @@ void configure_sweep_kernels() {
   allow_big_lds(k_trimul<true>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul<false>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul_t, GEMM_SMEM_BYTES);
-  allow_big_lds(k_trimul_v64, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_trimul_t64, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trimul_v64<true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trimul_v64<false>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trimul_t64<true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trimul_t64<false>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_blk_step, GEMM_SMEM_BYTES);
   allow_big_lds(k_cross_vv<128, true>, GEMM_SMEM_BYTES);
   allow_big_lds(k_cross_vv<128, false>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_cross_vv<64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_cross_vv<64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_cross_vv<64, false>, GEMM64_SMEM_BYTES);
   done[dev] = true;
 }
 
 // the sweep's 128-tile GEMM kernels on the tile core BOBE_GEMM_GLDS selects (a function pointer: pass every argument)
 static auto trimul_kernel() { return tuning().gemm_glds ? k_trimul<true> : k_trimul<false>; }
 static auto cross_vv128_kernel() { return tuning().gemm_glds ? k_cross_vv<128, true> : k_cross_vv<128, false>; }
+// and the 64-tile ones on the core BOBE_GEMM64_GLDS selects
+static auto cross_vv64_kernel() { return tuning().gemm64_glds ? k_cross_vv<64, true> : k_cross_vv<64, false>; }
+static auto trimul_v64_kernel() { return tuning().gemm64_glds ? k_trimul_v64<true> : k_trimul_v64<false>; }
+static auto trimul_t64_kernel() { return tuning().gemm64_glds ? k_trimul_t64<true> : k_trimul_t64<false>; }
 }  // namespace bobe
 
 void bobe_gp::decide_refinement(double min_diag) {
@@ -73,7 +80,7 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
   const bool few = (Mp / TILE) * nb < 2 * std::max(num_cus, 1);
   auto make_w = [&]() {
     if (few)
-      hipLaunchKernelGGL(k_trimul_t64, dim3((unsigned)(Mp / 64), (unsigned)(2 * nb)), dim3(256), GEMM64_SMEM_BYTES, stream,
+      hipLaunchKernelGGL(trimul_t64_kernel(), dim3((unsigned)(Mp / 64), (unsigned)(2 * nb)), dim3(256), GEMM64_SMEM_BYTES, stream,
                          (const double*)Linv.d(), Np, 2 * nb, (const double*)VZ.d(), Mp, WZ.d(), Mp);
     else
       hipLaunchKernelGGL(k_trimul_t, dim3((unsigned)(Mp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
@@ -103,7 +110,7 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
                        (const double*)qpart.d(), Mp, nb, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
   } else if (few) {
     const int nt = 2 * nb;
-    hipLaunchKernelGGL(k_trimul_v64, dim3((unsigned)(Mp / 64), (unsigned)nt), dim3(256), GEMM64_SMEM_BYTES, stream,
+    hipLaunchKernelGGL(trimul_v64_kernel(), dim3((unsigned)(Mp / 64), (unsigned)nt), dim3(256), GEMM64_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nt, (const double*)kXZ.d(), Mp, VZ.d(), Mp, qpart.d(), Mp);
     hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
                        (const double*)qpart.d(), Mp, nt, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
@@ -168,7 +175,7 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
       hipLaunchKernelGGL(cross_vv128_kernel(), dim3((unsigned)(ncp_ / TILE), (unsigned)nzt), dim3(256), GEMM_SMEM_BYTES, stream,
                          (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, SC);
     else
-      hipLaunchKernelGGL(k_cross_vv<64>, dim3((unsigned)(ncp_ / 64), (unsigned)(Mp / 64)), dim3(256), GEMM64_SMEM_BYTES,
+      hipLaunchKernelGGL(cross_vv64_kernel(), dim3((unsigned)(ncp_ / 64), (unsigned)(Mp / 64)), dim3(256), GEMM64_SMEM_BYTES,
                          stream, (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, SC);
     prof_end(BOBE_PROF_CROSSVV);
   };

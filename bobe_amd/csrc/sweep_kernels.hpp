@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void k_colsq_tile_parts(const double* __restri
 // scores came out 1e-2 ... 1 (relative) off an extended-precision evaluation where the triangular-solve form is 1e-4 ...
 // 1e-1 off (profiles/r05_conditioning.txt, tests/test_gpu_conditioning.py).  Same 2 N M flops per candidate.
 // T = 128: grid (ncols / 128, Mp / 128); T = 64: grid (ncols / 64, Mp / 64) - few integration points fill the chip only
-// with the small tile.  GLDS: the 128-tile core as in k_trimul (no effect on T = 64).
+// with the small tile.  GLDS: the 128-tile core as in k_trimul (T = 128) or gemm_tile64_glds (T = 64; BOBE_GEMM64_GLDS).
 template <int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ VZ, int64_t ldz,
                                                      const double* __restrict__ V, int64_t ldv, int64_t kend,
@@ -196,7 +196,10 @@ __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ 
       gemm_tile<RC, RC>(acc, VZ, ldz, (int64_t)tz * TILE, V, ldv, (int64_t)tc * TILE, 0, kend, smem);
     store_tile(acc, crossT, ldx, (int64_t)tz * TILE, (int64_t)tc * TILE, 1.0, 0.0);
   } else {
-    gemm_tile<RC, RC, 64, 64, BK64>(acc, VZ, ldz, (int64_t)tz * 64, V, ldv, (int64_t)tc * 64, 0, kend, smem);
+    if constexpr (GLDS)
+      gemm_tile64_glds<RC, RC>(acc, VZ, ldz, (int64_t)tz * 64, V, ldv, (int64_t)tc * 64, 0, kend, smem);
+    else
+      gemm_tile<RC, RC, 64, 64, BK64>(acc, VZ, ldz, (int64_t)tz * 64, V, ldv, (int64_t)tc * 64, 0, kend, smem);
     store_tile<64, 64>(acc, crossT, ldx, (int64_t)tz * 64, (int64_t)tc * 64, 1.0, 0.0);
   }
 }
@@ -218,6 +221,8 @@ __global__ __launch_bounds__(256, 2) void k_trimul_t(const double* __restrict__ 
 // ---- the same two products on 64 x 64 tiles, for right-hand sides with FEW columns (the M = 512 integration points of a
 // sweep: 4 x nb tiles of 128 x 128 leave half the chip idle for two launches of ~0.57 ms each at N = 4096; 8 x 2nb tiles
 // of 64 x 64 fill it).  V = Linv B with the column sums of squares per 64-row tile (qpart[2 nb][.]), W = Linv^T V.
+// GLDS: gemm_tile64_glds or the register-staged gemm_tile (BOBE_GEMM64_GLDS).
+template <bool GLDS>
 __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict__ Linv, int64_t ldi, int nt,
                                                        const double* __restrict__ B, int64_t ldb, double* __restrict__ V,
                                                        int64_t ldv, double* __restrict__ qpart, int64_t ldq) {
@@ -226,7 +231,11 @@ __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict_
   const int ti = nt - 1 - (int)blockIdx.y;                      // long K first
   v4d acc[2][2];
   acc_zero(acc);
-  gemm_tile<KC, RC, 64, 64, BK64>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64, smem);
+  if constexpr (GLDS)
+    gemm_tile64_glds<KC, RC>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64, smem);
+  else
+    gemm_tile<KC, RC, 64, 64, BK64>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64,
+                                    smem);
   store_tile<64, 64>(acc, V, ldv, (int64_t)ti * 64, (int64_t)tc * 64, 1.0, 0.0);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   double* red = smem;  // [2][64]
@@ -245,6 +254,7 @@ __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict_
   if (t < 64) qpart[(int64_t)ti * ldq + (int64_t)tc * 64 + t] = red[t] + red[64 + t];
 }
 
+template <bool GLDS>
 __global__ __launch_bounds__(256, 2) void k_trimul_t64(const double* __restrict__ Linv, int64_t ldi, int nt,
                                                        const double* __restrict__ V, int64_t ldv, double* __restrict__ W,
                                                        int64_t ldw) {
@@ -253,8 +263,12 @@ __global__ __launch_bounds__(256, 2) void k_trimul_t64(const double* __restrict_
   const int tc = blockIdx.x;
   v4d acc[2][2];
   acc_zero(acc);
-  gemm_tile<RC, RC, 64, 64, BK64>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64,
-                                  (int64_t)nt * 64, smem);
+  if constexpr (GLDS)
+    gemm_tile64_glds<RC, RC>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64, (int64_t)nt * 64,
+                             smem);
+  else
+    gemm_tile<RC, RC, 64, 64, BK64>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64,
+                                    (int64_t)nt * 64, smem);
   store_tile<64, 64>(acc, W, ldw, (int64_t)ti * 64, (int64_t)tc * 64, 1.0, 0.0);
 }
 

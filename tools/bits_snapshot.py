@@ -41,6 +41,9 @@ for N, d, kern in SIZES:
         r = gp.wip_sweep(rs.uniform(size=(700, d)), rs.uniform(size=(96, d)), want_mean_var=True)
         gp._lib.bobe_gp_set_chunk(gp._h, 0)
         out[f"sw_{N}"] = np.concatenate([r["wipv"], r["wipstd"], r["mean"], r["var"], [r["argmin_v"], r["argmin_s"]]])
+        if os.environ.get("BITS_WIP_GRAD"):   # score gradients: the W_Z = Linv^T V_Z product (k_trimul_t64 at these sizes)
+            gv = gp.wip_grad(rs.uniform(size=(300, d)), rs.uniform(size=(96, d)))
+            out[f"wg_{N}"] = np.concatenate([np.ravel(a) for a in gv])
     elif os.environ.get("BITS_BIG_SWEEP"):    # three chunks of 16384 candidates, 512 integration points: the fused cross
         rs = np.random.default_rng(10_000 + N)  # tiles in k_trimul and a closing k_cross_vv<128>
         gp._lib.bobe_gp_set_chunk(gp._h, 16384)
