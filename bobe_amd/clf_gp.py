@@ -178,6 +178,9 @@ class GPwithClassifier(GP):
         m, v, dm, dv = super().predict_grad(x, mean_only=mean_only)
         return (np.where(np.isneginf(m), self.minus_inf, m), v, dm, dv) if self._gated() else (m, v, dm, dv)
 
+    # (``predict_cov`` and ``sample_posterior`` are inherited unchanged and NOT gated: the joint posterior of the plain GP,
+    # like ``fantasy_var``, clf_gp.py:207-212)
+
     def update(self, new_x, new_y):
         """clf_gp.py:214-246: extend the classifier set, re-derive the GP subset, refactor."""
         new_x = np.atleast_2d(np.asarray(new_x, dtype=np.float64))

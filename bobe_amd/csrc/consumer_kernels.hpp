@@ -217,15 +217,7 @@ __global__ __launch_bounds__(256) void k_hmc_leapfrog(const double* __restrict__
 //   hist  [niter - hist_from][P][d]   u after iterations >= hist_from of this launch        (may be null)
 //   keep  [niter / thin][P][d+1]      x and mean after every thin-th iteration of this launch (may be null)
 //   dbg   [P][d+3]   last iteration's p0 (d), L, uniform, acceptance probability             (may be null)
-__device__ __forceinline__ unsigned long long hmc_mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ double hmc_u01(unsigned long long bits) {          // in (0, 1)
-  return ((double)(bits >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-}
+// (hmc_mix64 / hmc_u01: kernels_common.hpp)
 
 // Training points a thread of a 256-thread chain workgroup keeps in registers for the whole launch (a launch is hundreds
 // of leapfrog / random-walk steps over the same points): 256 x RESIDENT rows, the rest is streamed from L2 every step.

@@ -270,6 +270,23 @@ int bobe_gp_fantasy_var(bobe_gp_t* g, const double* cand, int64_t C, const doubl
   API_END
 }
 
+int bobe_gp_predict_cov(bobe_gp_t* g, const double* Xq, int64_t C, double* cov) {
+  API_BEGIN
+  NEED(g && Xq && cov, "NULL argument");
+  g->use();
+  return g->predict_cov(Xq, C, cov);
+  API_END
+}
+
+int bobe_gp_posterior_sample(bobe_gp_t* g, const double* Xq, int64_t C, int64_t S, uint64_t seed, const double* z,
+                             int centered, double* draws, double* jitter_out) {
+  API_BEGIN
+  NEED(g && Xq && draws, "NULL argument");
+  g->use();
+  return g->posterior_sample(Xq, C, S, seed, z, centered, draws, jitter_out);
+  API_END
+}
+
 int bobe_gp_wip_grad(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                      double* wipv, double* wipstd, double* dwipv, double* dwipstd) {
   API_BEGIN

@@ -4,6 +4,7 @@
 //                     (single evaluation, evaluation slots, lock-step batch, graph replay), state restore
 //   gp_sweep.hip      prediction / acquisition sweep, score and posterior gradients, rank-b append
 //   gp_consumers.hip  HMC on the surrogate, EI / LogEI, the classifier gate, GP.kernel, device clone
+//   gp_posterior.hip  joint posterior covariance at query points and correlated draws from it
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
 // without a HIP device every entry point fails with BOBE_ERR_HIP.
@@ -145,6 +146,7 @@ inline TileGrid tile_grid(int ntiles) {
 void configure_factor_kernels();
 void configure_sweep_kernels();
 void configure_consumer_kernels();
+void configure_posterior_kernels();
 
 struct Depth { int first, count, nblocks; };
 
@@ -382,6 +384,7 @@ struct bobe_gp {
     bobe::configure_factor_kernels();
     bobe::configure_sweep_kernels();
     bobe::configure_consumer_kernels();
+    bobe::configure_posterior_kernels();
   }
   void sync() { HIPCHK(hipStreamSynchronize(stream)); }
 
@@ -467,6 +470,11 @@ struct bobe_gp {
                 double* dwipv, double* dwipstd);
   void predict_grad(const double* Xq, int64_t C, double* mean, double* var, double* dmean, double* dvar);
   int append(const double* X_new, int64_t b, const double* y_all);
+
+  // ---- gp_posterior.hip (call-local buffers only; the factorisation of Sigma runs on a data-less child handle)
+  int predict_cov(const double* Xq, int64_t C, double* cov);
+  int posterior_sample(const double* Xq, int64_t C, int64_t S, uint64_t seed, const double* z, int centered, double* draws,
+                       double* jitter_out);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

@@ -44,6 +44,18 @@ __device__ __forceinline__ double kern_grad_factor(double r2, double kvar, doubl
   }
 }
 
+// ---- counter hash of the device's random numbers (the samplers' chains, the posterior draws' normals) --------------------
+// splitmix64's finaliser of a 64-bit counter, and its top 53 bits as a uniform in (0, 1)
+__device__ __forceinline__ unsigned long long hmc_mix64(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ double hmc_u01(unsigned long long bits) {          // in (0, 1)
+  return ((double)(bits >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+}
+
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
   union { double d; int i[2]; } u;
   u.d = v;

@@ -562,6 +562,36 @@ class GP:
         m, v = self.predict_batched(x)
         return m[0], v[0:1]
 
+    # ------------------------------------------------------------------ joint posterior
+    def predict_cov(self, x):
+        """The joint posterior covariance of f + noise at the C rows of ``x`` (C x C, physical units: x y_std^2):
+        k(x_i, x_j) + noise [i = j] - v_i . v_j with v = L^-1 k(X, x) - scikit-learn's ``predict(return_cov=True)`` plus
+        noise I.  Its diagonal is ``predict_var_batched`` before the clip.  1 <= C <= 16384.  Not gated: a
+        ``GPwithClassifier`` returns the plain GP's covariance.  A NaN state gives a NaN matrix."""
+        x = _lib.as_f64(np.atleast_2d(x))
+        c = x.shape[0]
+        out = np.empty((c, c))
+        _lib.check(self._lib.bobe_gp_predict_cov(self._h, _lib.ptr(x), c, _lib.ptr(out)), "bobe_gp_predict_cov")
+        return self.y_std ** 2 * out
+
+    def sample_posterior(self, x, n_samples=1, seed=0, z=None, centered=False, return_jitter=False):
+        """``n_samples`` correlated draws of the posterior at the C rows of ``x``, an (n_samples, C) array in physical
+        units: y_mean + y_std (m + L z_s), or y_std L z_s with ``centered=True`` (m: ``predict_mean_batched``'s mean in
+        standardised units, L: the Cholesky factor of the standardised ``predict_cov`` with the smallest jitter that
+        factorises).  ``z``: (n_samples, C) standard normals; None draws them on the device from ``seed`` (a counter
+        hash: the same seed gives the same draws).  ``return_jitter``: also return the jitter added to the standardised
+        covariance.  Not gated (like ``predict_cov``).  A covariance that does not factorise gives NaN draws."""
+        x = _lib.as_f64(np.atleast_2d(x))
+        c, s = x.shape[0], int(n_samples)
+        zz = None if z is None else _lib.as_f64(z, (s, c))
+        out = np.empty((s, c))
+        jit = C.c_double(0.0)
+        _lib.check(self._lib.bobe_gp_posterior_sample(self._h, _lib.ptr(x), c, s, int(seed) & (2 ** 64 - 1), _lib.ptr(zz),
+                                                      1 if centered else 0, _lib.ptr(out), C.byref(jit)),
+                   "bobe_gp_posterior_sample")
+        out = self.y_std * out if centered else self.y_mean + self.y_std * out
+        return (out, jit.value) if return_jitter else out
+
     # ------------------------------------------------------------------ update
     def update(self, new_x, new_y):
         """BOBE/gp.py:495-541 — duplicate filter, re-standardise, full refactor."""

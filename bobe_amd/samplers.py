@@ -75,10 +75,16 @@ def _draw_in_ellipsoid(mu, A, n, rng):
     return x[np.all((x >= 0.0) & (x <= 1.0), axis=1)]
 
 
-def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float) -> Dict:
+def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float, *, n_draws: int = 0,
+                      draws_seed: int = 0, draws_max_points: int = 16384) -> Dict:
     """The logZ dictionary of a finished run (samplers.py:172-183): the GP's predictive variance at every sample —
     ONE batched ``bobe_gp_predict`` call instead of the reference's ``lax.map`` over points — turns into
-    logl +- std for the upper / lower evidence integrals and into the variance estimate of logZ."""
+    logl +- std for the upper / lower evidence integrals and into the variance estimate of logZ.
+
+    ``upper`` / ``lower`` treat the GP's errors at the samples as perfectly correlated, ``var`` / ``std`` as independent.
+    ``n_draws > 0`` adds the distribution the GP itself implies (``_logz_draws``): ``draws`` (logZ of ``n_draws`` joint
+    posterior draws of the surrogate at the samples), ``draws_mean``, ``draws_std``, ``draws_points``, ``draws_jitter``.
+    The other keys do not depend on it, and the run's generator is not used."""
     logl = np.asarray(logl, dtype=np.float64)
     var = np.asarray(gp.predict_var_batched(samples_x), dtype=np.float64)
     std = np.sqrt(var)
@@ -87,8 +93,53 @@ def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float)
     var = np.clip(var, 1e-12, 1e12)
     log_var_delta = compute_integrals(logl=2 * logl + np.log(var), logvol=logvol, squared=True)[-1]
     var_logz = math.exp(float(np.clip(log_var_delta - 2 * mean, -100, 100)))
-    return {"mean": float(mean), "dlogz_sampler": float(logz_err), "upper": float(upper[-1]), "lower": float(lower[-1]),
-            "var": var_logz, "std": 2 * math.sqrt(var_logz)}
+    out = {"mean": float(mean), "dlogz_sampler": float(logz_err), "upper": float(upper[-1]), "lower": float(lower[-1]),
+           "var": var_logz, "std": 2 * math.sqrt(var_logz)}
+    if n_draws > 0:
+        out.update(_logz_draws(gp, samples_x, logl, logvol, int(n_draws), int(draws_seed), int(draws_max_points)))
+    return out
+
+
+def _log_weights(logl, logvol):
+    """The trapezoid weights of ``compute_integrals`` per sample (what ``nested_sampling`` reports as logwt)."""
+    pad = np.concatenate([[-1e300], logl])
+    dv = np.diff(logvol, prepend=0)
+    return np.logaddexp(pad[1:], pad[:-1]) + (logvol - dv + np.log1p(-np.exp(dv))) + math.log(0.5)
+
+
+def draws_points(gp, logl, logvol, max_points: int = 16384) -> np.ndarray:
+    """Indices (ascending) of the samples whose logl the evidence draws perturb: those with the largest weight ``logwt``,
+    at most ``max_points`` of them (ties: the earlier sample).  A sample with a non-finite logl or the gate's mark
+    ``gp.minus_inf`` is held fixed."""
+    logl = np.asarray(logl, dtype=np.float64)
+    free = np.isfinite(logl)
+    minus_inf = getattr(gp, "minus_inf", None)
+    if minus_inf is not None:
+        free &= logl != float(minus_inf)
+    idx = np.flatnonzero(free)
+    if len(idx) > max_points:
+        logwt = _log_weights(logl, np.asarray(logvol, dtype=np.float64))
+        idx = np.sort(idx[np.argsort(-logwt[idx], kind="stable")[:max_points]])
+    return idx
+
+
+def _logz_draws(gp, samples_x, logl, logvol, n_draws: int, seed: int, max_points: int) -> Dict:
+    """logZ of ``n_draws`` draws of the surrogate: draw s integrates logl + delta_s, delta_s a CENTRED joint posterior draw
+    of the GP at the perturbed samples (``draws_points``; ``gp.sample_posterior(..., centered=True)``, seeded by ``seed``)
+    and 0 elsewhere."""
+    logl = np.asarray(logl, dtype=np.float64)
+    idx = draws_points(gp, logl, logvol, max_points)
+    delta, jitter = np.zeros((n_draws, 0)), 0.0
+    if len(idx):
+        delta, jitter = gp.sample_posterior(np.asarray(samples_x)[idx], n_samples=n_draws, seed=seed, centered=True,
+                                            return_jitter=True)
+    draws = np.empty(n_draws)
+    for s in range(n_draws):
+        ls = logl.copy()
+        ls[idx] += delta[s]
+        draws[s] = compute_integrals(logl=ls, logvol=logvol)[-1]
+    return {"draws": draws, "draws_mean": float(np.mean(draws)), "draws_std": float(np.std(draws)),
+            "draws_points": int(len(idx)), "draws_jitter": float(jitter)}
 
 
 def _rwalk_pool(loglike, live, live_logl, worst, lstar, rng, n_walkers, walks, scale, gp=None):
@@ -130,7 +181,8 @@ def _rwalk_pool(loglike, live, live_logl, worst, lstar, rng, n_walkers, walks, s
 def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", dlogz: float = 0.01,
                     maxcall: int = int(5e6), equal_weights: bool = False, rng=None, batch: int = 8192,
                     enlarge: float = 1.25, nlive: Optional[int] = None, sample_method: str = "auto",
-                    walks: Optional[int] = None, device_walks: bool = True) -> Tuple[Dict, Dict, bool]:
+                    walks: Optional[int] = None, device_walks: bool = True, logz_draws: int = 0,
+                    logz_draws_seed: int = 0) -> Tuple[Dict, Dict, bool]:
     """Static nested sampling of exp(GP mean) over the unit cube -> (samples_dict, logz_dict, success).
 
     Settings follow ``nested_sampling_Dy`` (samplers.py:119-126): mode 'acq' uses nlive = max(100, min(500, 20 d))
@@ -138,7 +190,9 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     ``sample_method``: 'ellipsoid' = uniform draws in the enlarged bounding ellipsoid of the live points (exact, cheap
     in a few dimensions), 'rwalk' = batched constrained random walks (``_rwalk_pool``; what the reference asks dynesty
     for), 'auto' = ellipsoid up to 4 dimensions, rwalk above.  ``device_walks``: whole walks in one launch where the
-    surrogate offers ``rwalk`` (``bobe_gp_rwalk``); False steps them from the host, one batched prediction per step."""
+    surrogate offers ``rwalk`` (``bobe_gp_rwalk``); False steps them from the host, one batched prediction per step.
+    ``logz_draws`` > 0: the logZ dictionary also holds the evidence of that many joint posterior draws of the surrogate
+    (``logz_from_samples``, seeded by ``logz_draws_seed``); reported only, nothing else depends on them."""
     rng = rng if rng is not None else get_numpy_rng()
     ndim = ndim if ndim is not None else gp.ndim
     if mode == "acq":
@@ -155,8 +209,12 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     if not np.all(np.isfinite(live_logl)):               # a NaN surrogate (factor not positive definite): no evidence
         log.warning("nested sampling skipped: the surrogate returns non-finite values")
         nan = float("nan")
+        logz_nan = {"mean": nan, "dlogz_sampler": nan, "upper": nan, "lower": nan, "var": nan, "std": nan}
+        if logz_draws > 0:
+            logz_nan.update(draws=np.full(int(logz_draws), nan), draws_mean=nan, draws_std=nan, draws_points=0,
+                            draws_jitter=nan)
         return ({"x": live, "weights": np.ones(nlive), "logl": live_logl, "best": live[0], "method": "nested"},
-                {"mean": nan, "dlogz_sampler": nan, "upper": nan, "lower": nan, "var": nan, "std": nan}, False)
+                logz_nan, False)
     use_rwalk = sample_method == "rwalk" or (sample_method == "auto" and ndim > 4)
     walks = walks if walks is not None else max(25, 4 * ndim)           # dynesty's default is 25
     rw_scale = 2.38 / math.sqrt(ndim)
@@ -272,7 +330,8 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     # call logZ converged on it (a run cut by maxcall alone is reported the way dynesty's would be, with a flag)
     success = bool(~np.all(logl == logl[0])) and not gave_up
 
-    logz_dict = logz_from_samples(gp, samples_x, logl, logvol, mean, logz_err)
+    logz_dict = logz_from_samples(gp, samples_x, logl, logvol, mean, logz_err, n_draws=logz_draws,
+                                  draws_seed=logz_draws_seed)
     logz_dict.update(ncall=int(ncall), niter=int(niter), truncated=bool(truncated))
     best_pt = samples_x[int(np.argmax(logl))]
     weights = renormalise_log_weights(logwt)
@@ -293,13 +352,16 @@ def prior_transform(x):
 
 def nested_sampling_Dy(gp, mode: str = "acq", ndim: int = 1, dlogz: float = 0.1, dynamic: bool = False,
                        maxcall: Optional[int] = int(5e6), print_progress: Optional[bool] = True,
-                       equal_weights: bool = False, sample_method: str = "rwalk", rng=None):
+                       equal_weights: bool = False, sample_method: str = "rwalk", rng=None, *, logz_draws: int = 0,
+                       logz_draws_seed: int = 0):
     """The reference's entry point name and keywords (samplers.py:55-65) on ``nested_sampling`` above; ``dynamic``,
     ``print_progress`` are dynesty options without a counterpart here; ``sample_method='rwalk'`` (the reference's
-    default) maps to 'auto': exact ellipsoid draws in up to 4 dimensions, batched random walks above."""
+    default) maps to 'auto': exact ellipsoid draws in up to 4 dimensions, batched random walks above.  ``logz_draws``,
+    ``logz_draws_seed``: see ``nested_sampling``."""
     return nested_sampling(gp, ndim=ndim if ndim and ndim > 1 else gp.ndim, mode=mode, dlogz=dlogz,
                            maxcall=maxcall if maxcall is not None else int(5e6), equal_weights=equal_weights, rng=rng,
-                           sample_method="auto" if sample_method == "rwalk" else sample_method)
+                           sample_method="auto" if sample_method == "rwalk" else sample_method, logz_draws=logz_draws,
+                           logz_draws_seed=logz_draws_seed)
 
 
 def get_hmc_settings(ndim, warmup_steps=None, num_samples=None, thinning=None):

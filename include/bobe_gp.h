@@ -128,6 +128,31 @@ int bobe_gp_fantasy_var(bobe_gp_t* gp, const double* cand, int64_t C, const doub
 int bobe_gp_wip_grad(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                      double* wipv, double* wipstd, double* dwipv, double* dwipstd);
 
+/* The JOINT posterior of the latent-plus-noise process at C query points Xq (C x d), 1 <= C <= 16384 - what scikit-learn's
+ * GaussianProcessRegressor.predict(return_cov=True) (plus noise I) and sample_y return; the reference has no counterpart.
+ * Standardised units.  Every work buffer (V: N x C, Sigma and its factor: C x C each) belongs to the call and is freed before
+ * it returns.  NOT gated: the classifier gate is not applied (like bobe_gp_fantasy_var).
+ *   cov[i][j] = k(q_i, q_j) + noise [i = j] - v_i . v_j,   v = L^-1 k(X, q)   (C x C, row-major, both triangles; the upper one is
+ *               the lower one bit for bit; not clipped).  The diagonal is predict_var_single (gp.py:459-466) before its clip;
+ *               v is formed as bobe_gp_predict forms it (the product with the inverse factor, or the blocked substitution
+ *               while the refine switch is active, bobe_gp_set_refine_kappa).
+ * Returns BOBE_ERR_STATE without a factorised state, BOBE_ERR_ARG for C out of range or a NULL pointer, BOBE_NOT_PD (cov is
+ * NaN) for a NaN state. */
+int bobe_gp_predict_cov(bobe_gp_t* gp, const double* Xq, int64_t C, double* cov);
+
+/* S correlated draws of that posterior at Xq (C x d), S >= 1:
+ *   draws[s] = m + L_S z_s   (S x C, row-major),   m = bobe_gp_predict's mean (centered != 0: m is left out),
+ *   L_S = chol(cov + tau mean(diag cov) I), tau the first of {0, 1e-12, 1e-10, 1e-8, 1e-6} that factorises under
+ *   bobe_gp_mll_from_k's test for a bare matrix (a pivot <= 0 or NaN fails); *jitter_out (may be NULL) = the jitter added,
+ *   tau mean(diag cov).  No tau works: BOBE_NOT_PD, draws NaN.
+ * z: S x C standard normals of the caller, or NULL: the device draws them from a counter hash of (seed, s, c) -
+ *   key = mix(seed ^ mix(s)), u1 = u01(mix(key + 2c)), u2 = u01(mix(key + 2c + 1)), z = sqrt(-2 log u1) cos(2 pi u2), with
+ *   mix the splitmix64 finaliser and u01(b) = ((b >> 11) + 0.5) / 2^53 of the HMC / NUTS / random-walk kernels (the exact
+ *   contract is above k_draw_normals in posterior_kernels.hpp).  The same seed gives the same draws, bit for bit.
+ * Errors as bobe_gp_predict_cov (S < 1 or a NULL draws: BOBE_ERR_ARG; a NaN state: BOBE_NOT_PD, draws NaN).  NOT gated. */
+int bobe_gp_posterior_sample(bobe_gp_t* gp, const double* Xq, int64_t C, int64_t S, uint64_t seed, const double* z,
+                             int centered, double* draws, double* jitter_out);
+
 /* EI.fun / LogEI.fun (acquisition.py:226-253, 318-330) for C points: out[c] = +EI (mode 0) or
  * +log EI (mode 1); best_y, zeta in standardised units. */
 int bobe_gp_acq_ei(bobe_gp_t* gp, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);
@@ -261,7 +286,8 @@ int bobe_gp_rwalk(bobe_gp_t* gp, int64_t P, double* X, double* logl, const doubl
  *   bobe_gp_hmc_leapfrog / bobe_gp_hmc_run   mean = minus_inf (physical units), no mean gradient: never accepted
  *   bobe_gp_nuts_run                         mean = minus_inf: a divergent leaf at the default minus_inf, never chosen
  *   bobe_gp_rwalk                            mean = minus_inf: never accepted
- * bobe_gp_wip_sweep, bobe_gp_fantasy_var and bobe_gp_wip_grad are NOT gated (fantasy_var is not, clf_gp.py:207-212).
+ * bobe_gp_wip_sweep, bobe_gp_fantasy_var and bobe_gp_wip_grad are NOT gated (fantasy_var is not, clf_gp.py:207-212), nor
+ * are bobe_gp_predict_cov and bobe_gp_posterior_sample.
  * One summation order serves every entry point (256 partial sums, a fixed tree), so a point near the boundary falls on
  * the same side everywhere.  The gate is not part of the state bobe_gp_clone_state copies. */
 int bobe_gp_set_gate(bobe_gp_t* gp, const double* support_vectors, int64_t n_sv, const double* dual_coef, double intercept,
