@@ -423,6 +423,8 @@ class BOBE:
             gp_fit(self.gp, n_restarts=n_restarts, maxiters=maxiter, rng=self.np_rng,
                    factorisable_start=self.factorisable_start)
             self.n_points_since_last_fit = 0
+            if getattr(self, "loo_diagnostics", False):
+                self._record_loo()
         self.timing["GP Training"] += time.time() - t0
         self.gp_hyperparam_history.append({"iteration": int(step), "lengthscales": [float(v) for v in self.gp.lengthscales],
                                            "kernel_variance": float(self.gp.kernel_variance)})
@@ -430,6 +432,18 @@ class BOBE:
             t0 = time.time()
             self.gp.train_classifier()
             self.timing["Classifier Training"] = self.timing.get("Classifier Training", 0.0) + time.time() - t0
+
+    def _record_loo(self) -> None:
+        """``run(loo_diagnostics=True)``: the leave-one-out summary of the surrogate just refitted (``GP.loo``, one pass over
+        the factor on the device) - one log line and one ``loo_history`` entry.  Draws nothing from the run's generator."""
+        r = self.gp.loo()
+        entry = {"n": int(self.gp.npoints), "elpd": float(r["elpd"]), "rmse": float(r["rmse"]),
+                 "max_abs_z": float(r["max_abs_z"]), "frac_within_1sigma": float(r["frac_within_1sigma"]),
+                 "frac_within_2sigma": float(r["frac_within_2sigma"])}
+        log.info(f"LOO-CV at N={entry['n']}: elpd={entry['elpd']:.4f} rmse={entry['rmse']:.4e} "
+                 f"max|z|={entry['max_abs_z']:.3f} within 1/2 sigma: {entry['frac_within_1sigma']:.3f}/"
+                 f"{entry['frac_within_2sigma']:.3f}")
+        self.loo_history.append(entry)
 
     def get_next_batch(self, acq_kwargs, n_batch, n_restarts, maxiter, early_stop_patience, step, verbose=True):
         """bo.py:681-705: the acquisition's kriging-believer batch + the mean acquisition value in the history."""
@@ -552,11 +566,14 @@ class BOBE:
             num_hmc_warmup: int = 512, num_hmc_samples: int = 512, mc_points_size: int = 64, thinning: int = 4,
             num_chains: int = 4, mc_points_method: str = "NUTS", zeta_ei: float = 0.01, *,
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
-            mc_sampler: str = "hmc") -> dict:
+            mc_sampler: str = "hmc", loo_diagnostics: bool = False) -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
-        'hmc' (default) or 'nuts' (``sample_GP_NUTS(sampler="nuts")``).  ``acq`` may be a tuple of stages, run one after the other on the
+        'hmc' (default) or 'nuts' (``sample_GP_NUTS(sampler="nuts")``), and ``loo_diagnostics`` - True: every refit of the
+        hyper-parameters logs the leave-one-out summary of the surrogate (``GP.loo``) and appends ``{n, elpd, rmse, max_abs_z,
+        frac_within_1sigma, frac_within_2sigma}`` to the ``loo_history`` list of the returned results (off: no such key, no
+        extra device call; either way nothing is drawn from the run's generator and the checkpoint files are unchanged).  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -582,6 +599,7 @@ class BOBE:
         if mc_sampler not in ("hmc", "nuts"):
             raise ValueError(f"mc_sampler must be 'hmc' or 'nuts', not {mc_sampler!r}")
         self.mc_sampler = mc_sampler
+        self.loo_diagnostics, self.loo_history = bool(loo_diagnostics), []
         self.converged, self.convergence_counter = False, 0
         self.min_delta_seen = np.inf
         self.termination_reason = "Max evaluation budget reached"          # bo.py:1118
@@ -649,6 +667,8 @@ class BOBE:
         log.info(f"Sampling stopped: {self.termination_reason}")
         log.info(f"Final GP training set size: {self.gp.train_x.shape[0]}, max size: {self.max_gp_size}")
         self.finalise_results()
+        if self.loo_diagnostics:
+            self.results_dict["loo_history"] = list(self.loo_history)
         self.start_iteration = self.current_iteration            # (a further run() on this object counts on)
         return self.results_dict
 

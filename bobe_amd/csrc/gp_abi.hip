@@ -212,6 +212,24 @@ int bobe_gp_mll(bobe_gp_t* g, const double* ls, double kvar, double* mll, double
   API_END
 }
 
+int bobe_gp_loo(bobe_gp_t* g, double* mean, double* var, double* lpd, double* sum_lpd) {
+  API_BEGIN
+  NEED(g, "gp is NULL");
+  return g->loo_state(mean, var, lpd, sum_lpd);
+  API_END
+}
+
+int bobe_gp_loo_objective(bobe_gp_t* g, const double* ls, double kvar, double* loo, double* grad) {
+  API_BEGIN
+  NEED(g && ls && loo, "NULL argument");
+  if (!g->have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  Hyper h = g->hyp;
+  for (int j = 0; j < g->d; ++j) h.ls[j] = ls[j];
+  h.kvar = kvar;
+  return g->loo_objective(h, loo, grad);
+  API_END
+}
+
 int bobe_gp_mll_batch(bobe_gp_t* g, int64_t B, const double* ls, const double* kvar, double* mll, double* grad,
                       int* status) {
   API_BEGIN

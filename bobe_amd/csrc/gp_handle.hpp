@@ -5,6 +5,7 @@
 //   gp_sweep.hip      prediction / acquisition sweep, score and posterior gradients, rank-b append
 //   gp_consumers.hip  HMC on the surrogate, EI / LogEI, the classifier gate, GP.kernel, device clone
 //   gp_posterior.hip  joint posterior covariance at query points and correlated draws from it
+//   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
 // without a HIP device every entry point fails with BOBE_ERR_HIP.
@@ -147,6 +148,7 @@ void configure_factor_kernels();
 void configure_sweep_kernels();
 void configure_consumer_kernels();
 void configure_posterior_kernels();
+void configure_loo_kernels();
 
 struct Depth { int first, count, nblocks; };
 
@@ -385,6 +387,7 @@ struct bobe_gp {
     bobe::configure_sweep_kernels();
     bobe::configure_consumer_kernels();
     bobe::configure_posterior_kernels();
+    bobe::configure_loo_kernels();
   }
   void sync() { HIPCHK(hipStreamSynchronize(stream)); }
 
@@ -475,6 +478,12 @@ struct bobe_gp {
   int predict_cov(const double* Xq, int64_t C, double* cov);
   int posterior_sample(const double* Xq, int64_t C, int64_t S, uint64_t seed, const double* z, int centered, double* draws,
                        double* jitter_out);
+
+  // ---- gp_loo.hip (loo_ws: seven vectors of Np - diag K^-1, mean, var, lpd, sqrt c, b / sqrt c, w)
+  DBuf loo_ws;
+  void loo_terms(const double* linv, const double* al, bool with_grad_terms, double* sum_out);
+  int loo_state(double* mean, double* var, double* lpd, double* sum_lpd);
+  int loo_objective(const Hyper& h, double* loo, double* grad);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

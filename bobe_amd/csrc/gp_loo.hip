@@ -1,0 +1,145 @@
+// libbobe_gp.so, leave-one-out unit: the LOO predictive terms of the factorised state (bobe_gp_loo) and the LOO log
+// pseudo-likelihood with its gradient at a hyper-parameter vector (bobe_gp_loo_objective).  Kernels: loo_kernels.hpp; the
+// factorisation, the triangular inverse and K^-1 are gp_factor.hip's (factor_into, lauum).
+#include "gp_handle.hpp"
+
+#include "loo_kernels.hpp"
+
+using namespace bobe;
+
+namespace bobe {
+
+void configure_loo_kernels() {
+  static bool done[64] = {false};
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || done[dev]) return;
+  allow_big_lds(k_loo_grad<0, 8, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 16, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 32, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 8, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 16, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 32, 64>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 8, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 16, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 32, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 8, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 16, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 32, 64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 8, 128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 16, 128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<0, 32, 128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 8, 128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 16, 128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_loo_grad<1, 32, 128>, GEMM_SMEM_BYTES);
+  done[dev] = true;
+}
+
+}  // namespace bobe
+
+// a = diag(K^-1) from the inverse factor `linv`, then mean / var / lpd (and sqrt c, b / sqrt c when `with_grad_terms`) into
+// loo_ws, and sum lpd into sum_out (device).  loo_ws: seven vectors of Np - a, mean, var, lpd, sqrt c, b / sqrt c, w.
+void bobe_gp::loo_terms(const double* linv, const double* al, bool with_grad_terms, double* sum_out) {
+  loo_ws.ensure((size_t)7 * Np * sizeof(double));
+  double* ws = loo_ws.d();
+  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb), dim3(256), 0, stream, linv, Np, part.d(), Np);
+  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), 1u), dim3(256), 0, stream, (const double*)part.d(), Np,
+                     nb, 1, Np, ws, (int64_t)0, (int64_t)0);
+  hipLaunchKernelGGL(k_loo_point, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, stream, (const double*)ws, al,
+                     (const double*)y.d(), N, Np, ws + Np, ws + 2 * Np, ws + 3 * Np, with_grad_terms ? ws + 4 * Np : nullptr,
+                     with_grad_terms ? ws + 5 * Np : nullptr);
+  hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, stream, (const double*)(ws + 3 * Np), N, sum_out);
+  LAUNCH_CHECK();
+}
+
+// bobe_gp_loo: the factorised state's Linv and alpha, whatever installed them (factorisation, append, clone, set_chol)
+int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  use();
+  loo_terms(Linv.d(), alpha.d(), false, res.d() + 102);
+  const double* ws = loo_ws.d();
+  double* outs[3] = {mean, var, lpd};
+  for (int q = 0; q < 3; ++q)
+    if (outs[q])
+      HIPCHK(hipMemcpyAsync(outs[q], ws + (q + 1) * Np, (size_t)N * sizeof(double),
+                            is_device_ptr(outs[q]) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  if (sum_lpd)
+    HIPCHK(hipMemcpyAsync(sum_lpd, res.d() + 102, sizeof(double),
+                          is_device_ptr(sum_lpd) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  sync();
+  if (not_pd) {                        // (the NaN state gave NaN outputs)
+    g_err = "the factorised state is not positive definite";
+    return BOBE_NOT_PD;
+  }
+  return BOBE_OK;
+}
+
+// bobe_gp_loo_objective: bobe_gp_mll's pipeline on the evaluation workspace up to Linv2 / alpha2, then
+//   value     a, the per-point terms, the fixed-order sum                                    (loo_terms)
+//   gradient  K^-1 stored by the existing lauum into Tmp, B = diag(sqrt c) K^-1 into A2 (the factor L is no longer
+//             needed), w = B^T (b / sqrt c), the dense B^T B tiles with the gradient epilogue, k_mll_grad_reduce.
+// The workspace ends up holding no factor (A2 is overwritten): its record is cleared, bobe_gp_factor will not adopt it.
+int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
+  use();
+  tag2.clear();
+  const double floor_h = pivot_floor(h);
+  factor_into(h, XsT2.d(), A2.d(), Linv2.d(), w2.d(), alpha2.d());
+  // the info word and the smallest pivot's root (res[100], res[101]), while A2 still holds L
+  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w2.d(), (const double*)A2.d(), Np, Np, res.d(),
+                     (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
+  loo_terms(Linv2.d(), alpha2.d(), grad != nullptr, res.d() + 102);
+  if (grad) {
+    double* ws = loo_ws.d();
+    const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
+    (void)lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), Tmp.d(), dcap);      // K^-1's lower tiles -> Tmp (its partial sums go unused)
+    const int nt32 = (int)(Np / 32);
+    hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2)), dim3(256), 0, stream, (const double*)Tmp.d(), Np,
+                       (const double*)(ws + 4 * Np), A2.d());
+    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Np / 64), (unsigned)nb, 1u), dim3(256), 0, stream, (const double*)A2.d(), Np,
+                       0, (const double*)(ws + 5 * Np), part.d(), Np, (int64_t)0, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), 1u), dim3(256), 0, stream, (const double*)part.d(), Np,
+                       nb, 0, Np, ws + 6 * Np, (int64_t)0, (int64_t)0);
+    // (the tile size fixes the order of the partial sums: a function of N only, lauum's rule)
+    const bool small = nb * (nb + 1) / 2 < LAUUM64_BELOW;
+    const int nt = small ? 2 * nb : nb;
+    const int ntiles = nt * (nt + 1) / 2;
+    const bool g64 = tuning().gemm64_glds;
+    prof_begin(BOBE_PROF_LAUUM);
+#define LG(KE, DC, TT)                                                                                                     \
+  hipLaunchKernelGGL((g64 ? k_loo_grad<KE, DC, TT, TT == 64> : k_loo_grad<KE, DC, TT, false>), dim3(ntiles), dim3(256),     \
+                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)A2.d(), Np, Np, N,           \
+                     (const double*)alpha2.d(), (const double*)(ws + 6 * Np), (const double*)XsT2.d(), Np, h, gpart.d())
+#define LGD(KE, TT)                                                                         \
+  do {                                                                                      \
+    if (dcap == 8) LG(KE, 8, TT); else if (dcap == 16) LG(KE, 16, TT); else LG(KE, 32, TT); \
+  } while (0)
+    if (h.kern == 0) {
+      if (small) LGD(0, 64); else LGD(0, 128);
+    } else {
+      if (small) LGD(1, 64); else LGD(1, 128);
+    }
+#undef LGD
+#undef LG
+    prof_end(BOBE_PROF_LAUUM);
+    // (d + 1 workgroups: the gradient components; the scalar terms were reduced above)
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1), dim3(256), 0, stream, (const double*)gpart.d(), ntiles, dcap + 1, d, dcap,
+                       res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np, (const int*)nullptr, (int64_t)0,
+                       (int64_t)0, (int64_t)0, (int64_t)0);
+    LAUNCH_CHECK();
+  }
+  HIPCHK(hipMemcpyAsync(h_res, res.p, 103 * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
+  int inf;
+  std::memcpy(&inf, h_res + 100, sizeof(int));
+  if (inf != 0x7f7f7f7f || !pivots_resolved(h_res[101], floor_h)) {
+    *loo = std::nan("");
+    if (grad)
+      for (int j = 0; j <= d; ++j) grad[j] = std::nan("");
+    g_err = not_pd_text(inf, h_res[101]);
+    return BOBE_NOT_PD;
+  }
+  *loo = h_res[102];
+  if (grad)
+    for (int j = 0; j <= d; ++j) grad[j] = h_res[2 + j];
+  return BOBE_OK;
+}

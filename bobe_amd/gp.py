@@ -163,11 +163,12 @@ class GP:
                  kernel_variance_bounds=[1e-4, 1e8], lengthscale_bounds=[0.01, 5], lengthscales=None,
                  kernel_variance=None, kernel_variance_prior=None, lengthscale_prior=None, tausq=None,
                  tausq_bounds=[1e-4, 1e4], param_names: Optional[List[str]] = None, device: int = 0,
-                 pivot_floor_ulp: Optional[float] = None, _factor: bool = True):
+                 pivot_floor_ulp: Optional[float] = None, _factor: bool = True, fit_objective: str = "mll"):
         """Same keywords as BOBE/gp.py:201-203 plus ``device`` (HIP device index) and ``pivot_floor_ulp`` (None: the
         library's default, 0 = the reference's rule - a factorisation fails only on a pivot <= 0, gp.py:175, 549; 64 is
         what ``BOBE(...)`` passes, see the property).  ``_factor=False`` (internal) leaves the factorisation to the caller,
-        which is about to install a known one (``from_state_dict``, ``copy``)."""
+        which is about to install a known one (``from_state_dict``, ``copy``).  ``fit_objective``: what ``fit`` minimises,
+        'mll' (the reference's -(MLL + log prior)) or 'loo' (see the ``fit_objective`` property)."""
         self._lib = _lib.load()
         self._h = C.c_void_p(0)
         self.device = int(device)
@@ -193,6 +194,7 @@ class GP:
         # way; "auto" = lock step where SciPy's routine can be stepped (optim._rc_available), else slots: measured
         # 33.7 vs 53.5 ms at N = 100, 39.5 vs 45.7 at 600, 124 vs 141 at 2048, 457 vs 461 at 4096 for a 4-restart fit
         self.restart_mode = "auto"
+        self.fit_objective = fit_objective
 
         self.lengthscale_bounds = lengthscale_bounds
         self.kernel_variance_bounds = kernel_variance_bounds
@@ -401,12 +403,77 @@ class GP:
             grad[idx] = g_tau * tausq
         return val, -grad
 
+    # ------------------------------------------------------------------ leave-one-out cross-validation
+    @property
+    def fit_objective(self) -> str:
+        """What ``fit`` minimises: 'mll' (default) = -(MLL + log prior), the reference's objective, or 'loo' = -(L_LOO + log
+        prior) with L_LOO the leave-one-out log pseudo-likelihood (``neg_loo_value_and_grad``), which is more robust to a
+        mis-specified kernel.  With 'loo' the restarts run one after another through the same ``mll_optimize`` driver (no
+        batch or slot form of the LOO objective exists), and the ``'mll'`` key of ``fit``'s result - callers read it -
+        holds ``-best_loss`` of the LOO objective, i.e. L_LOO + log prior at the optimum, not a marginal likelihood."""
+        return self._fit_objective
+
+    @fit_objective.setter
+    def fit_objective(self, value: str) -> None:
+        if value not in ("mll", "loo"):
+            raise ValueError(f"fit_objective must be 'mll' or 'loo', not {value!r}")
+        self._fit_objective = value
+
+    def loo(self) -> dict:
+        """Leave-one-out cross-validation of the fitted surrogate at its training points (Rasmussen & Williams 5.4.2), from
+        the factor on the device (``bobe_gp_loo``: one pass over the stored inverse factor, no refit, no refactorisation -
+        also on a GP made by ``copy`` / ``from_state_dict`` or grown by ``update``).  Hyper-parameters, noise and the
+        y-standardisation are held fixed while a point is left out.  Physical units:
+        ``mean`` (N) mu_-i y_std + y_mean; ``var`` (N) sigma^2_-i y_std^2 (noise included); ``z`` (N) the standardised
+        residual (y_i - mu_-i) / sigma_-i; ``lpd`` (N) log predictive density of y_i (the standardised one minus log y_std);
+        ``elpd`` their sum; and the summaries ``rmse`` (of y_i - mu_-i), ``max_abs_z``, ``frac_within_1sigma``,
+        ``frac_within_2sigma``.  A ``GPwithClassifier`` reports on its thresholded GP subset; the gate is not applied.
+        A NaN state gives NaN."""
+        n = self.npoints
+        mean, var, lpd = np.empty(n), np.empty(n), np.empty(n)
+        s = C.c_double(0.0)
+        _lib.check(self._lib.bobe_gp_loo(self._h, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(lpd), C.byref(s)), "bobe_gp_loo")
+        y = np.asarray(self.train_y, dtype=np.float64).reshape(-1)
+        resid = y - mean                                             # standardised
+        z = resid / np.sqrt(var)
+        log_ystd = math.log(self.y_std)
+        az = np.abs(z)
+        return {"mean": mean * self.y_std + self.y_mean, "var": var * self.y_std ** 2, "z": z, "lpd": lpd - log_ystd,
+                "elpd": float(s.value) - n * log_ystd, "rmse": float(np.sqrt(np.mean(resid ** 2)) * self.y_std),
+                "max_abs_z": float(np.max(az)), "frac_within_1sigma": float(np.mean(az <= 1.0)),
+                "frac_within_2sigma": float(np.mean(az <= 2.0))}
+
+    def loo_data(self, lengthscales, kernel_variance, want_grad=True):
+        """Data term of the LOO objective: L_LOO = sum_i lpd_i (standardised units) at the given hyper-parameters and its
+        gradient wrt (log ls, log kvar) on the GPU (``bobe_gp_loo_objective``) - the counterpart of ``mll_data``.  Does not
+        disturb the factorised state.  Not positive definite: NaN."""
+        ls = _lib.as_f64(lengthscales).reshape(-1)
+        val = C.c_double(0.0)
+        grad = np.empty(self.ndim + 1) if want_grad else None
+        _lib.check(self._lib.bobe_gp_loo_objective(self._h, _lib.ptr(ls), float(kernel_variance), C.byref(val),
+                                                   _lib.ptr(grad)), "bobe_gp_loo_objective")
+        return val.value, grad
+
+    def neg_loo_value_and_grad(self, log_params, want_grad=True):
+        """(f, df/dtheta) with f = -(L_LOO + log prior), theta = log hp: ``neg_mll_value_and_grad`` with the LOO log
+        pseudo-likelihood in the place of the marginal likelihood (priors, a fixed kernel variance and tausq handled by the
+        same ``_assemble_objective``)."""
+        log_params = np.asarray(log_params, dtype=np.float64)
+        ls, kvar, tausq = self._parse_hyperparams(log_params)
+        val, g_data = self.loo_data(ls, kvar, want_grad)
+        return self._assemble_objective(log_params, ls, kvar, tausq, val, g_data, want_grad)
+
     def fit(self, x0: np.ndarray = None, maxiter: int = 500) -> dict:
-        """BOBE/gp.py:400-437."""
+        """BOBE/gp.py:400-437.  With ``fit_objective='loo'`` the returned ``'mll'`` is L_LOO + log prior at the optimum."""
         if x0 is None:
             x0 = np.log(self.get_hyperparams())[None, :]
         x0 = np.atleast_2d(np.asarray(x0, dtype=np.float64))
         optimizer_options = dict(self.optimizer_options)
+        if self.fit_objective == "loo":
+            best_params_log, best_loss = self.mll_optimize(
+                self.neg_loo_value_and_grad, num_params=self.num_hyperparams, bounds=self.hyperparam_bounds, x0=x0,
+                maxiter=maxiter, n_restarts=x0.shape[0], optimizer_options=optimizer_options)
+            return {"mll": -best_loss, "params": best_params_log}
         # restarts are independent L-BFGS-B runs: each gets a host thread and an evaluation slot of the library
         extra = {}
         if self.concurrent_restarts and x0.shape[0] > 1 and self.mll_optimize is optimize_scipy:

@@ -100,6 +100,28 @@ int bobe_gp_mll_batch(bobe_gp_t* gp, int64_t B, const double* lengthscales, cons
 int bobe_gp_mll_submit(bobe_gp_t* gp, int slot, const double* lengthscales, double kernel_variance, int want_grad);
 int bobe_gp_mll_wait(bobe_gp_t* gp, int slot, double* mll, double* grad);
 
+/* Leave-one-out cross-validation of the factorised state (Rasmussen & Williams, section 5.4.2; the reference has no
+ * counterpart): what the surrogate predicts at training point i when that point is left out, with the hyper-parameters, the
+ * noise and the y-standardisation held fixed.  Standardised units.  With A = K^-1 (noise included), a_i = A_ii, alpha = A y:
+ *   mean[i] = y_i - alpha_i / a_i,   var[i] = 1 / a_i (noise included, no floor: a_i > 0 whenever the factor exists),
+ *   lpd[i]  = 1/2 log a_i - alpha_i^2 / (2 a_i) - 1/2 log 2 pi,   *sum_lpd = sum_i lpd[i] (fixed order).
+ * a_i = sum_{k >= i} (L^-1)_ki^2, the column sums of squares of the stored inverse factor: one pass over its lower triangle,
+ * no product.  Reads the state as it is - after bobe_gp_factor, bobe_gp_append, bobe_gp_clone_state or bobe_gp_set_chol - and
+ * returns the same bits for the same state.  mean / var / lpd: N (host or device memory), sum_lpd: one double (host or
+ * device); any of them may be NULL.  NOT gated by the classifier (the outputs are about training points).
+ * BOBE_ERR_STATE without a factorised state; BOBE_NOT_PD (outputs NaN) for a NaN state. */
+int bobe_gp_loo(bobe_gp_t* gp, double* mean, double* var, double* lpd, double* sum_lpd);
+
+/* The LOO log pseudo-likelihood L_LOO = sum_i lpd[i] at the given hyper-parameters (noise from set_hyper) and its gradient:
+ * the counterpart of bobe_gp_mll for a fit that maximises L_LOO instead of the marginal likelihood.  *loo (host) = L_LOO;
+ * grad (host, may be NULL: the value alone, same bits) has d+1 entries: d L_LOO / d log ls_j (j < d), d L_LOO / d log
+ * kernel_variance,
+ *   dL_LOO / dtheta_j = sum_ab M_ab dK_ab / dtheta_j,   M = -A diag(c) A - 1/2 (w alpha^T + alpha w^T),
+ *   c_i = 1 / (2 a_i) + alpha_i^2 / (2 a_i^2),   b_i = -alpha_i / a_i,   w = A b.
+ * Runs on the evaluation workspace: does not disturb the state left by bobe_gp_factor.  One evaluation at a time (no slot,
+ * batch or lock-step form).  BOBE_NOT_PD (the rank test of bobe_gp_set_pivot_floor_ulp included) -> *loo and grad are NaN. */
+int bobe_gp_loo_objective(bobe_gp_t* gp, const double* lengthscales, double kernel_variance, double* loo, double* grad);
+
 /* GP.predict_mean_batched / predict_var_batched / predict_batched (gp.py:450-493) for C query points
  * Xq (C x d).  mean[c] = k_c^T alpha; var[c] = kvar + noise - |L^-1 k_c|^2 with
  *   nan_policy 0: clip(var, 1e-12) keeps NaN (predict_var_single, gp.py:465)
