@@ -183,6 +183,31 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
         vals, idx = self.sweep(gp, candidates, mc_points)
         return float(vals[idx]), int(idx)
 
+    def get_next_batch(self, gp: GP, n_batch: int = 1, acq_kwargs=None, maxiter: int = 500, n_restarts: int = 8,
+                       verbose: bool = True, early_stop_patience: int = 25, rng=None, *, batch_mode: str = "believer"):
+        """``batch_mode='believer'`` (default): the inherited kriging-believer loop, unchanged - ``n_batch`` sweeps of the
+        integration points, each on a surrogate that gained the previous pick.
+
+        ``batch_mode='sweep'``: the same believer batch out of ONE sweep (``GP.wip_select_batch``).  One set of integration
+        points is drawn (one ``get_mc_points`` call, where the loop draws one per member); the candidates are
+        ``acq_kwargs['candidates']`` or, without that key, all of ``mc_samples['x']``; the picks are rows of that pool (no
+        L-BFGS polish, whatever the size of the design).  Returns ``(x_batch (n_batch, d), acq_vals (n_batch,))`` like the
+        loop, the values in the caller's units (``y_std`` held fixed over the batch)."""
+        if batch_mode == "believer":
+            return super().get_next_batch(gp, n_batch=n_batch, acq_kwargs=acq_kwargs, maxiter=maxiter,
+                                          n_restarts=n_restarts, verbose=verbose,
+                                          early_stop_patience=early_stop_patience, rng=rng)
+        if batch_mode != "sweep":
+            raise ValueError(f"batch_mode must be 'believer' or 'sweep', not {batch_mode!r}")
+        acq_kwargs = acq_kwargs if acq_kwargs is not None else {}
+        mc_samples = acq_kwargs.get("mc_samples")
+        mc_points = get_mc_points(mc_samples, mc_points_size=acq_kwargs.get("mc_points_size", 128), rng=rng)
+        candidates = acq_kwargs.get("candidates")
+        if candidates is None:
+            candidates = mc_samples["x"]
+        r = gp.wip_select_batch(candidates, mc_points, n_batch, criterion=self._key)
+        return np.array(r["points"]), np.array(r["scores"])
+
     def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 100, n_restarts: int = 1, verbose: bool = True,
                        early_stop_patience: int = 25, rng=None):
         acq_kwargs = acq_kwargs if acq_kwargs is not None else {}

@@ -28,7 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 from scipy.stats import qmc
 
-from .acquisition import EI, LogEI, WIPStd, WIPV, get_mc_samples
+from .acquisition import EI, LogEI, WeightedIntegratedPosteriorBase, WIPStd, WIPV, get_mc_samples
 from .dist_sweep import dist_info, merge_best_fit, shard_bounds
 from .gp import GP
 from .likelihood import Likelihood
@@ -207,6 +207,7 @@ class BOBE:
         self.num_hmc_warmup, self.num_hmc_samples, self.mc_points_size = 512, 512, 64
         self.hmc_thinning, self.hmc_num_chains, self.mc_points_method, self.zeta_ei = 4, 4, "NUTS", 0.01
         self.num_mc_samples, self.acq_threshold, self.verbose, self.mc_sampler = 1024, None, False, "hmc"
+        self.wip_batch_mode = "believer"
         self.min_delta_seen = np.inf
         self.current_iteration = 0
         self.start_iteration = 0
@@ -448,9 +449,15 @@ class BOBE:
     def get_next_batch(self, acq_kwargs, n_batch, n_restarts, maxiter, early_stop_patience, step, verbose=True):
         """bo.py:681-705: the acquisition's kriging-believer batch + the mean acquisition value in the history."""
         t0 = time.time()
+        # (``wip_batch_mode='sweep'``: WIPV / WIPStd take their batch from one sweep; every other case is the inherited call)
+        extra = {}
+        if self.wip_batch_mode == "sweep" and \
+                isinstance(self.acquisition, WeightedIntegratedPosteriorBase):
+            extra["batch_mode"] = "sweep"
         new_pts_u, acq_vals = self.acquisition.get_next_batch(gp=self.gp, n_batch=n_batch, acq_kwargs=acq_kwargs,
                                                               n_restarts=n_restarts, maxiter=maxiter,
-                                                              early_stop_patience=early_stop_patience, rng=self.np_rng)
+                                                              early_stop_patience=early_stop_patience, rng=self.np_rng,
+                                                              **extra)
         self.timing["Acquisition Optimization"] += time.time() - t0
         acq_val = float(np.mean(acq_vals))
         if verbose:
@@ -566,14 +573,18 @@ class BOBE:
             num_hmc_warmup: int = 512, num_hmc_samples: int = 512, mc_points_size: int = 64, thinning: int = 4,
             num_chains: int = 4, mc_points_method: str = "NUTS", zeta_ei: float = 0.01, *,
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
-            mc_sampler: str = "hmc", loo_diagnostics: bool = False) -> dict:
+            mc_sampler: str = "hmc", loo_diagnostics: bool = False, wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
         'hmc' (default) or 'nuts' (``sample_GP_NUTS(sampler="nuts")``), and ``loo_diagnostics`` - True: every refit of the
         hyper-parameters logs the leave-one-out summary of the surrogate (``GP.loo``) and appends ``{n, elpd, rmse, max_abs_z,
         frac_within_1sigma, frac_within_2sigma}`` to the ``loo_history`` list of the returned results (off: no such key, no
-        extra device call; either way nothing is drawn from the run's generator and the checkpoint files are unchanged).  ``acq`` may be a tuple of stages, run one after the other on the
+        extra device call; either way nothing is drawn from the run's generator and the checkpoint files are unchanged), and
+        ``wip_batch_mode`` - how a WIPV / WIPStd batch is made: 'believer' (default: the reference's loop, one sweep of the
+        integration points per member) or 'sweep' (``get_next_batch(batch_mode="sweep")``: one sweep of ALL integration
+        samples as the candidate pool and rank-one downdates on the device, ``GP.wip_select_batch``; the default mode leaves
+        the run's generator and the checkpoint files as they were).  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -599,6 +610,9 @@ class BOBE:
         if mc_sampler not in ("hmc", "nuts"):
             raise ValueError(f"mc_sampler must be 'hmc' or 'nuts', not {mc_sampler!r}")
         self.mc_sampler = mc_sampler
+        if wip_batch_mode not in ("believer", "sweep"):
+            raise ValueError(f"wip_batch_mode must be 'believer' or 'sweep', not {wip_batch_mode!r}")
+        self.wip_batch_mode = wip_batch_mode
         self.loo_diagnostics, self.loo_history = bool(loo_diagnostics), []
         self.converged, self.convergence_counter = False, 0
         self.min_delta_seen = np.inf

@@ -278,6 +278,14 @@ int bobe_gp_wip_sweep(bobe_gp_t* g, const double* cand, int64_t C, const double*
   API_END
 }
 
+int bobe_gp_wip_select_batch(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                             int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  return g->wip_select_batch(cand, C, Z, M, y_std, n_batch, criterion, picks, pick_scores, stage_scores);
+  API_END
+}
+
 int bobe_gp_fantasy_var(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                         double* out) {
   API_BEGIN

@@ -1,0 +1,113 @@
+// libbobe_gp.so, batch unit: one-sweep batch selection for WIPV / WIPStd (bobe_gp_wip_select_batch).  Kernels:
+// batch_kernels.hpp (the downdates), kernels_common.hpp (k_gemv_t_part); stage 0 and every scoring launch are bobe_gp::sweep's
+// and bobe_gp::wip_score's own (gp_sweep.hip).
+// Every buffer of the call (the retained V, crossT, s_c, base_z copy, u rows, scores) belongs to the call and is freed before
+// it returns.  The handle's Z-side state (ZsT, V_Z, base_z) is read, never written: a later bobe_gp_wip_sweep sees what it
+// would have seen without the call.
+#include "gp_handle.hpp"
+
+#include "batch_kernels.hpp"
+
+using namespace bobe;
+
+namespace {
+// Cap of the call's buffers that grow with the candidate count: 16 GiB = 2^31 doubles.  Counted are V, crossT, the scaled
+// candidates and s_c, (Np + Mp + d + 1) x Cp, the row-block partial sums and the u rows of the later stages, (Np / 128 +
+// n_batch - 1) x Cp, and the staging rows of scores that go to host memory, (n_batch or 1) x C.  N = 4096, d = 8 with 512
+// integration points and the largest batch (64, all stage scores to the host: 4776 doubles per candidate) admits 449 536
+// candidates; a larger pool is the caller's to split (BOBE_ERR_ARG).
+constexpr size_t BATCH_KEEP_BYTES = size_t(16) << 30;
+}  // namespace
+
+int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch,
+                              int criterion, int64_t* picks, double* pick_scores, double* stage_scores) {
+  if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
+  if (n_batch < 1 || n_batch > BATCH_MAX || n_batch > C) throw Err(BOBE_ERR_ARG, "n_batch must be in [1, min(C, 64)]");
+  if (criterion != 0 && criterion != 1) throw Err(BOBE_ERR_ARG, "criterion must be 0 (WIPV) or 1 (WIPStd)");
+  if (!picks) throw Err(BOBE_ERR_ARG, "picks is NULL");
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  const int64_t Cp = round_up(C, TILE), Mp = round_up(M, TILE);
+  const int nu = n_batch - 1;                            // u rows kept
+  const bool dev_scores = stage_scores && is_device_ptr(stage_scores);
+  const size_t n_stage_rows = dev_scores ? 0 : (stage_scores ? (size_t)n_batch : 1);
+  const size_t per_col = (size_t)(Np + Mp + d + 1) + (nu > 0 ? (size_t)(nb + nu) : 0);
+  if ((per_col * (size_t)Cp + n_stage_rows * (size_t)C) * sizeof(double) > BATCH_KEEP_BYTES)
+    throw Err(BOBE_ERR_ARG, "too many candidates: the call's buffers, (Np + Mp + d + 1 + Np / 128 + n_batch - 1) x Cp + staged "
+                            "score rows x C doubles, exceed 16 GiB");
+  use();
+  const bool wipv = criterion == 0;
+  CallBuf cst, vkeep, xT, scb, bz, scores, vstar, pin, partc, partz, uc, uz, dpick, dval;
+  cst.ensure((size_t)d * Cp * sizeof(double));
+  vkeep.ensure((size_t)Np * Cp * sizeof(double));
+  xT.ensure((size_t)Mp * Cp * sizeof(double));
+  scb.ensure((size_t)Cp * sizeof(double));
+  dpick.ensure((size_t)n_batch * sizeof(int64_t));
+  dval.ensure((size_t)n_batch * sizeof(double));
+  // the scores of stage j: the caller's row j when stage_scores is device memory, else a row of a staging buffer (one
+  // row, overwritten per stage, when the caller wants none)
+  if (!dev_scores) scores.ensure(n_stage_rows * (size_t)C * sizeof(double));
+  auto stage_row = [&](int j) -> double* {
+    if (dev_scores) return stage_scores + (int64_t)j * C;
+    return scores.d() + (stage_scores ? (int64_t)j * C : 0);
+  };
+  int64_t* d_picks = static_cast<int64_t*>(dpick.p);
+
+  // ---- stage 0: the sweep itself, writing into the retained buffers
+  SweepKeep keep;
+  keep.CsT = cst.d();
+  keep.V = vkeep.d();
+  keep.crossT = xT.d();
+  keep.sc = scb.d();
+  keep.ld = Cp;
+  int64_t pick0 = -1;
+  double val0 = 0.0;
+  sweep(cand, C, Z, M, y_std, wipv ? stage_row(0) : nullptr, wipv ? nullptr : stage_row(0), nullptr, nullptr, 1,
+        wipv ? &pick0 : nullptr, wipv ? &val0 : nullptr, wipv ? nullptr : &pick0, wipv ? nullptr : &val0, nullptr, false,
+        &keep);                                          // (synchronises: pick0 / val0 are on the host)
+  HIPCHK(hipMemcpyAsync(d_picks, &pick0, sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(dval.p, &val0, sizeof(double), hipMemcpyHostToDevice, stream));
+
+  // ---- stages 1 .. n_batch - 1: rank-one downdates of crossT, base_z, s_c and a rescoring, queued without a host round trip
+  if (nu > 0) {
+    bz.ensure((size_t)Mp * sizeof(double));
+    vstar.ensure((size_t)Np * sizeof(double));
+    pin.ensure((size_t)BATCH_PIN * sizeof(double));
+    partc.ensure((size_t)nb * Cp * sizeof(double));
+    partz.ensure((size_t)nb * Mp * sizeof(double));
+    uc.ensure((size_t)nu * Cp * sizeof(double));
+    uz.ensure((size_t)nu * Mp * sizeof(double));
+    HIPCHK(hipMemcpyAsync(bz.p, basez.p, (size_t)Mp * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  }
+  for (int j = 1; j < n_batch; ++j) {
+    const int nprev = j - 1;
+    double* ucj = uc.d() + (int64_t)nprev * Cp;
+    double* uzj = uz.d() + (int64_t)nprev * Mp;
+    hipLaunchKernelGGL(k_batch_gather, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, stream, keep.V_used, keep.ldv_used,
+                       Np, (const double*)cst.d(), Cp, d, (const double*)scb.d(), (const double*)uc.d(), Cp, nprev,
+                       (const int64_t*)(d_picks + nprev), vstar.d(), pin.d());
+    // V_C^T v* and V_Z^T v*: partial sums per row block of 128, added up in k_batch_u
+    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Cp / 64), (unsigned)nb), dim3(256), 0, stream, keep.V_used,
+                       keep.ldv_used, 0, (const double*)vstar.d(), partc.d(), Cp, (int64_t)0, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Mp / 64), (unsigned)nb), dim3(256), 0, stream, (const double*)VZ.d(), Mp,
+                       0, (const double*)vstar.d(), partz.d(), Mp, (int64_t)0, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL(k_batch_u, dim3((unsigned)((Cp + 255) / 256)), dim3(256), 0, stream, (const double*)partc.d(), Cp, nb,
+                       (const double*)cst.d(), Cp, C, Cp, hyp, (const double*)pin.d(), (const double*)uc.d(), Cp, nprev, ucj,
+                       scb.d());
+    hipLaunchKernelGGL(k_batch_u, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream, (const double*)partz.d(), Mp, nb,
+                       (const double*)ZsT.d(), Mp, M, Mp, hyp, (const double*)pin.d(), (const double*)uz.d(), Mp, nprev, uzj,
+                       bz.d());
+    hipLaunchKernelGGL(k_batch_rank1, dim3((unsigned)((Cp + 255) / 256), (unsigned)(Mp / 16)), dim3(256), 0, stream, xT.d(), Cp, Cp,
+                       (const double*)uzj, (const double*)ucj);
+    double* row = stage_row(j);
+    wip_score(xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, wipv ? row : nullptr, wipv ? nullptr : row, nullptr);
+    hipLaunchKernelGGL(k_argmin_masked, dim3(1), dim3(1024), 0, stream, (const double*)row, C, d_picks, j,
+                       static_cast<double*>(dval.p) + j);
+    LAUNCH_CHECK();
+  }
+  HIPCHK(hipMemcpyAsync(picks, dpick.p, (size_t)n_batch * sizeof(int64_t), hipMemcpyDefault, stream));
+  if (pick_scores) HIPCHK(hipMemcpyAsync(pick_scores, dval.p, (size_t)n_batch * sizeof(double), hipMemcpyDefault, stream));
+  if (stage_scores && !dev_scores)
+    HIPCHK(hipMemcpyAsync(stage_scores, scores.p, (size_t)n_batch * C * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
+  return BOBE_OK;
+}

@@ -6,6 +6,7 @@
 //   gp_consumers.hip  HMC on the surrogate, EI / LogEI, the classifier gate, GP.kernel, device clone
 //   gp_posterior.hip  joint posterior covariance at query points and correlated draws from it
 //   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
+//   gp_batch.hip      one-sweep batch selection for WIPV / WIPStd (the sweep's intermediates kept, rank-one downdates)
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
 // without a HIP device every entry point fails with BOBE_ERR_HIP.
@@ -81,6 +82,14 @@ struct DBuf {
   double* d() const { return static_cast<double*>(p); }
 };
 
+// a device buffer of one call: freed when the call returns, whichever way
+struct CallBuf : DBuf {
+  CallBuf() = default;
+  CallBuf(const CallBuf&) = delete;
+  CallBuf& operator=(const CallBuf&) = delete;
+  ~CallBuf() { release(); }
+};
+
 // The factorisation's rank test.  A pivot (L_jj^2) below 64 ulp of the kernel matrix's diagonal k(x,x) + noise is as large as
 // the rounding accumulated in its column's update at N of a few thousand: it carries no information, and neither does the
 // log-determinant built on it (a too small one - the optimiser is drawn to exactly these hyper-parameters).  Such a
@@ -151,6 +160,22 @@ void configure_posterior_kernels();
 void configure_loo_kernels();
 
 struct Depth { int first, count, nblocks; };
+
+// Retention buffers of a sweep (bobe_gp::sweep's last argument; bobe_gp_wip_select_batch, gp_batch.hip): the caller's
+// device buffers, all with leading dimension ld = C rounded up to 128, that receive what the sweep otherwise keeps per chunk
+// or per super-chunk in the handle's workspace - CsT [d x ld] scaled candidates, V [Np x ld] = L^-1 K(X, C), crossT [Mp x ld],
+// sc [ld] = s_c.  The launches and their order are the sweep's own; only the addresses they write to differ.
+// V_used / ldv_used (out): where V ended up - the caller's buffer, or the handle's V_Z when the candidates are the
+// integration points (that path forms no V of its own).
+struct SweepKeep {
+  double* CsT = nullptr;
+  double* V = nullptr;
+  double* crossT = nullptr;
+  double* sc = nullptr;
+  int64_t ld = 0;
+  const double* V_used = nullptr;
+  int64_t ldv_used = 0;
+};
 
 // What an evaluation workspace (a lock-step batch slot, an evaluation slot, the single evaluation's own A2 / Linv2 / ...)
 // holds once its evaluation was collected: the factor of `h` on data generation `gen` at padded size `Np`, and the
@@ -465,10 +490,12 @@ struct bobe_gp {
 
   // ---- gp_sweep.hip
   void prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w);
+  void wip_score(const double* crossT, int64_t ldx, const double* cst, const double* scs, const double* bz, int64_t ns,
+                 int64_t M, int64_t Mp, double y_std, double* wv, double* ws, double* vo);
   // gated: apply the classifier gate (when one is set) to the mean / var outputs (the predict family, not the sweep)
   void sweep(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv, double* wipstd,
              double* mean, double* var, int policy, int64_t* argmin_v, double* min_v, int64_t* argmin_s, double* min_s,
-             double* fantasy_out, bool gated = false);
+             double* fantasy_out, bool gated = false, bobe::SweepKeep* keep = nullptr);
   void wip_grad(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv, double* wipstd,
                 double* dwipv, double* dwipstd);
   void predict_grad(const double* Xq, int64_t C, double* mean, double* var, double* dmean, double* dvar);
@@ -484,6 +511,10 @@ struct bobe_gp {
   void loo_terms(const double* linv, const double* al, bool with_grad_terms, double* sum_out);
   int loo_state(double* mean, double* var, double* lpd, double* sum_lpd);
   int loo_objective(const Hyper& h, double* loo, double* grad);
+
+  // ---- gp_batch.hip (call-local buffers only; the handle's Z-side state is read, never written)
+  int wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,
+                       int64_t* picks, double* pick_scores, double* stage_scores);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

@@ -29,14 +29,6 @@ namespace {
 constexpr int64_t MAX_QUERIES = 16384;             // bobe_gp.h: C <= 16384
 constexpr size_t V_CHUNK_BYTES = size_t(1) << 30;  // V and K(X, chunk) are formed for at most this many bytes of columns each
 
-// a device buffer of one call: freed when the call returns, whichever way
-struct CallBuf : DBuf {
-  CallBuf() = default;
-  CallBuf(const CallBuf&) = delete;
-  CallBuf& operator=(const CallBuf&) = delete;
-  ~CallBuf() { release(); }
-};
-
 // the scaled query coordinates QsT (d x Cp) and, optionally, the posterior mean
 struct Queries {
   int64_t C = 0, Cp = 0;

@@ -127,9 +127,26 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
   if (host_z) z_seen_m = M;
 }
 
+// the scoring launch of ns candidates (k_wip_score): crossT and the scaled candidates CsT with leading dimension ldx, s_c, base_z
+void bobe_gp::wip_score(const double* crossT, int64_t ldx, const double* cst, const double* scs, const double* bz, int64_t ns,
+                        int64_t M, int64_t Mp, double y_std, double* wv, double* ws, double* vo) {
+  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
+  const dim3 grid((unsigned)((ns + 63) / 64));
+  const size_t sm = (size_t)(d + 1) * 128 * sizeof(double);
+#define WS(KE, DC)                                                                                                        \
+  hipLaunchKernelGGL((k_wip_score<KE, DC>), grid, dim3(256), sm, stream, crossT, ldx, cst, ldx, (const double*)ZsT.d(), Mp, M, \
+                     scs, bz, ns, hyp, y_std * y_std, wv, ws, vo, M)
+  if (hyp.kern == 0) {
+    if (dcap == 8) WS(0, 8); else if (dcap == 16) WS(0, 16); else WS(0, 32);
+  } else {
+    if (dcap == 8) WS(1, 8); else if (dcap == 16) WS(1, 16); else WS(1, 32);
+  }
+#undef WS
+}
+
 void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv,
                     double* wipstd, double* mean, double* var, int policy, int64_t* argmin_v, double* min_v,
-                    int64_t* argmin_s, double* min_s, double* fantasy_out, bool gated) {
+                    int64_t* argmin_s, double* min_s, double* fantasy_out, bool gated, bobe::SweepKeep* keep) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   if (C <= 0) throw Err(BOBE_ERR_ARG, "C must be positive");
   const bool do_wip = (Z != nullptr);
@@ -153,30 +170,39 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
   }
   // scoring runs once per super-chunk of SC candidates (bounded crossT workspace: Mp x SC doubles)
   const int64_t SC = round_up(std::min<int64_t>(C, std::max<int64_t>(CH, 65536)), CH);
-  CsT.ensure((size_t)d * SC * sizeof(double));
+  // keep (bobe_gp_wip_select_batch, gp_batch.hip): the scaled candidates, V, crossT and s_c of ALL candidates are written
+  // into the caller's buffers (leading dimension keep->ld) instead of the handle's per-chunk / per-super-chunk workspace -
+  // other addresses for the same launches, nothing else
+  if (!keep) CsT.ensure((size_t)d * SC * sizeof(double));
   if (!cand_is_z) kXC.ensure((size_t)Np * CH * sizeof(double));
-  sc.ensure((size_t)SC * sizeof(double));
+  if (!keep) sc.ensure((size_t)SC * sizeof(double));
   qpart.ensure((size_t)nb * (Mp > CH ? Mp : CH) * sizeof(double));
   part.ensure((size_t)nb * (Np > CH ? Np : CH) * sizeof(double));
-  if (do_wip) pv.ensure((size_t)Mp * SC * sizeof(double));                   // crossT
-  if ((do_wip || refine_v) && !cand_is_z) vxc.ensure((size_t)Np * CH * sizeof(double));      // V = Linv K(X, chunk)
+  if (do_wip && !keep) pv.ensure((size_t)Mp * SC * sizeof(double));          // crossT
+  if ((do_wip || refine_v) && !cand_is_z && !keep) vxc.ensure((size_t)Np * CH * sizeof(double));   // V = Linv K(X, chunk)
   // The cross-covariance tiles of a chunk ride in the launch that solves the NEXT chunk (k_trimul), so V alternates
   // between two buffers; the last chunk of a super-chunk gets a launch of its own (k_cross_vv).  The blocked substitution of
   // an ill-conditioned factor (solve_v) is followed by a separate cross launch per chunk.
   const bool fuse_cross = do_wip && !refine_v && C > CH;
-  if (fuse_cross) vxc2.ensure((size_t)Np * CH * sizeof(double));
+  if (fuse_cross && !keep) vxc2.ensure((size_t)Np * CH * sizeof(double));
   double* vbuf[2] = {vxc.d(), fuse_cross ? vxc2.d() : vxc.d()};
   int vsel = 0;
+  const int64_t ldC = keep ? keep->ld : SC;      // leading dimension of the scaled candidates and of crossT
+  const int64_t ldV = keep ? keep->ld : CH;      // ... and of V
+  if (keep) {
+    keep->V_used = cand_is_z ? VZ.d() : keep->V;
+    keep->ldv_used = cand_is_z ? Mp : keep->ld;
+  }
   struct { bool valid; const double* V; int64_t ncp; double* cross; } pend = {false, nullptr, 0, nullptr};
   auto cross_alone = [&](const double* Vc, int64_t ncp_, double* cross_out, int64_t ldvc) {
     // cross-covariances from the two solved factors (sweep_kernels.hpp, k_cross_vv): crossT[z][c] = VZ[:, z] . V[:, c]
     prof_begin(BOBE_PROF_CROSSVV);
     if ((int64_t)nzt * (ncp_ / TILE) >= 2 * std::max(num_cus, 1))
       hipLaunchKernelGGL(cross_vv128_kernel(), dim3((unsigned)(ncp_ / TILE), (unsigned)nzt), dim3(256), GEMM_SMEM_BYTES, stream,
-                         (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, SC);
+                         (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, ldC);
     else
       hipLaunchKernelGGL(cross_vv64_kernel(), dim3((unsigned)(ncp_ / 64), (unsigned)(Mp / 64)), dim3(256), GEMM64_SMEM_BYTES,
-                         stream, (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, SC);
+                         stream, (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, ldC);
     prof_end(BOBE_PROF_CROSSVV);
   };
   double* d_mean = out_dev(mean, C, o_mean);
@@ -197,26 +223,28 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
   if (fantasy_out) {   // dumped with leading dimension M (dense), C x M
     d_fant = is_device_ptr(fantasy_out) ? fantasy_out : (kout.ensure((size_t)C * M * sizeof(double)), kout.d());
   }
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
   for (int64_t s0 = 0; s0 < C; s0 += SC) {
     const int64_t ns = (C - s0 < SC) ? (C - s0) : SC;
     const int64_t nsp = round_up(ns, TILE);
-    scale(cin + s0 * d, ns, nsp, hyp, CsT.d(), SC);
+    double* const cst = keep ? keep->CsT + s0 : CsT.d();        // this super-chunk's scaled candidates, crossT, s_c
+    double* const xT = keep ? keep->crossT + s0 : pv.d();
+    double* const scs = keep ? keep->sc + s0 : sc.d();
+    scale(cin + s0 * d, ns, nsp, hyp, cst, ldC);
     for (int64_t c0 = 0; c0 < ns; c0 += CH) {
       const int64_t nc = (ns - c0 < CH) ? (ns - c0) : CH;
       const int64_t ncp = round_up(nc, TILE);
       if (cand_is_z) {                // (one chunk: C <= CH) V_C = V_Z, s_c from its column sums, the cross tiles V_Z^T V_Z
         hipLaunchKernelGGL(k_colsq_tile_parts, dim3((unsigned)((ncp + 255) / 256), (unsigned)nb), dim3(256), 0, stream,
                            (const double*)VZ.d(), Mp, ncp, qpart.d(), CH);
-        cross_alone(VZ.d(), ncp, pv.d() + c0, Mp);
+        cross_alone(VZ.d(), ncp, xT + c0, Mp);
         hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream,
-                           (const double*)qpart.d(), CH, nb, nc, kself, policy, sc.d() + c0, (double*)nullptr);
+                           (const double*)qpart.d(), CH, nb, nc, kself, policy, scs + c0, (double*)nullptr);
         LAUNCH_CHECK();
         continue;
       }
       // (posterior mean: the assembly leaves K(X, chunk)^T alpha per row tile on the way, k_gemv_t_part's partial sums)
       prof_begin(BOBE_PROF_KXC);
-      kernel_matrix_cross(XsT.d(), Np, N, Np, CsT.d() + c0, SC, nc, ncp, hyp, kXC.d(), CH,
+      kernel_matrix_cross(XsT.d(), Np, N, Np, cst + c0, ldC, nc, ncp, hyp, kXC.d(), CH,
                           d_mean ? (const double*)alpha.d() : nullptr, d_mean ? part.d() : nullptr, CH);
       prof_end(BOBE_PROF_KXC);
       if (d_mean) {
@@ -224,48 +252,37 @@ void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, d
                            (const double*)part.d(), CH, nb, 0, nc, d_mean + s0 + c0);
       }
       if (do_wip || d_var) {       // (a mean-only prediction - nested sampling's likelihood calls - needs no triangular product)
-        double* vcur = vbuf[vsel];
+        double* vcur = keep ? keep->V + s0 + c0 : vbuf[vsel];
         prof_begin(BOBE_PROF_TRIMUL);
         if (fuse_cross) {
           const int ncv = (int)(ncp / TILE), ncx = pend.valid ? (int)(pend.ncp / TILE) : 0;
           const int nz = pend.valid ? nzt : 0;
           hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)std::max(ncv, ncx), (unsigned)(nb + nz)), dim3(256), GEMM_SMEM_BYTES,
-                             stream, (const double*)Linv.d(), Np, nb, (const double*)kXC.d(), CH, vcur, CH, qpart.d(), CH,
-                             (const double*)VZ.d(), Mp, nz, pend.cross, SC, pend.V, CH, ncx, ncv);
-          pend = {true, vcur, ncp, pv.d() + c0};
+                             stream, (const double*)Linv.d(), Np, nb, (const double*)kXC.d(), CH, vcur, ldV, qpart.d(), CH,
+                             (const double*)VZ.d(), Mp, nz, pend.cross, ldC, pend.V, ldV, ncx, ncv);
+          pend = {true, vcur, ncp, xT + c0};
           vsel ^= 1;
         } else {
-          solve_v(kXC.d(), CH, ncp, (do_wip || refine_v) ? vcur : nullptr, CH, qpart.d(), CH);
+          solve_v(kXC.d(), CH, ncp, (do_wip || refine_v) ? vcur : nullptr, ldV, qpart.d(), CH);
         }
         prof_end(BOBE_PROF_TRIMUL);
-        if (do_wip && !fuse_cross) cross_alone(vcur, ncp, pv.d() + c0, CH);
+        if (do_wip && !fuse_cross) cross_alone(vcur, ncp, xT + c0, ldV);
         // s_c for the scorer, var for the caller
         hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream,
-                           (const double*)qpart.d(), CH, nb, nc, kself, policy, sc.d() + c0,
+                           (const double*)qpart.d(), CH, nb, nc, kself, policy, scs + c0,
                            d_var ? d_var + s0 + c0 : nullptr);
       }
       LAUNCH_CHECK();
     }
     if (pend.valid) {                 // the super-chunk's last chunk: no next launch to ride in
-      cross_alone(pend.V, pend.ncp, pend.cross, CH);
+      cross_alone(pend.V, pend.ncp, pend.cross, ldV);
       pend.valid = false;
     }
     if (do_wip) {
-      const dim3 grid((unsigned)((ns + 63) / 64));
-      const size_t sm = (size_t)(d + 1) * 128 * sizeof(double);
       double* vo = d_fant ? d_fant + s0 * M : nullptr;
       prof_begin(BOBE_PROF_CROSS);
-#define WS(KE, DC)                                                                                              \
-  hipLaunchKernelGGL((k_wip_score<KE, DC>), grid, dim3(256), sm, stream, (const double*)pv.d(), SC,             \
-                     (const double*)CsT.d(), SC, (const double*)ZsT.d(), Mp, M, (const double*)sc.d(),          \
-                     (const double*)basez.d(), ns, hyp, y_std * y_std, d_wipv ? d_wipv + s0 : nullptr,          \
-                     d_wipstd ? d_wipstd + s0 : nullptr, vo, M)
-      if (hyp.kern == 0) {
-        if (dcap == 8) WS(0, 8); else if (dcap == 16) WS(0, 16); else WS(0, 32);
-      } else {
-        if (dcap == 8) WS(1, 8); else if (dcap == 16) WS(1, 16); else WS(1, 32);
-      }
-#undef WS
+      wip_score(xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, d_wipv ? d_wipv + s0 : nullptr,
+                d_wipstd ? d_wipstd + s0 : nullptr, vo);
       prof_end(BOBE_PROF_CROSS);
       LAUNCH_CHECK();
     }

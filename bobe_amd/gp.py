@@ -744,6 +744,34 @@ class GP:
             out["mean"], out["var"] = mean, var
         return out
 
+    def wip_select_batch(self, candidates, mc_points, n_batch, criterion="wipstd", return_stage_scores=False):
+        """A kriging-believer batch of ``n_batch`` WIPV / WIPStd picks out of ``candidates`` from ONE sweep
+        (``bobe_gp_wip_select_batch``): stage 0 is ``wip_sweep`` (same bits), every later member a rank-one downdate of the
+        sweep's retained intermediates on the device instead of a sweep on a surrogate that gained the pick.  A picked
+        candidate is not picked again.  ``y_std`` is held fixed over the batch (the believer loop standardises again after
+        every member; in standardised units the two agree).  Not gated.
+
+        ``candidates`` / ``mc_points``: NumPy arrays or torch CUDA tensors.  Returns dict(indices (n_batch,), points
+        (n_batch, d), scores (n_batch,) - the winning score of every stage[, stage_scores (n_batch, C) - every stage's scores
+        of all candidates])."""
+        if criterion not in ("wipv", "wipstd"):
+            raise ValueError(f"criterion must be 'wipv' or 'wipstd', not {criterion!r}")
+        dev = hasattr(candidates, "data_ptr")
+        cand = candidates if dev else _lib.as_f64(np.atleast_2d(candidates))
+        z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
+        c, m, nb = int(cand.shape[0]), int(z.shape[0]), int(n_batch)
+        picks = np.full(max(nb, 1), -1, dtype=np.int64)
+        scores = np.empty(max(nb, 1))
+        stage = np.empty((max(nb, 1), c)) if return_stage_scores else None
+        _lib.check(self._lib.bobe_gp_wip_select_batch(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), nb,
+                                                      0 if criterion == "wipv" else 1, _lib.ptr(picks), _lib.ptr(scores),
+                                                      _lib.ptr(stage)), "bobe_gp_wip_select_batch")
+        pts = cand[picks.tolist()].detach().cpu().numpy() if dev else np.array(cand[picks])
+        out = {"indices": picks, "points": pts, "scores": scores}
+        if return_stage_scores:
+            out["stage_scores"] = stage
+        return out
+
     def acq_ei(self, x, best_y, zeta=0.0, log_ei=False):
         """+EI / +log EI at x (acquisition.py:226-253, 318-330), standardised units."""
         x = _lib.as_f64(np.atleast_2d(x))

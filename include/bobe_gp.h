@@ -139,6 +139,36 @@ int bobe_gp_wip_sweep(bobe_gp_t* gp, const double* cand, int64_t C, const double
                       double* wipv, double* wipstd, double* mean, double* var, int64_t* argmin_v, double* min_v,
                       int64_t* argmin_s, double* min_s);
 
+/* A kriging-believer batch of n_batch WIPV (criterion 0) or WIPStd (criterion 1) picks out of the C candidates from ONE sweep
+ * (the reference has no counterpart; its loop, acquisition.py:147-196, sweeps once per member on a surrogate that gained the
+ * previous pick at its predicted mean).  The scores depend on the design points only, so appending a pick c* is a rank-one
+ * change of what the scorer reads: with s* the pick's noise-included posterior variance and
+ *   u(.) = (k(., c*) - V(.)^T V(c*) - sum_{i<j} u_i(.) u_i(c*)) / sqrt(s*),   V = L^-1 K(X, .),
+ * the cross term gains u(z) u(c), base_z loses u(z)^2, s_c loses u(c)^2, and the scoring kernel runs again.
+ *   stage 0  is bobe_gp_wip_sweep's own launch sequence (the plain product or the blocked substitution, the chunking, the fused
+ *            cross tiles) with its intermediates kept for all candidates: stage_scores row 0, picks[0] and pick_scores[0] are
+ *            the bits bobe_gp_wip_sweep returns as wipv / wipstd, argmin_* and min_* for the same inputs (cand == Z included).
+ *   stage j  one pass over the retained V, one read-modify-write of the cross terms, one scoring pass; all on the handle's
+ *            stream, fixed summation orders: the same state gives the same bits.
+ * picks[j] (n_batch, required) = the argmin of stage j over the candidates NOT picked before (first occurrence; a picked
+ * index is masked - the reference's update() would drop it as a duplicate); pick_scores[j] (n_batch, may be NULL) its score;
+ * stage_scores (n_batch x C, may be NULL) every stage's scores of ALL candidates, picked ones included (the computed value).
+ * The NaN / 1e-12 floor rules are the scorer's (gp.py:574-576) at every stage.  picks, pick_scores and stage_scores may be
+ * host or device memory.
+ * Units: y_std is the CALLER's at every stage.  The believer loop standardises its data again after every appended point
+ * (gp.py:520-536), which rescales its scores by (y_std_j / y_std)^p, p = 2 (WIPV) or 1 (WIPStd), a factor common to all
+ * candidates of a stage; that re-standardisation is NOT imitated: in standardised units (scores / y_std^p) the two agree.
+ * NOT gated (like bobe_gp_wip_sweep's scores).  All work buffers are call-local and freed before the call returns; the
+ * handle's state is left as it was.  The buffers that grow with C are capped at 16 GiB = 2^31 doubles in all: (Np + Mp + d + 1)
+ * x Cp for V, the cross terms, the scaled candidates and s_c, (Np / 128 + n_batch - 1) x Cp for the later stages' partial sums
+ * and u rows (n_batch > 1), and (n_batch, or 1 without stage_scores) x C for scores staged on their way to host memory (Np, Mp,
+ * Cp: N, M, C rounded up to 128).  N = 4096, M = 512, d = 8 with n_batch = 64 and host stage_scores admits 449 536 candidates.
+ * Returns BOBE_ERR_ARG for n_batch outside 1 ... min(C, 64), a criterion other than 0 / 1, a NULL picks / cand / Z, C or M
+ * < 1, or a candidate count above the cap; BOBE_ERR_STATE without a factorised state.  A NaN state behaves as in
+ * bobe_gp_wip_sweep (BOBE_OK, scores at the floor).  One handle, one device: there is no bobe_mgpu_* form. */
+int bobe_gp_wip_select_batch(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                             int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores);
+
 /* GP.fantasy_var (gp.py:552-576) for C candidates at once: out is C x M, out[c][z] = var+(z|c)*y_std^2. */
 int bobe_gp_fantasy_var(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                         double* out);
