@@ -762,7 +762,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void k_chol_panel(double* __restrict
     const int64_t kb = (int64_t)jb.k0 * 64, ke = (int64_t)jb.k1 * 64;
     v4d acc[2][2];
     load_tile<64, 64>(acc, As, lda, r0, c0, tid);
-    gemm_tile<KC, KC, 64, 64, FILL_BK, true>(acc, As, lda, r0, As, lda, c0, kb, ke, S + grp * FILL_SMEM_DOUBLES, tid);
+    tile_gemm<false, KC, KC, 64, true, false, FILL_BK>(acc, As, lda, r0, As, lda, c0, kb, ke, S + grp * FILL_SMEM_DOUBLES, tid);
     if (live) store_tile<64, 64>(acc, As, lda, r0, c0, 1.0, 0.0, tid);
     return;
   }
@@ -794,7 +794,7 @@ __global__ __launch_bounds__(256) void k_copy_diag(double* __restrict__ A, int64
 // colk0 / far_col (optional, 64x64 tiles only): block columns >= far_col read their first pending panel from colk0[column]
 // (deferred columns: the K range [colk0[c], k1) differs from column to column; colk0[c] >= k1 skips the column); columns
 // before far_col take the scalar k0 without touching memory.
-// GLDS (T = 64, BK = 16 only): the tile core gemm_tile64_glds instead of the register-staged gemm_tile - same bits
+// GLDS (T = 64, BK = 16 only): the direct-to-LDS tile core instead of the register-staged one (tile_gemm) - same bits
 // (BOBE_GEMM64_GLDS, gp_handle.hpp).  Its occupancy bound of two workgroups per CU caps the registers at 256, so the
 // MFMAs accumulate in VGPRs: with room for 512 the compiler takes the AGPR form and copies all 32 accumulator registers
 // out and back in every K-step of this loop.
@@ -802,6 +802,7 @@ template <int T, int BK, bool GLDS = false>
 __global__ __launch_bounds__(256, GLDS ? 2 : 1) void k_syrk_trail(double* __restrict__ A, int64_t lda, int k0, int k1, int first,
                                                     int colmode, int n, int64_t bsA = 0, int per = 0,
                                                     const int* __restrict__ colk0 = nullptr, int far_col = 0, int ncol = 0) {
+  static_assert(!GLDS || has_glds_core<T, BK>, "no direct-to-LDS core for this tile and K-step");
   extern __shared__ double smem[];
   A += blockIdx.y * bsA;
   int a, b;
@@ -832,12 +833,8 @@ __global__ __launch_bounds__(256, GLDS ? 2 : 1) void k_syrk_trail(double* __rest
   const int64_t base = (int64_t)first * TILE;
   v4d acc[T / 32][T / 32];
   load_tile<T, T>(acc, A, lda, base + (int64_t)a * T, base + (int64_t)b * T);   // acc = C, then acc -= A B^T
-  if constexpr (GLDS && T == 64 && BK == 16)
-    gemm_tile64_glds<KC, KC, true>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T, (int64_t)k0 * TILE,
-                                   (int64_t)k1 * TILE, smem);
-  else
-    gemm_tile<KC, KC, T, T, BK, true>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T,
-                                      (int64_t)k0 * TILE, (int64_t)k1 * TILE, smem);
+  tile_gemm<GLDS, KC, KC, T, true, false, BK>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T,
+                                              (int64_t)k0 * TILE, (int64_t)k1 * TILE, smem);
   store_tile<T, T>(acc, A, lda, base + (int64_t)a * T, base + (int64_t)b * T, 1.0, 0.0);
 }
 
@@ -866,7 +863,7 @@ __device__ __forceinline__ bool tri_find(const TriProb* __restrict__ probs, int 
   return false;
 }
 
-// GLDS (T = 64 only): gemm_tile64_glds as in k_syrk_trail (k_trtri_R likewise)
+// GLDS: the tile core as in k_syrk_trail (k_trtri_R likewise); the host asks for it on 64 x 64 tiles only
 template <int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_trtri_T(const double* __restrict__ L, int64_t ldl,
                                                     const double* __restrict__ Linv, int64_t ldi,
@@ -892,10 +889,7 @@ __global__ __launch_bounds__(256, 2) void k_trtri_T(const double* __restrict__ L
     const int64_t m0 = (int64_t)p.mid * TILE + (int64_t)ti * T, n0 = (int64_t)p.lo * TILE + (int64_t)tj * T;
     v4d acc[T / 32][T / 32];
     acc_zero(acc);
-    if constexpr (GLDS && T == 64)
-      gemm_tile64_glds<KC, RC>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
-    else
-      gemm_tile<KC, RC, T, T, TileCfg<T>::bk>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
+    tile_gemm<GLDS, KC, RC, T>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
     store_tile<T, T>(acc, Tmp, ldt, m0, n0, 1.0, 0.0);
   }
 }
@@ -924,10 +918,7 @@ __global__ __launch_bounds__(256, 2) void k_trtri_R(double* __restrict__ Linv, i
     const int64_t m0 = (int64_t)p.mid * TILE + (int64_t)ti * T, n0 = (int64_t)p.lo * TILE + (int64_t)tj * T;
     v4d acc[T / 32][T / 32];
     acc_zero(acc);
-    if constexpr (GLDS && T == 64)
-      gemm_tile64_glds<KC, RC>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
-    else
-      gemm_tile<KC, RC, T, T, TileCfg<T>::bk>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
+    tile_gemm<GLDS, KC, RC, T>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
     store_tile<T, T>(acc, Linv, ldi, m0, n0, -1.0, 0.0);
   }
 }
@@ -950,8 +941,8 @@ __global__ __launch_bounds__(256, 2) void k_lauum_tiles32(const double* __restri
   const int r32 = 2 * ti + ((tile >> 1) & 1), c32 = 2 * tj + (tile & 1);
   v4d acc[1][1];
   acc_zero(acc);
-  gemm_tile<RC, RC, 32, 32, BK32>(acc, Linv, ldi, (int64_t)r32 * 32, Linv, ldi, (int64_t)c32 * 32,
-                                  (int64_t)(r32 > c32 ? r32 : c32) * 32, np, smem);
+  tile_gemm<false, RC, RC, 32>(acc, Linv, ldi, (int64_t)r32 * 32, Linv, ldi, (int64_t)c32 * 32,
+                               (int64_t)(r32 > c32 ? r32 : c32) * 32, np, smem);
   store_tile<32, 32>(acc, Kinv, ldk, (int64_t)r32 * 32, (int64_t)c32 * 32, 1.0, 0.0);
 }
 
@@ -961,7 +952,7 @@ __global__ __launch_bounds__(256, 2) void k_lauum_tiles32(const double* __restri
 // off-diagonal tiles weighted x2.  Optionally stores Kinv (lower tiles) for tests.
 // from_kinv: the tiles of K^-1 are already in Kinv (k_lauum_tiles, slot stride bsK): only the gradient epilogue runs, each
 // thread on the elements it would own after the GEMM - the partial sums are the fused kernel's, bit for bit.
-// GLDS (T = 64 only): gemm_tile64_glds as in k_syrk_trail.
+// GLDS: the tile core as in k_syrk_trail; the host asks for it on 64 x 64 tiles only.
 template <int KERN, int DCAP, int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict__ Linv, int64_t ldi, int64_t np,
                                                        int64_t n, const double* __restrict__ alpha,
@@ -988,11 +979,7 @@ __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict_
     load_tile<T, T>(acc, Kinv + slot * bsK, ldk, (int64_t)ti * T, (int64_t)tj * T);
   } else {
     acc_zero(acc);
-    if constexpr (GLDS && T == 64)
-      gemm_tile64_glds<RC, RC>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np, smem);
-    else
-      gemm_tile<RC, RC, T, T, TileCfg<T>::bk>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T,
-                                              np, smem);
+    tile_gemm<GLDS, RC, RC, T>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np, smem);
     if (Kinv) store_tile<T, T>(acc, Kinv, ldk, (int64_t)ti * T, (int64_t)tj * T, 1.0, 0.0);
   }
   // stage coordinates and alpha in the (now free) GEMM LDS

@@ -200,23 +200,16 @@ struct Stamps {
 // launch (k_chol_panel<true, .>) are two tile groups in one 512-thread workgroup, each with its own smem slice - the
 // barriers inside are workgroup-wide, so both groups must run the same number of K-steps.
 // NEGA: accumulate -A*B (the A fragment is negated on the way into the MFMA).
-// SYNC: the barrier between K-steps; WgSync (a workgroup barrier) is the only policy in use.
-struct WgSync {
-  __device__ __forceinline__ void sync() { __syncthreads(); }
-};
-
 // TRIL: the A operand is LOWER TRIANGULAR in its last TM columns of K (A(m0 + r, kend - TM + c) = 0 for c > r: the
 // diagonal block of a triangular matrix closes the K range).  In those K-steps the MFMAs of 4-column groups that lie wholly
 // right of a 16-row fragment's last row are skipped - exact zeros times finite numbers: the accumulators keep their bits
 // (up to the sign of a zero).  The steps before the block run the plain loop body (a predicate in every step cost the
 // sweep GEMM 2.7 %; this form gains it 1.2 %; on 64 x 64 tiles - the inverse's launches - the skips cost more than they
 // save: 4 MFMAs per K group and fragment row there).
-template <int LA, int LB, int TM = 128, int TN = 128, int BK = BK128, bool NEGA = false, class SYNC = WgSync, bool TRIL = false>
+template <int LA, int LB, int TM = 128, int TN = 128, int BK = BK128, bool NEGA = false, bool TRIL = false>
 __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const double* __restrict__ A, int64_t lda,
                                           int64_t m0, const double* __restrict__ B, int64_t ldb, int64_t n0,
-                                          int64_t kbeg, int64_t kend, double* smem, int tid = threadIdx.x,
-                                          SYNC* sy = nullptr) {
-  WgSync wg_default;
+                                          int64_t kbeg, int64_t kend, double* smem, int tid = threadIdx.x) {
   constexpr int FM = TM / 32, FN = TN / 32;
   constexpr int IA = Img<LA, TM, BK>::doubles;
   constexpr int IB = Img<LB, TN, BK>::doubles;
@@ -231,7 +224,7 @@ __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const do
   stage_load<LB, TN, BK>(rb, B, ldb, n0, kbeg, t);
   stage_store<LA, TM, BK>(ra, smem, t);
   stage_store<LB, TN, BK>(rb, smem + IA, t);
-  if (sy) sy->sync(); else wg_default.sync();
+  __syncthreads();
   BOBE_STAMPS_DECL
   int buf = 0;
   // one K-step: next step's operands on their way, this step's MFMAs, next step's LDS image.  IN (a constant): the step
@@ -272,7 +265,7 @@ __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const do
       stage_store<LB, TN, BK>(rb, na + IA, t);
     }
     BOBE_STAMP(2);
-    if (sy) sy->sync(); else wg_default.sync();
+    __syncthreads();
     BOBE_STAMP(3);
     BOBE_STAMP_STEP();
     buf ^= 1;
@@ -284,44 +277,57 @@ __device__ __forceinline__ void gemm_tile(v4d (&acc)[TM / 32][TN / 32], const do
   BOBE_STAMPS_END(t);
 }
 
-// ---- 128 x 128 tiles, BK = 16: operands straight into LDS, fragments one sub-step ahead -------------------------------
-// The same MFMAs as gemm_tile<LA, LB, 128, 128, 16, NEGA, WgSync, TRIL> in the same order for every accumulator, so the
-// same bits; what differs is how the operands get there.
+// ---- 128 x 128 and 64 x 64 tiles, BK = 16: operands straight into LDS, fragments one sub-step ahead -------------------
+// The same MFMAs as gemm_tile<LA, LB, T, T, 16, NEGA, TRIL> in the same order for every accumulator, so the same bits; what
+// differs is how the operands get there.
 //   * Staging: buffer_load_dwordx4 ... lds (16 B per lane straight into LDS; the destination is the wave-uniform base +
-//     16 B x lane).  No staging registers (32 VGPRs at 128 x 16 x 2 operands) and no vmcnt-gated ds_write block at the end of a
-//     K-step: the next step's loads are issued at the top of the step and waited for by the barrier that closes it.
-//   * An RC image keeps gemm_tile's [BK][R + 16] layout: one k-row (128 doubles = 1 KiB) is one wave-instruction.
-//   * A KC image cannot keep the 2-double row pad (an instruction covers 8 rows of 128 B), so it is [128][16] unpadded
+//     16 B x lane).  One wave-instruction carries 1 KiB, so an operand tile of T x 16 is T / 8 of them, T / 32 per wave.  No
+//     staging registers (32 VGPRs at 128 x 16 x 2 operands) and no vmcnt-gated ds_write block at the end of a K-step: the
+//     next step's loads are issued at the top of the step and waited for by the barrier that closes it.
+//   * A KC image cannot keep gemm_tile's 2-double row pad (an instruction covers 8 rows of 128 B), so it is [T][16] unpadded
 //     with the 16-byte chunk c of row r stored at chunk c ^ ((r >> 1) & 7): each lane's SOURCE address carries the
 //     permutation, the fragment read applies it again (an involution).  A 32-lane ds_read_b64 group still hits 32
 //     distinct bank pairs: rows r and r + 1 differ by 32 banks, the eight row pairs by the chunk permutation.
+//   * An RC image of T = 128 keeps gemm_tile's [BK][R + 16] layout: one k-row (128 doubles = 1 KiB) is one wave-instruction.
+//   * An RC image of T = 64: a 64-wide k-row is only 512 B, so one instruction carries k-rows 2g and 2g + 1 and the row pad
+//     cannot be kept.  The image is [16][64] with the chunks of every ODD k-row stored at c ^ 8 (element (k, r) at
+//     k * 64 + (r ^ 16 (k & 1))); the source address carries the permutation, the read applies it again.  A 32-lane
+//     ds_read_b64 group reads k-rows 4 ks and 4 ks + 1 at 16 consecutive r from a multiple of 16: 32 dwords each, which the
+//     XOR puts in opposite halves of the 64 banks (unpadded, k-rows k and k + 1 are 128 dwords apart: the same 32 banks, a
+//     two-way conflict).
 //   * Fragments are double-buffered: the reads of sub-step ks + 1 are issued ahead of the MFMAs of ks.  The barrier
 //     comes after the MFMAs of the third sub-step; the first sub-step of the next K-step is read right behind it, under
-//     the MFMAs of the fourth.  Every fragment read has the 16 MFMAs of one sub-step to land in.
-// One barrier per K-step (its fence drains the step's LDS loads with vmcnt(0)); 73,728 B of LDS or less, so two
-// workgroups per CU as before.  The last K-step reloads its own slice into the idle buffer rather than branching round
-// the loads (a branch there costs the fragment reads their counted waits).
-template <int L>
-struct Img128 {
-  static constexpr int doubles = (L == KC) ? 128 * 16 : 16 * (128 + 16);
-};
-template <int LA, int LB>
-constexpr int gemm128_smem_doubles() { return 2 * (Img128<LA>::doubles + Img128<LB>::doubles); }
-static_assert(gemm128_smem_doubles<RC, RC>() <= GEMM_SMEM_DOUBLES && gemm128_smem_doubles<KC, RC>() <= GEMM_SMEM_DOUBLES,
-              "the 128-tile LDS images must fit the launches' GEMM_SMEM_BYTES");
+//     the MFMAs of the fourth.  Every fragment read has the MFMAs of one sub-step (16 at T = 128) to land in.
+// One barrier per K-step (its fence drains the step's LDS loads with vmcnt(0)).  T = 128: 73,728 B of LDS or less, so two
+// workgroups per CU as with gemm_tile.  T = 64: 32,768 B (two buffers of two 8 KiB images), within GEMM64_SMEM_BYTES and
+// k_syrk_trail's SYRK64_SMEM, so the launches keep their occupancy.  The last K-step reloads its own slice into the idle
+// buffer rather than branching round the loads (a branch there costs the fragment reads their counted waits).
+// Which tiles have this core (the one place that says so; tile_gemm below asks it):
+template <int T, int BK = TileCfg<T>::bk>
+constexpr bool has_glds_core = (T == 64 || T == 128) && BK == 16;
 
-// global -> LDS, one operand tile of 128 x 16: four wave-instructions per wave (wave w: KC rows 8g .. 8g + 7, RC k-row g,
-// g = w + 4i)
-template <int L>
-__device__ __forceinline__ void glds_stage128(const double* __restrict__ p, int64_t ld, int64_t r0, int64_t k0, double* img,
-                                              int wave, int lane) {
+template <int L, int T>
+struct ImgGlds {
+  static constexpr int doubles = (L == RC && T == 128) ? 16 * (128 + 16) : T * 16;
+};
+template <int LA, int LB, int T>
+constexpr int gemm_glds_smem_doubles() { return 2 * (ImgGlds<LA, T>::doubles + ImgGlds<LB, T>::doubles); }
+static_assert(gemm_glds_smem_doubles<RC, RC, 128>() <= GEMM_SMEM_DOUBLES && gemm_glds_smem_doubles<KC, RC, 128>() <= GEMM_SMEM_DOUBLES,
+              "the 128-tile LDS images must fit the launches' GEMM_SMEM_BYTES");
+static_assert(gemm_glds_smem_doubles<RC, RC, 64>() * 8 <= GEMM64_SMEM_BYTES, "the 64-tile LDS images must fit GEMM64_SMEM_BYTES");
+
+// global -> LDS, one operand tile of T x 16: T / 32 wave-instructions per wave (wave w, g = w + 4i: KC rows 8g .. 8g + 7;
+// RC k-row g at T = 128, k-rows 2g and 2g + 1 at T = 64)
+template <int L, int T>
+__device__ __forceinline__ void glds_stage(const double* __restrict__ p, int64_t ld, int64_t r0, int64_t k0, double* img,
+                                           int wave, int lane) {
   // (a buffer load into LDS rather than global_load_lds: the compiler treats the latter as a FLAT access that may return
   // out of order and then waits lgkmcnt(0) for every fragment read; the resource is based at the tile's corner, so the
   // 32-bit offsets stay below 128 x ld x 8 bytes)
   const double* base = (L == KC) ? p + r0 * ld + k0 : p + k0 * ld + r0;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < T / 32; ++i) {
     const int g = wave + 4 * i;
     unsigned off;
     double* dst;
@@ -329,51 +335,56 @@ __device__ __forceinline__ void glds_stage128(const double* __restrict__ p, int6
       const int r = 8 * g + (lane >> 3);
       off = (unsigned)((r * ld + 2 * ((lane & 7) ^ ((r >> 1) & 7))) * 8);
       dst = img + 128 * g;
-    } else {
+    } else if (T == 128) {
       off = (unsigned)((g * ld + 2 * lane) * 8);
       dst = img + (128 + 16) * g;
+    } else {
+      const int h = lane >> 5;                                     // k-row 2 g + h, LDS chunk lane & 31
+      off = (unsigned)(((2 * g + h) * ld + 2 * ((lane & 31) ^ (8 * h))) * 8);
+      dst = img + 128 * g;
     }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, off, 0, 0, 0);
   }
 }
 
-// fragment read from a 128 x 16 image: 16-row sub-tile s of the wave's rows at woff, sub-step ks.  KC: the lane's row is
+// fragment read from a T x 16 image: 16-row sub-tile s of the wave's rows at woff, sub-step ks.  KC: the lane's row is
 // woff + 16 s + (lane & 15), its chunk 2 ks + (lane >> 5) (= 2 ks ^ (lane >> 5)), permuted by ((lane & 15) >> 1)
-template <int L>
-__device__ __forceinline__ double frag_read128(const double* img, int woff, int s, int ks, int lane) {
+template <int L, int T>
+__device__ __forceinline__ double frag_read_glds(const double* img, int woff, int s, int ks, int lane) {
   if (L == KC) {
     const int h = (lane >> 5) ^ ((lane & 15) >> 1);
     return img[(woff + 16 * s + (lane & 15)) * 16 + 2 * ((2 * ks) ^ h) + ((lane >> 4) & 1)];
-  } else {
+  } else if (T == 128) {
     return img[(4 * ks + (lane >> 4)) * (128 + 16) + woff + 16 * s + (lane & 15)];
+  } else {
+    return img[(4 * ks + (lane >> 4)) * 64 + ((woff + 16 * s + (lane & 15)) ^ (((lane >> 4) & 1) << 4))];
   }
 }
 
-template <int LA, int LB, bool NEGA = false, bool TRIL = false>
-__device__ __forceinline__ void gemm_tile128_glds(v4d (&acc)[4][4], const double* __restrict__ A, int64_t lda, int64_t m0,
-                                                  const double* __restrict__ B, int64_t ldb, int64_t n0, int64_t kbeg,
-                                                  int64_t kend, double* smem, int tid = threadIdx.x) {
-  constexpr int BK = 16, TM = 128;
-  constexpr int IA = Img128<LA>::doubles, IB = Img128<LB>::doubles;
+// TRIL as in gemm_tile (no 64-tile caller uses it: the skips cost more than they save there).
+template <int LA, int LB, int T, bool NEGA = false, bool TRIL = false>
+__device__ __forceinline__ void gemm_tile_glds(v4d (&acc)[T / 32][T / 32], const double* __restrict__ A, int64_t lda,
+                                               int64_t m0, const double* __restrict__ B, int64_t ldb, int64_t n0,
+                                               int64_t kbeg, int64_t kend, double* smem, int tid = threadIdx.x) {
+  constexpr int BK = 16, F = T / 32;
+  static_assert(has_glds_core<T, BK>, "no direct-to-LDS core for this tile");
+  constexpr int IA = ImgGlds<LA, T>::doubles, IB = ImgGlds<LB, T>::doubles;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = (wave >> 1) * 64;
-  const int wn = (wave & 1) * 64;
+  const int wm = (wave >> 1) * (T / 2);
+  const int wn = (wave & 1) * (T / 2);
   if (kend <= kbeg) return;
   auto stage = [&](int64_t k0, int b) {
     double* ia = smem + b * (IA + IB);
-    glds_stage128<LA>(A, lda, m0, k0, ia, wave, lane);
-    glds_stage128<LB>(B, ldb, n0, k0, ia + IA, wave, lane);
+    glds_stage<LA, T>(A, lda, m0, k0, ia, wave, lane);
+    glds_stage<LB, T>(B, ldb, n0, k0, ia + IA, wave, lane);
   };
-  double fa[2][4], fb[2][4];
-  auto frags = [&](double (&a)[4], double (&b)[4], const double* ia, int ks) {
+  double fa[2][F], fb[2][F];
+  auto frags = [&](double (&a)[F], double (&b)[F], const double* ia, int ks) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      a[s] = frag_read128<LA>(ia, wm, s, ks, lane);
-      if (NEGA) a[s] = -a[s];
-    }
+    for (int s = 0; s < F; ++s) a[s] = frag_read_glds<LA, T>(ia, wm, s, ks, lane);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) b[s] = frag_read128<LB>(ia + IA, wn, s, ks, lane);
+    for (int s = 0; s < F; ++s) b[s] = frag_read_glds<LB, T>(ia + IA, wn, s, ks, lane);
   };
   stage(kbeg, 0);
   __syncthreads();
@@ -384,14 +395,15 @@ __device__ __forceinline__ void gemm_tile128_glds(v4d (&acc)[4][4], const double
   auto kstep = [&](int64_t k0, auto in_c, int rel) {
     constexpr bool IN = decltype(in_c)::value;
     const bool more = (k0 + BK) < kend;
+    // (NEGA negates A in the MFMA phase, a sub-step after its read: negated where it is read, every sub-step would wait
+    // for the reads it has just issued)
     auto mfmas = [&](int ks) {
-      const double(&a)[4] = fa[ks & 1];
-      const double(&b)[4] = fb[ks & 1];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
+      for (int i = 0; i < F; ++i) {
         if (IN && rel + 4 * ks > wm + 16 * i + 15) continue;        // columns right of the fragment's rows: zeros
+        const double a = NEGA ? -fa[ks & 1][i] : fa[ks & 1][i];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < F; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, fb[ks & 1][j], acc[i][j], 0, 0, 0);
       }
     };
     stage(more ? k0 + BK : k0, buf ^ 1);
@@ -418,113 +430,25 @@ __device__ __forceinline__ void gemm_tile128_glds(v4d (&acc)[4][4], const double
     __builtin_amdgcn_sched_barrier(0);
     BOBE_STAMP(0);
   };
-  const int64_t kd = TRIL ? (kend - TM > kbeg ? kend - TM : kbeg) : kend;
+  const int64_t kd = TRIL ? (kend - T > kbeg ? kend - T : kbeg) : kend;        // start of the closing diagonal block
   for (int64_t k0 = kbeg; k0 < kd; k0 += BK) kstep(k0, std::false_type(), 0);
   if (TRIL)
-    for (int64_t k0 = kd; k0 < kend; k0 += BK) kstep(k0, std::true_type(), (int)(k0 - (kend - TM)));
+    for (int64_t k0 = kd; k0 < kend; k0 += BK) kstep(k0, std::true_type(), (int)(k0 - (kend - T)));
   BOBE_STAMPS_END(tid);
 }
 
-// ---- 64 x 64 tiles, BK = 16: the same loop as gemm_tile128_glds --------------------------------------------------------
-// The same MFMAs as gemm_tile<LA, LB, 64, 64, 16, NEGA> in the same order for every accumulator (same bits).  An operand tile
-// of 64 x 16 is eight wave-instructions of 1 KiB, two per wave.
-//   * KC: [64][16] unpadded, chunk c of row r at c ^ ((r >> 1) & 7) - the 128 image's layout and read, on 64 rows.
-//   * RC: a 64-wide k-row is only 512 B, so one instruction carries k-rows 2g and 2g + 1 and the row pad cannot be kept.
-//     The image is [16][64] with the chunks of every ODD k-row stored at c ^ 8 (element (k, r) at k * 64 + (r ^ 16 (k & 1)));
-//     the source address carries the permutation, the read applies it again.  A 32-lane ds_read_b64 group reads k-rows
-//     4 ks and 4 ks + 1 at 16 consecutive r from a multiple of 16: 32 dwords each, which the XOR puts in opposite halves of
-//     the 64 banks (unpadded, k-rows k and k + 1 are 128 dwords apart: the same 32 banks, a two-way conflict).
-// 32,768 B of LDS (two buffers of two 8 KiB images), within GEMM64_SMEM_BYTES and k_syrk_trail's SYRK64_SMEM, so the
-// launches keep their occupancy.  No TRIL variant (no 64-tile caller skips a diagonal block).
-constexpr int IMG64_DOUBLES = 64 * 16;
-constexpr int GEMM64_GLDS_SMEM_DOUBLES = 4 * IMG64_DOUBLES;
-static_assert(GEMM64_GLDS_SMEM_DOUBLES * 8 <= GEMM64_SMEM_BYTES, "the 64-tile LDS images must fit GEMM64_SMEM_BYTES");
-
-template <int L>
-__device__ __forceinline__ void glds_stage64(const double* __restrict__ p, int64_t ld, int64_t r0, int64_t k0, double* img,
-                                             int wave, int lane) {
-  const double* base = (L == KC) ? p + r0 * ld + k0 : p + k0 * ld + r0;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int g = wave + 4 * i;
-    unsigned off;
-    if (L == KC) {
-      const int r = 8 * g + (lane >> 3);
-      off = (unsigned)((r * ld + 2 * ((lane & 7) ^ ((r >> 1) & 7))) * 8);
-    } else {
-      const int h = lane >> 5;                                     // k-row 2 g + h, LDS chunk lane & 31
-      off = (unsigned)(((2 * g + h) * ld + 2 * ((lane & 31) ^ (8 * h))) * 8);
-    }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(img + 128 * g), 16, off, 0, 0, 0);
-  }
-}
-
-template <int L>
-__device__ __forceinline__ double frag_read64(const double* img, int woff, int s, int ks, int lane) {
-  if (L == KC) {
-    const int h = (lane >> 5) ^ ((lane & 15) >> 1);
-    return img[(woff + 16 * s + (lane & 15)) * 16 + 2 * ((2 * ks) ^ h) + ((lane >> 4) & 1)];
-  } else {
-    return img[(4 * ks + (lane >> 4)) * 64 + ((woff + 16 * s + (lane & 15)) ^ (((lane >> 4) & 1) << 4))];
-  }
-}
-
-template <int LA, int LB, bool NEGA = false>
-__device__ __forceinline__ void gemm_tile64_glds(v4d (&acc)[2][2], const double* __restrict__ A, int64_t lda, int64_t m0,
-                                                 const double* __restrict__ B, int64_t ldb, int64_t n0, int64_t kbeg,
-                                                 int64_t kend, double* smem, int tid = threadIdx.x) {
-  constexpr int BK = 16;
-  static_assert(BK64 == BK, "gemm_tile64_glds is the BK = 16 loop");
-  constexpr int IA = IMG64_DOUBLES, IB = IMG64_DOUBLES;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = (wave >> 1) * 32;
-  const int wn = (wave & 1) * 32;
-  if (kend <= kbeg) return;
-  auto stage = [&](int64_t k0, int b) {
-    double* ia = smem + b * (IA + IB);
-    glds_stage64<LA>(A, lda, m0, k0, ia, wave, lane);
-    glds_stage64<LB>(B, ldb, n0, k0, ia + IA, wave, lane);
-  };
-  double fa[2][2], fb[2][2];
-  auto frags = [&](double (&a)[2], double (&b)[2], const double* ia, int ks) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) a[s] = frag_read64<LA>(ia, wm, s, ks, lane);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) b[s] = frag_read64<LB>(ia + IA, wn, s, ks, lane);
-  };
-  // (NEGA negates A in the MFMA phase, a sub-step after its read: negated where it is read, every sub-step would wait
-  // for the reads it has just issued)
-  auto mfmas = [&](int ks) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const double a = NEGA ? -fa[ks & 1][i] : fa[ks & 1][i];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, fb[ks & 1][j], acc[i][j], 0, 0, 0);
-    }
-  };
-  stage(kbeg, 0);
-  __syncthreads();
-  frags(fa[0], fb[0], smem, 0);
-  int buf = 0;
-  for (int64_t k0 = kbeg; k0 < kend; k0 += BK) {
-    stage(k0 + BK < kend ? k0 + BK : k0, buf ^ 1);
-    const double* ia = smem + buf * (IA + IB);
-#pragma unroll
-    for (int ks = 0; ks < BK / 4 - 1; ++ks) {
-      frags(fa[(ks + 1) & 1], fb[(ks + 1) & 1], ia, ks + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(ks);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-    buf ^= 1;
-    frags(fa[0], fb[0], smem + buf * (IA + IB), 0);
-    __builtin_amdgcn_sched_barrier(0);
-    mfmas(BK / 4 - 1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+// ---- the one way to ask for a tile product: acc += A(m0.., k) * B(n0.., k), k in [kbeg, kend) ---------------------------
+// GLDS: take the direct-to-LDS core where the tile has one (has_glds_core), else - and with GLDS = false always - the
+// register-staged gemm_tile; the bits are the same either way.  smem: the launch's GEMM_SMEM_BYTES / GEMM64_SMEM_BYTES /
+// GEMM32_SMEM_BYTES serve both cores.
+template <bool GLDS, int LA, int LB, int T, bool NEGA = false, bool TRIL = false, int BK = TileCfg<T>::bk>
+__device__ __forceinline__ void tile_gemm(v4d (&acc)[T / 32][T / 32], const double* __restrict__ A, int64_t lda, int64_t m0,
+                                          const double* __restrict__ B, int64_t ldb, int64_t n0, int64_t kbeg, int64_t kend,
+                                          double* smem, int tid = threadIdx.x) {
+  if constexpr (GLDS && has_glds_core<T, BK>)
+    gemm_tile_glds<LA, LB, T, NEGA, TRIL>(acc, A, lda, m0, B, ldb, n0, kbeg, kend, smem, tid);
+  else
+    gemm_tile<LA, LB, T, T, BK, NEGA, TRIL>(acc, A, lda, m0, B, ldb, n0, kbeg, kend, smem, tid);
 }
 
 // Coordinates of accumulator element (i, j, r) of this lane inside the TM x TN tile.

@@ -593,21 +593,24 @@ int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const d
     hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, linv, Np, Np, scratch, Np,
                        bsL, bsS, B);
   }
-  const bool g64 = tuning().gemm64_glds;       // (the 64-tile core; no effect on TT = 128)
-#define LG(KE, DC, TT)                                                                                          \
-  hipLaunchKernelGGL((g64 ? k_lauum_grad<KE, DC, TT, TT == 64> : k_lauum_grad<KE, DC, TT, false>), dim3(ntiles * B), \
-                     dim3(256), (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst,   \
-                     Np, h, gpo, kio, Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK)
-#define LGD(KE, TT)                                                                 \
-  do {                                                                              \
-    if (dcap == 8) LG(KE, 8, TT); else if (dcap == 16) LG(KE, 16, TT); else LG(KE, 32, TT); \
+  // (BOBE_GEMM64_GLDS selects the core of the 64 x 64 tiles; the 128 x 128 ones are register-staged)
+#define LG(KE, DC, TT, GL)                                                                                            \
+  hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT, GL>), dim3(ntiles * B), dim3(256),                                     \
+                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst, Np, h, gpo, \
+                     kio, Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK)
+#define LGD(KE, TT, GL)                                                                                 \
+  do {                                                                                                  \
+    if (dcap == 8) LG(KE, 8, TT, GL); else if (dcap == 16) LG(KE, 16, TT, GL); else LG(KE, 32, TT, GL); \
   } while (0)
-  if (h.kern == 0) {
-    if (small) LGD(0, 64); else LGD(0, 128);
-  } else {
-    if (small) LGD(1, 64); else LGD(1, 128);
-  }
+#define LGT(KE)                                                          \
+  do {                                                                   \
+    if (!small) LGD(KE, 128, false);                                     \
+    else if (tuning().gemm64_glds) LGD(KE, 64, true);                    \
+    else LGD(KE, 64, false);                                             \
+  } while (0)
+  if (h.kern == 0) LGT(0); else LGT(1);
   prof_end(BOBE_PROF_LAUUM);
+#undef LGT
 #undef LGD
 #undef LG
   LAUNCH_CHECK();

@@ -127,9 +127,9 @@ void allow_big_lds(K kernel, int bytes) {
 //   BOBE_TRACE          print launch plans and batch timings to stderr
 //   BOBE_FACTOR_REUSE   0: bobe_gp_factor always factorises, never adopts an evaluation's factor (1; for A/B runs)
 //   BOBE_GEMM_GLDS      0: the sweep's 128-tile GEMMs (k_trimul, k_cross_vv<128>) take the register-staged tile core
-//                       instead of gemm_tile128_glds (1; for A/B runs)
+//                       instead of the direct-to-LDS one (tile_gemm's GLDS, gemm_f64.hpp; 1; for A/B runs)
 //   BOBE_GEMM64_GLDS    0: the 64-tile GEMMs (k_syrk_trail<64, 16>, k_trtri_T/R<64>, k_lauum_grad<., ., 64>, k_cross_vv<64>,
-//                       k_trimul_v64, k_trimul_t64) take the register-staged tile core instead of gemm_tile64_glds (1; A/B)
+//                       k_trimul_v64, k_trimul_t64, k_loo_grad<., ., 64>) likewise (1; A/B)
 struct Tuning {
   int syrk32_below, trtri64_below, pair_min, lockstep_min_n, mll_slots, graph_max_n, xcd_shares, fill;
   bool mll_slots_set, trace, factor_reuse, gemm_glds, gemm64_glds;

@@ -103,21 +103,24 @@ int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
     const bool small = nb * (nb + 1) / 2 < LAUUM64_BELOW;
     const int nt = small ? 2 * nb : nb;
     const int ntiles = nt * (nt + 1) / 2;
-    const bool g64 = tuning().gemm64_glds;
     prof_begin(BOBE_PROF_LAUUM);
-#define LG(KE, DC, TT)                                                                                                     \
-  hipLaunchKernelGGL((g64 ? k_loo_grad<KE, DC, TT, TT == 64> : k_loo_grad<KE, DC, TT, false>), dim3(ntiles), dim3(256),     \
-                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)A2.d(), Np, Np, N,           \
+    // (BOBE_GEMM64_GLDS selects the core of the 64 x 64 tiles; the 128 x 128 ones are register-staged: lauum's rule)
+#define LG(KE, DC, TT, GL)                                                                                             \
+  hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(ntiles), dim3(256),                                            \
+                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)A2.d(), Np, Np, N,      \
                      (const double*)alpha2.d(), (const double*)(ws + 6 * Np), (const double*)XsT2.d(), Np, h, gpart.d())
-#define LGD(KE, TT)                                                                         \
-  do {                                                                                      \
-    if (dcap == 8) LG(KE, 8, TT); else if (dcap == 16) LG(KE, 16, TT); else LG(KE, 32, TT); \
+#define LGD(KE, TT, GL)                                                                                 \
+  do {                                                                                                  \
+    if (dcap == 8) LG(KE, 8, TT, GL); else if (dcap == 16) LG(KE, 16, TT, GL); else LG(KE, 32, TT, GL); \
   } while (0)
-    if (h.kern == 0) {
-      if (small) LGD(0, 64); else LGD(0, 128);
-    } else {
-      if (small) LGD(1, 64); else LGD(1, 128);
-    }
+#define LGT(KE)                                                          \
+  do {                                                                   \
+    if (!small) LGD(KE, 128, false);                                     \
+    else if (tuning().gemm64_glds) LGD(KE, 64, true);                    \
+    else LGD(KE, 64, false);                                             \
+  } while (0)
+    if (h.kern == 0) LGT(0); else LGT(1);
+#undef LGT
 #undef LGD
 #undef LG
     prof_end(BOBE_PROF_LAUUM);

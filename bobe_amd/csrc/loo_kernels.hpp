@@ -112,7 +112,7 @@ static __global__ __launch_bounds__(256) void k_loo_make_b(const double* __restr
 // operand of k_lauum_grad);  W = 2 M = -2 G - (w alpha^T + alpha w^T) on the tile.
 // partial[tile * (DCAP + 1) + j] = sum_ab W_ab dK_ab / dlog ls_j (j < d), [DCAP] = sum_ab W_ab Kt_ab (Kt: without noise),
 // off-diagonal tiles weighted x2: the layout and the epilogue arithmetic of k_lauum_grad, reduced by k_mll_grad_reduce
-// (x 1/2).  One tile per workgroup, tile = blockIdx.x; GLDS (T = 64 only): gemm_tile64_glds.
+// (x 1/2).  One tile per workgroup, tile = blockIdx.x; GLDS: the tile core, as in k_lauum_grad.
 template <int KERN, int DCAP, int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_loo_grad(const double* __restrict__ B, int64_t ldb, int64_t np, int64_t n,
                                                      const double* __restrict__ alpha, const double* __restrict__ wv,
@@ -124,10 +124,7 @@ __global__ __launch_bounds__(256, 2) void k_loo_grad(const double* __restrict__ 
   tri_decode(tile, ti, tj);
   v4d acc[T / 32][T / 32];
   acc_zero(acc);
-  if constexpr (GLDS && T == 64)
-    gemm_tile64_glds<RC, RC>(acc, B, ldb, (int64_t)ti * T, B, ldb, (int64_t)tj * T, (int64_t)0, np, smem);
-  else
-    gemm_tile<RC, RC, T, T, TileCfg<T>::bk>(acc, B, ldb, (int64_t)ti * T, B, ldb, (int64_t)tj * T, (int64_t)0, np, smem);
+  tile_gemm<GLDS, RC, RC, T>(acc, B, ldb, (int64_t)ti * T, B, ldb, (int64_t)tj * T, (int64_t)0, np, smem);
   __syncthreads();                    // (every wave is through with the GEMM's LDS images)
   double* xa = smem;                  // [d][T]
   double* xb = smem + MAX_D * T;      // [d][T]

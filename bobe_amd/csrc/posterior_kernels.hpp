@@ -9,7 +9,7 @@ namespace bobe {
 // ---- Sigma[i][j] = k(q_i, q_j) + noise [i = j] - V_i . V_j,   V = L^-1 K(X, Q) (Np x ldv, column c = query c) ----------
 // One workgroup = one 128 x 128 tile of the LOWER triangle.  Its rows are queries i0 + 128 ti + [0, 128) of the column chunk VI,
 // its columns queries j0 + 128 tj + [0, 128) of VJ.  diag = 1 (VI and VJ are the same chunk): the ntI (ntI + 1) / 2 tile pairs
-// tj <= ti; else every tile of the ntI x ntJ block.  The product runs on the sweep's 128-tile core (gemm_tile128_glds, RC x RC
+// tj <= ti; else every tile of the ntI x ntJ block.  The product runs on the sweep's 128-tile core (direct-to-LDS, RC x RC
 // like k_cross_vv) over the whole padded K = Np: V's padded rows are 0.  The epilogue stages the tile's scaled coordinates
 // (QsT[j * ldq + c] = q_cj / ls_j, d x 128 for the rows and for the columns) in the LDS the product is done with, evaluates
 // k(q_i, q_j) as the kernel-matrix assembly does (fma over the dimensions; kvar + noise on the diagonal, the kself of
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256, 2) void k_sigma_tiles(const double* __restrict
   }
   v4d acc[4][4];
   acc_zero(acc);
-  gemm_tile128_glds<RC, RC>(acc, VI, ldv, (int64_t)ti * TILE, VJ, ldv, (int64_t)tj * TILE, 0, kend, smem);
+  tile_gemm<true, RC, RC, TILE>(acc, VI, ldv, (int64_t)ti * TILE, VJ, ldv, (int64_t)tj * TILE, 0, kend, smem);
   const int64_t gi0 = i0 + (int64_t)ti * TILE, gj0 = j0 + (int64_t)tj * TILE;
   double* qa = smem;                       // [d][128] rows
   double* qb = smem + MAX_D * TILE;        // [d][128] columns   (2 x 32 x 128 doubles <= GEMM_SMEM_DOUBLES)
@@ -110,8 +110,8 @@ __global__ __launch_bounds__(256, 2) void k_trmm_draws(const double* __restrict_
   const int tc = nbC - 1 - (int)blockIdx.y;
   v4d acc[4][4];
   acc_zero(acc);
-  gemm_tile128_glds<KC, RC, false, true>(acc, L, ldl, (int64_t)tc * TILE, Zt, ldz, (int64_t)ts * TILE, 0,
-                                         (int64_t)(tc + 1) * TILE, smem);
+  tile_gemm<true, KC, RC, TILE, false, true>(acc, L, ldl, (int64_t)tc * TILE, Zt, ldz, (int64_t)ts * TILE, 0,
+                                             (int64_t)(tc + 1) * TILE, smem);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll

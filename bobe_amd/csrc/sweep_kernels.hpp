@@ -4,6 +4,29 @@
 
 namespace bobe {
 
+// out[c] = the sum of squares of column c of the workgroup's T x T accumulator tile, c < T.  The association is fixed
+// (k_colsq_tile_parts restates it and must give the same bits): per 16-column fragment the sum over i, then r; lanes
+// xor 16, then 32; the two T/2-row halves through LDS (smem: 2 T doubles, free once the tile's product is done), half 0 +
+// half 1.  All 256 threads must call.
+template <int T>
+__device__ __forceinline__ void tile_colsq(const v4d (&acc)[T / 32][T / 32], double* smem, double* out) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  double* red = smem;  // [2][T]
+#pragma unroll
+  for (int j = 0; j < T / 32; ++j) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < T / 32; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    if (lane < 16) red[(wave >> 1) * T + (wave & 1) * (T / 2) + 16 * j + lane] = s;
+  }
+  __syncthreads();
+  if (t < T) out[t] = red[t] + red[T + t];
+}
+
 // ---- the sweep's one big GEMM launch ------------------------------------------------------------
 // grid.x = column (candidate) tile; grid.y enumerates row tiles, heaviest first:
 //   y <  nzt : cross tile   G[z][c]  = sum_n  VZ[n][z] Bx[n][c]     (full K)   -> crossT (optional, nzt may be 0)
@@ -14,7 +37,7 @@ namespace bobe {
 // solves the next chunk, where their full-K tiles fill the tails of the triangular ones, instead of a launch of their own
 // (2.62 ms per chunk of 8192 candidates at N = 4096, M = 512 against 2.17 + 0.59).  ncv / ncx: column tiles of the two
 // parts (the grid spans the larger; a chunk's last tiles may be missing in one of them).
-// GLDS: the tile core (gemm_f64.hpp): gemm_tile128_glds (true, the default) or the register-staged gemm_tile - same bits
+// GLDS: the tile core (gemm_f64.hpp, tile_gemm): direct-to-LDS (true, the default) or register-staged - same bits
 // (BOBE_GEMM_GLDS, gp_handle.hpp).
 template <bool GLDS>
 __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Linv, int64_t ldi, int nb,
@@ -34,10 +57,7 @@ __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Li
   if ((int)blockIdx.y < nzt) {
     if (tc >= ncx) return;
     const int tz = blockIdx.y;
-    if constexpr (GLDS)
-      gemm_tile128_glds<RC, RC>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
-    else
-      gemm_tile<RC, RC>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
+    tile_gemm<GLDS, RC, RC, TILE>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
     store_tile(acc, crossT, ldx, (int64_t)tz * TILE, (int64_t)tc * TILE, 1.0, 0.0);
     return;
   }
@@ -45,30 +65,10 @@ __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Li
   const int ti = nb - 1 - ((int)blockIdx.y - nzt);
   // (the K range of a row tile ends with its diagonal block of the lower-triangular Linv: the zeros above the diagonal are
   // skipped, 1.2 % of the launch)
-  if constexpr (GLDS)
-    gemm_tile128_glds<KC, RC, false, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE, 0,
-                                           (int64_t)(ti + 1) * TILE, smem);
-  else
-    gemm_tile<KC, RC, TILE, TILE, BK128, false, WgSync, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE,
-                                                              0, (int64_t)(ti + 1) * TILE, smem);
+  tile_gemm<GLDS, KC, RC, TILE, false, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE, 0,
+                                             (int64_t)(ti + 1) * TILE, smem);
   if (V) store_tile(acc, V, ldv, (int64_t)ti * TILE, (int64_t)tc * TILE, 1.0, 0.0);
-  if (qpart) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    double* red = smem;  // [2][128]
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      if (lane < 16) red[(wave >> 1) * TILE + (wave & 1) * 64 + 16 * j + lane] = s;
-    }
-    __syncthreads();
-    if (t < TILE) qpart[(int64_t)ti * ldq + (int64_t)tc * TILE + t] = red[t] + red[TILE + t];
-  }
+  if (qpart) tile_colsq<TILE>(acc, smem, qpart + (int64_t)ti * ldq + (int64_t)tc * TILE);
 }
 
 // ---- V = L^-1 B as a BLOCKED FORWARD SUBSTITUTION (the reference's solve_triangular, gp.py:462, 484, 571) -----------------
@@ -104,32 +104,16 @@ __global__ __launch_bounds__(256, 2) void k_blk_step(const double* __restrict__ 
   acc_zero(acc);
   if ((int)blockIdx.y < u_rows) {
     const int ti = u_r0 + (int)blockIdx.y;
-    gemm_tile<KC, RC>(acc, L, ld, (int64_t)ti * TILE, V, ldv, (int64_t)tc * TILE, (int64_t)u_k0 * TILE,
-                      (int64_t)u_k1 * TILE, smem);
+    tile_gemm<false, KC, RC, TILE>(acc, L, ld, (int64_t)ti * TILE, V, ldv, (int64_t)tc * TILE, (int64_t)u_k0 * TILE,
+                                   (int64_t)u_k1 * TILE, smem);
     store_tile(acc, B, ldb, (int64_t)ti * TILE, (int64_t)tc * TILE, -1.0, 1.0);
     return;
   }
   const int ti = s_r0 + s_rows - 1 - ((int)blockIdx.y - u_rows);
-  gemm_tile<KC, RC, TILE, TILE, BK128, false, WgSync, true>(acc, Linv, ld, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE,
-                                                            (int64_t)s_r0 * TILE, (int64_t)(ti + 1) * TILE, smem);
+  tile_gemm<false, KC, RC, TILE, false, true>(acc, Linv, ld, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE,
+                                              (int64_t)s_r0 * TILE, (int64_t)(ti + 1) * TILE, smem);
   store_tile(acc, V, ldv, (int64_t)ti * TILE, (int64_t)tc * TILE, 1.0, 0.0);
-  if (qpart) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    double* red = smem;  // [2][128]
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      if (lane < 16) red[(wave >> 1) * TILE + (wave & 1) * 64 + 16 * j + lane] = s;
-    }
-    __syncthreads();
-    if (t < TILE) qpart[(int64_t)ti * ldq + (int64_t)tc * TILE + t] = red[t] + red[TILE + t];
-  }
+  if (qpart) tile_colsq<TILE>(acc, smem, qpart + (int64_t)ti * ldq + (int64_t)tc * TILE);
 }
 
 // v[c*ldv + i] += dv[c*ldv + i]  /  r[c*ldv + i] = k[c*ldv + i] - lv[c*ldv + i]   (the vector forms of the same step)
@@ -180,7 +164,7 @@ __global__ __launch_bounds__(256) void k_colsq_tile_parts(const double* __restri
 // scores came out 1e-2 ... 1 (relative) off an extended-precision evaluation where the triangular-solve form is 1e-4 ...
 // 1e-1 off (profiles/r05_conditioning.txt, tests/test_gpu_conditioning.py).  Same 2 N M flops per candidate.
 // T = 128: grid (ncols / 128, Mp / 128); T = 64: grid (ncols / 64, Mp / 64) - few integration points fill the chip only
-// with the small tile.  GLDS: the 128-tile core as in k_trimul (T = 128) or gemm_tile64_glds (T = 64; BOBE_GEMM64_GLDS).
+// with the small tile.  GLDS: the tile core as in k_trimul (T = 128: BOBE_GEMM_GLDS, T = 64: BOBE_GEMM64_GLDS).
 template <int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ VZ, int64_t ldz,
                                                      const double* __restrict__ V, int64_t ldv, int64_t kend,
@@ -189,19 +173,8 @@ __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ 
   const int tc = blockIdx.x, tz = blockIdx.y;
   v4d acc[T / 32][T / 32];
   acc_zero(acc);
-  if constexpr (T == 128) {
-    if constexpr (GLDS)
-      gemm_tile128_glds<RC, RC>(acc, VZ, ldz, (int64_t)tz * TILE, V, ldv, (int64_t)tc * TILE, 0, kend, smem);
-    else
-      gemm_tile<RC, RC>(acc, VZ, ldz, (int64_t)tz * TILE, V, ldv, (int64_t)tc * TILE, 0, kend, smem);
-    store_tile(acc, crossT, ldx, (int64_t)tz * TILE, (int64_t)tc * TILE, 1.0, 0.0);
-  } else {
-    if constexpr (GLDS)
-      gemm_tile64_glds<RC, RC>(acc, VZ, ldz, (int64_t)tz * 64, V, ldv, (int64_t)tc * 64, 0, kend, smem);
-    else
-      gemm_tile<RC, RC, 64, 64, BK64>(acc, VZ, ldz, (int64_t)tz * 64, V, ldv, (int64_t)tc * 64, 0, kend, smem);
-    store_tile<64, 64>(acc, crossT, ldx, (int64_t)tz * 64, (int64_t)tc * 64, 1.0, 0.0);
-  }
+  tile_gemm<GLDS, RC, RC, T>(acc, VZ, ldz, (int64_t)tz * T, V, ldv, (int64_t)tc * T, 0, kend, smem);
+  store_tile<T, T>(acc, crossT, ldx, (int64_t)tz * T, (int64_t)tc * T, 1.0, 0.0);
 }
 
 // ---- W = Linv^T * V  (upper-triangular times dense):  W[m][z] = sum_{k >= m} Linv[k][m] V[k][z]
@@ -213,15 +186,15 @@ __global__ __launch_bounds__(256, 2) void k_trimul_t(const double* __restrict__ 
   const int tc = blockIdx.x;
   v4d acc[4][4];
   acc_zero(acc);
-  gemm_tile<RC, RC>(acc, Linv, ldi, (int64_t)ti * TILE, V, ldv, (int64_t)tc * TILE, (int64_t)ti * TILE,
-                    (int64_t)nb * TILE, smem);
+  tile_gemm<false, RC, RC, TILE>(acc, Linv, ldi, (int64_t)ti * TILE, V, ldv, (int64_t)tc * TILE, (int64_t)ti * TILE,
+                                 (int64_t)nb * TILE, smem);
   store_tile(acc, W, ldw, (int64_t)ti * TILE, (int64_t)tc * TILE, 1.0, 0.0);
 }
 
 // ---- the same two products on 64 x 64 tiles, for right-hand sides with FEW columns (the M = 512 integration points of a
 // sweep: 4 x nb tiles of 128 x 128 leave half the chip idle for two launches of ~0.57 ms each at N = 4096; 8 x 2nb tiles
 // of 64 x 64 fill it).  V = Linv B with the column sums of squares per 64-row tile (qpart[2 nb][.]), W = Linv^T V.
-// GLDS: gemm_tile64_glds or the register-staged gemm_tile (BOBE_GEMM64_GLDS).
+// GLDS: the tile core, direct-to-LDS or register-staged (BOBE_GEMM64_GLDS).
 template <bool GLDS>
 __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict__ Linv, int64_t ldi, int nt,
                                                        const double* __restrict__ B, int64_t ldb, double* __restrict__ V,
@@ -231,27 +204,9 @@ __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict_
   const int ti = nt - 1 - (int)blockIdx.y;                      // long K first
   v4d acc[2][2];
   acc_zero(acc);
-  if constexpr (GLDS)
-    gemm_tile64_glds<KC, RC>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64, smem);
-  else
-    gemm_tile<KC, RC, 64, 64, BK64>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64,
-                                    smem);
+  tile_gemm<GLDS, KC, RC, 64>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64, smem);
   store_tile<64, 64>(acc, V, ldv, (int64_t)ti * 64, (int64_t)tc * 64, 1.0, 0.0);
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  double* red = smem;  // [2][64]
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s += acc[i][j][r] * acc[i][j][r];
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    if (lane < 16) red[(wave >> 1) * 64 + (wave & 1) * 32 + 16 * j + lane] = s;
-  }
-  __syncthreads();
-  if (t < 64) qpart[(int64_t)ti * ldq + (int64_t)tc * 64 + t] = red[t] + red[64 + t];
+  tile_colsq<64>(acc, smem, qpart + (int64_t)ti * ldq + (int64_t)tc * 64);
 }
 
 template <bool GLDS>
@@ -263,12 +218,8 @@ __global__ __launch_bounds__(256, 2) void k_trimul_t64(const double* __restrict_
   const int tc = blockIdx.x;
   v4d acc[2][2];
   acc_zero(acc);
-  if constexpr (GLDS)
-    gemm_tile64_glds<RC, RC>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64, (int64_t)nt * 64,
-                             smem);
-  else
-    gemm_tile<RC, RC, 64, 64, BK64>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64,
-                                    (int64_t)nt * 64, smem);
+  tile_gemm<GLDS, RC, RC, 64>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64, (int64_t)nt * 64,
+                              smem);
   store_tile<64, 64>(acc, W, ldw, (int64_t)ti * 64, (int64_t)tc * 64, 1.0, 0.0);
 }
 

@@ -103,7 +103,7 @@ int main(int argc, char** argv) {
   std::printf("{\"loop\": \"%s\", \"stamped_ms_per_launch\": %.4f, \"waves\": %zu, \"clock_ghz_median\": %.4f, "
               "\"clock_ghz_p10\": %.4f, \"clock_ghz_p90\": %.4f, \"cycles_per_kstep\": {\"first_fragment_wait\": %.1f, "
               "\"mfma_body\": %.1f, \"staging_wait\": %.1f, \"barrier\": %.1f, \"loop_total\": %.1f}}\n",
-              glds ? "gemm_tile128_glds" : "gemm_tile (register-staged)", ms, clk.size(), med,
+              glds ? "gemm_tile_glds<128>" : "gemm_tile (register-staged)", ms, clk.size(), med,
               clk.empty() ? 0.0 : clk[clk.size() / 10], clk.empty() ? 0.0 : clk[clk.size() * 9 / 10], seg[0] / steps,
               seg[1] / steps, seg[2] / steps, seg[3] / steps, loop / steps);
   return 0;

@@ -1,6 +1,6 @@
 // Tile-GEMM core per tile/BK variant: per-tile latency at K = 128 (the Cholesky trailing-update shape) and
-// steady-state throughput at K = 4096 (the sweep's shape).  "+glds": the direct-to-LDS cores (gemm_tile64_glds,
-// gemm_tile128_glds) on the same KC x KC shape.
+// steady-state throughput at K = 4096 (the sweep's shape).  "+glds": the direct-to-LDS core (gemm_tile_glds, through
+// tile_gemm) on the same KC x KC shape.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -o tools/bin/ubench_gemm tools/ubench_gemm.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -17,12 +17,8 @@ __global__ __launch_bounds__(256, GLDS ? 2 : 1) void k_t(const double* __restric
   unsigned long long t0 = __builtin_amdgcn_s_memtime();
   v4d acc[T / 32][T / 32];
   acc_zero(acc);
-  if constexpr (GLDS && T == 64)
-    gemm_tile64_glds<KC, KC>(acc, A, lda, (int64_t)ty * T, A, lda, (int64_t)tx * T, 0, K, smem);
-  else if constexpr (GLDS)
-    gemm_tile128_glds<KC, KC>(acc, A, lda, (int64_t)ty * T, A, lda, (int64_t)tx * T, 0, K, smem);
-  else
-    gemm_tile<KC, KC, T, T, BK>(acc, A, lda, (int64_t)ty * T, A, lda, (int64_t)tx * T, 0, K, smem);
+  static_assert(!GLDS || has_glds_core<T, BK>, "no direct-to-LDS core for this tile and K-step");
+  tile_gemm<GLDS, KC, KC, T, false, false, BK>(acc, A, lda, (int64_t)ty * T, A, lda, (int64_t)tx * T, 0, K, smem);
   unsigned long long t1 = __builtin_amdgcn_s_memtime();
   store_tile<T, T>(acc, C, ldc, (int64_t)ty * T, (int64_t)tx * T, 1.0, 0.0);
   unsigned long long t2 = __builtin_amdgcn_s_memtime();
