@@ -31,14 +31,11 @@ __global__ __launch_bounds__(256, 2) void k_debug_gemm(const double* __restrict_
 
 void configure_debug_kernels() {
   static bool done[64] = {false};
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || done[dev]) return;
+  if (!first_use_on_device(done)) return;
   allow_big_lds(k_debug_gemm<0, 0>, GEMM_SMEM_BYTES);
   allow_big_lds(k_debug_gemm<0, 1>, GEMM_SMEM_BYTES);
   allow_big_lds(k_debug_gemm<1, 0>, GEMM_SMEM_BYTES);
   allow_big_lds(k_debug_gemm<1, 1>, GEMM_SMEM_BYTES);
-  done[dev] = true;
 }
 
 }  // namespace
@@ -261,8 +258,12 @@ int bobe_gp_predict(bobe_gp_t* g, const double* Xq, int64_t C, double* mean, dou
   API_BEGIN
   NEED(g && Xq, "NULL argument");
   g->use();
-  g->sweep(Xq, C, nullptr, 0, 1.0, nullptr, nullptr, mean, var, nan_policy ? 1 : 0, nullptr, nullptr, nullptr, nullptr,
-           nullptr, true);
+  SweepReq r;
+  r.cand = Xq; r.C = C;
+  r.mean = mean; r.var = var;
+  r.policy = nan_policy ? 1 : 0;
+  r.gated = true;
+  g->sweep(r);
   return BOBE_OK;
   API_END
 }
@@ -273,7 +274,11 @@ int bobe_gp_wip_sweep(bobe_gp_t* g, const double* cand, int64_t C, const double*
   API_BEGIN
   NEED(g && cand && Z, "NULL argument");
   g->use();
-  g->sweep(cand, C, Z, M, y_std, wipv, wipstd, mean, var, 1, argmin_v, min_v, argmin_s, min_s, nullptr);
+  SweepReq r;
+  r.cand = cand; r.C = C; r.Z = Z; r.M = M; r.y_std = y_std;
+  r.wipv = wipv; r.wipstd = wipstd; r.mean = mean; r.var = var;
+  r.argmin_v = argmin_v; r.min_v = min_v; r.argmin_s = argmin_s; r.min_s = min_s;
+  g->sweep(r);
   return BOBE_OK;
   API_END
 }
@@ -291,7 +296,10 @@ int bobe_gp_fantasy_var(bobe_gp_t* g, const double* cand, int64_t C, const doubl
   API_BEGIN
   NEED(g && cand && Z && out, "NULL argument");
   g->use();
-  g->sweep(cand, C, Z, M, y_std, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, out);
+  SweepReq r;
+  r.cand = cand; r.C = C; r.Z = Z; r.M = M; r.y_std = y_std;
+  r.fantasy_out = out;
+  g->sweep(r);
   return BOBE_OK;
   API_END
 }
@@ -799,7 +807,11 @@ int bobe_mgpu_wip_sweep(bobe_gp_t* g, const double* cand, int64_t C, int64_t glo
   if (C > 0) {
     try {
       g->use();
-      g->sweep(cand, C, Z, M, y_std, wipv, wipstd, mean, var, 1, &lv, &mv, &ls, &msd, nullptr);
+      SweepReq r;
+      r.cand = cand; r.C = C; r.Z = Z; r.M = M; r.y_std = y_std;
+      r.wipv = wipv; r.wipstd = wipstd; r.mean = mean; r.var = var;
+      r.argmin_v = &lv; r.min_v = &mv; r.argmin_s = &ls; r.min_s = &msd;
+      g->sweep(r);
       lv += global_offset;
       ls += global_offset;
     } catch (const Err& e) {

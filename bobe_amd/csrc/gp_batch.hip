@@ -61,9 +61,13 @@ int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, in
   keep.ld = Cp;
   int64_t pick0 = -1;
   double val0 = 0.0;
-  sweep(cand, C, Z, M, y_std, wipv ? stage_row(0) : nullptr, wipv ? nullptr : stage_row(0), nullptr, nullptr, 1,
-        wipv ? &pick0 : nullptr, wipv ? &val0 : nullptr, wipv ? nullptr : &pick0, wipv ? nullptr : &val0, nullptr, false,
-        &keep);                                          // (synchronises: pick0 / val0 are on the host)
+  SweepReq rq;
+  rq.cand = cand; rq.C = C; rq.Z = Z; rq.M = M; rq.y_std = y_std;
+  (wipv ? rq.wipv : rq.wipstd) = stage_row(0);
+  (wipv ? rq.argmin_v : rq.argmin_s) = &pick0;
+  (wipv ? rq.min_v : rq.min_s) = &val0;
+  rq.keep = &keep;
+  sweep(rq);                                             // (synchronises: pick0 / val0 are on the host)
   HIPCHK(hipMemcpyAsync(d_picks, &pick0, sizeof(int64_t), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dval.p, &val0, sizeof(double), hipMemcpyHostToDevice, stream));
 

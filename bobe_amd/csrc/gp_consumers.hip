@@ -10,16 +10,12 @@ using namespace bobe;
 namespace bobe {
 void configure_consumer_kernels() {       // (the chain kernels keep training points in up to 150 KB of LDS)
   static bool done[64] = {false};
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || done[dev]) return;
-#define BIG(KE, DC)                                         \
-  allow_big_lds((k_hmc_run<KE, DC>), CHAIN_LDS_BYTES);      \
-  allow_big_lds((k_rwalk<KE, DC>), CHAIN_LDS_BYTES);        \
-  allow_big_lds((k_nuts_run<KE, DC>), NUTS_LDS_BYTES)
-  BIG(0, 8); BIG(0, 16); BIG(0, 32); BIG(1, 8); BIG(1, 16); BIG(1, 32);
-#undef BIG
-  done[dev] = true;
+  if (!first_use_on_device(done)) return;
+  for_each_kern_dcap([](auto KE, auto DC) {
+    allow_big_lds((k_hmc_run<KE, DC>), CHAIN_LDS_BYTES);
+    allow_big_lds((k_rwalk<KE, DC>), CHAIN_LDS_BYTES);
+    allow_big_lds((k_nuts_run<KE, DC>), NUTS_LDS_BYTES);
+  });
 }
 }  // namespace bobe
 
@@ -113,12 +109,10 @@ void bobe_gp::train_ellipsoid(const double* X, const double* yv, int64_t N, cons
 void bobe_gp::gate_apply(const double* xq_dev, int64_t C, double* decision, double* feasible, double* mean, double* var,
                          double* dmean, double* dvar, double* proba) {
   if (!gate_on(gate)) throw Err(BOBE_ERR_STATE, "no classifier gate is set (bobe_gp_set_gate)");
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-#define GT(DC) \
-  hipLaunchKernelGGL((k_gate<DC>), dim3((unsigned)C), dim3(256), 0, stream, gate, xq_dev, d, decision, feasible, mean, var, dmean, dvar, \
-                     proba)
-  if (dcap == 8) GT(8); else if (dcap == 16) GT(16); else GT(32);
-#undef GT
+  with_dcap(d, [&](auto DC) {
+    hipLaunchKernelGGL((k_gate<DC>), dim3((unsigned)C), dim3(256), 0, stream, gate, xq_dev, d, decision, feasible, mean, var,
+                       dmean, dvar, proba);
+  });
   LAUNCH_CHECK();
 }
 
@@ -149,7 +143,11 @@ void bobe_gp::acq_ei(const double* Xq, int64_t C, double best_y, double zeta, in
   o_mean.ensure(C * sizeof(double));
   o_var.ensure(C * sizeof(double));
   // (predict_single, acquisition.py:246 / 323: gated for a GPwithClassifier)
-  sweep(Xq, C, nullptr, 0, 1.0, nullptr, nullptr, o_mean.d(), o_var.d(), 1, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+  SweepReq rq;
+  rq.cand = Xq; rq.C = C;
+  rq.mean = o_mean.d(); rq.var = o_var.d();
+  rq.gated = true;
+  sweep(rq);
   double* d_out = out_dev(out, C, o_wipv);
   hipLaunchKernelGGL(k_ei, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, (const double*)o_mean.d(),
                      (const double*)o_var.d(), C, best_y, zeta, mode, d_out, gate.minus_inf);
@@ -180,17 +178,11 @@ void bobe_gp::hmc_leapfrog(int64_t P, double* U, double* Pm, const double* inv_m
   HIPCHK(hipMemcpyAsync(dP, Pm, pd * sizeof(double), in, stream));
   HIPCHK(hipMemcpyAsync(dI, inv_mass, (size_t)d * sizeof(double), is_device_ptr(inv_mass) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                         stream));
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-#define HL(KE, DC)                                                                                                   \
-  hipLaunchKernelGGL((k_hmc_leapfrog<KE, DC>), dim3((unsigned)P), dim3(256), 0, stream, (const double*)XsT.d(),   \
-                     Np, N, (const double*)alpha.d(), hyp, dU, dP, (const double*)dI, eps, L, y_std, y_mean, \
-                     temp, dL, dG, dM, dX, gate)
-  if (hyp.kern == 0) {
-    if (dcap == 8) HL(0, 8); else if (dcap == 16) HL(0, 16); else HL(0, 32);
-  } else {
-    if (dcap == 8) HL(1, 8); else if (dcap == 16) HL(1, 16); else HL(1, 32);
-  }
-#undef HL
+  with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+    hipLaunchKernelGGL((k_hmc_leapfrog<KE, DC>), dim3((unsigned)P), dim3(256), 0, stream, (const double*)XsT.d(), Np, N,
+                       (const double*)alpha.d(), hyp, dU, dP, (const double*)dI, eps, L, y_std, y_mean, temp, dL, dG, dM, dX,
+                       gate);
+  });
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(U, dU, pd * sizeof(double), out, stream));
   HIPCHK(hipMemcpyAsync(Pm, dP, pd * sizeof(double), out, stream));
@@ -223,22 +215,14 @@ void bobe_gp::hmc_run(int64_t P, double* state, double* adapt, const double* inv
   HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dI, inv_mass, (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream));
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
   // training points of a chain's workgroup: registers first, then LDS (chain_lds_groups), the rest streamed
-#define HR(KE, DC)                                                                                                  \
-  do {                                                                                                              \
-    const int lg = chain_lds_groups(N, d, ChainRows<DC>::HMC);                                                      \
-    hipLaunchKernelGGL((k_hmc_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double), \
-                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA,             \
-                       (const double*)dI, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp,      \
-                       hist_from, hist ? dH : nullptr, thin, keep ? dK : nullptr, dbg ? dD : nullptr, gate, lg);    \
-  } while (0)
-  if (hyp.kern == 0) {
-    if (dcap == 8) HR(0, 8); else if (dcap == 16) HR(0, 16); else HR(0, 32);
-  } else {
-    if (dcap == 8) HR(1, 8); else if (dcap == 16) HR(1, 16); else HR(1, 32);
-  }
-#undef HR
+  with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+    const int lg = chain_lds_groups(N, d, ChainRows<DC>::HMC);
+    hipLaunchKernelGGL((k_hmc_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
+                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA, (const double*)dI,
+                       (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from, hist ? dH : nullptr,
+                       thin, keep ? dK : nullptr, dbg ? dD : nullptr, gate, lg);
+  });
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -320,22 +304,13 @@ void bobe_gp::nuts_run(int64_t P, double* state, double* adapt, const double* in
   HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dM, met.data(), nm * sizeof(double), hipMemcpyHostToDevice, stream));
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-#define HN(KE, DC)                                                                                                  \
-  do {                                                                                                              \
-    const int lg = chain_lds_groups(N, d, ChainRows<DC>::NUTS, NUTS_LDS_BYTES);                                      \
-    hipLaunchKernelGGL((k_nuts_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double), \
-                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA,             \
-                       (const double*)dM, max_depth, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, \
-                       temp, hist_from, hist ? dH : nullptr, thin, keep ? dK : nullptr, stats ? dT : nullptr,       \
-                       dbg ? dD : nullptr, gate, lg);                                                               \
-  } while (0)
-  if (hyp.kern == 0) {
-    if (dcap == 8) HN(0, 8); else if (dcap == 16) HN(0, 16); else HN(0, 32);
-  } else {
-    if (dcap == 8) HN(1, 8); else if (dcap == 16) HN(1, 16); else HN(1, 32);
-  }
-#undef HN
+  with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+    const int lg = chain_lds_groups(N, d, ChainRows<DC>::NUTS, NUTS_LDS_BYTES);
+    hipLaunchKernelGGL((k_nuts_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
+                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA, (const double*)dM,
+                       max_depth, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from,
+                       hist ? dH : nullptr, thin, keep ? dK : nullptr, stats ? dT : nullptr, dbg ? dD : nullptr, gate, lg);
+  });
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -363,21 +338,12 @@ void bobe_gp::rwalk(int64_t P, double* Xw, double* logl, const double* step, dou
   HIPCHK(hipMemcpyAsync(dX, Xw, pd * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dL, logl, (size_t)P * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(dS, step, (size_t)d * d * sizeof(double), hipMemcpyHostToDevice, stream));
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-#define RW(KE, DC)                                                                                                 \
-  do {                                                                                                             \
-    const int lg = chain_lds_groups(N, d, ChainRows<DC>::WALK);                                                    \
-    hipLaunchKernelGGL((k_rwalk<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double), \
-                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, dX, dL,               \
-                       (const double*)dS, lstar, walks, (unsigned long long)seed, y_std, y_mean, dA, dN,           \
-                       dbg ? dD : nullptr, gate, lg);                                                              \
-  } while (0)
-  if (hyp.kern == 0) {
-    if (dcap == 8) RW(0, 8); else if (dcap == 16) RW(0, 16); else RW(0, 32);
-  } else {
-    if (dcap == 8) RW(1, 8); else if (dcap == 16) RW(1, 16); else RW(1, 32);
-  }
-#undef RW
+  with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+    const int lg = chain_lds_groups(N, d, ChainRows<DC>::WALK);
+    hipLaunchKernelGGL((k_rwalk<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
+                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, dX, dL, (const double*)dS,
+                       lstar, walks, (unsigned long long)seed, y_std, y_mean, dA, dN, dbg ? dD : nullptr, gate, lg);
+  });
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(Xw, dX, pd * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(logl, dL, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, stream));

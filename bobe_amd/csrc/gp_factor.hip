@@ -17,9 +17,7 @@ constexpr int SYRK64_SMEM = gemm_smem_doubles_exact<KC, KC, 64, 64, SYRK64_BK>()
 
 void configure_factor_kernels() {
   static bool done[64] = {false};
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || done[dev]) return;
+  if (!first_use_on_device(done)) return;
   allow_big_lds(k_potf2<true>, POTF2_SMEM_BYTES);
   allow_big_lds(k_potf2<false>, POTF2_SMEM_BYTES);
   allow_big_lds(k_trti_diag, POTF2_SMEM_BYTES);
@@ -40,25 +38,11 @@ void configure_factor_kernels() {
   allow_big_lds(k_trtri_T<32>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_trtri_R<32>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_lauum_tiles32, GEMM32_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 8, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 16, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 32, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 8, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 16, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 32, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 8, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 16, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 32, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 8, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 16, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 32, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 8, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 16, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<0, 32, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 8, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 16, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_lauum_grad<1, 32, 128>, GEMM_SMEM_BYTES);
-  done[dev] = true;
+  for_each_kern_dcap([](auto KE, auto DC) {
+    allow_big_lds((k_lauum_grad<KE, DC, 64>), GEMM64_SMEM_BYTES);
+    allow_big_lds((k_lauum_grad<KE, DC, 64, true>), GEMM64_SMEM_BYTES);
+    allow_big_lds((k_lauum_grad<KE, DC, 128>), GEMM_SMEM_BYTES);
+  });
 }
 
 const Tuning& tuning() {
@@ -206,37 +190,26 @@ void bobe_gp::scale(const double* in, int64_t n, int64_t npad, const Hyper& h, d
   LAUNCH_CHECK();
 }
 
-#define KM_LAUNCH(KE, SQ, DC, grid, ...)                                                                 \
-  do {                                                                                                   \
-    if (h.d == DC)                                                                                       \
-      hipLaunchKernelGGL((k_kernel_matrix<KE, SQ, DC, true>), grid, dim3(256), 0, stream, __VA_ARGS__);  \
-    else                                                                                                 \
-      hipLaunchKernelGGL((k_kernel_matrix<KE, SQ, DC, false>), grid, dim3(256), 0, stream, __VA_ARGS__); \
-  } while (0)
-#define KM_DISPATCH(SQ, grid, ...)                                                                    \
-  do {                                                                                                \
-    const int dc_ = h.d <= 8 ? 8 : (h.d <= 16 ? 16 : 32);                                             \
-    if (h.kern == 0) {                                                                                \
-      if (dc_ == 8) KM_LAUNCH(0, SQ, 8, grid, __VA_ARGS__);                                           \
-      else if (dc_ == 16) KM_LAUNCH(0, SQ, 16, grid, __VA_ARGS__);                                    \
-      else KM_LAUNCH(0, SQ, 32, grid, __VA_ARGS__);                                                   \
-    } else if (!SQ && h.kern == 2) {   /* dist_sq: cross form only */                                 \
-      if (dc_ == 8) KM_LAUNCH(2, false, 8, grid, __VA_ARGS__);                                        \
-      else if (dc_ == 16) KM_LAUNCH(2, false, 16, grid, __VA_ARGS__);                                 \
-      else KM_LAUNCH(2, false, 32, grid, __VA_ARGS__);                                                \
-    } else {                                                                                          \
-      if (dc_ == 8) KM_LAUNCH(1, SQ, 8, grid, __VA_ARGS__);                                           \
-      else if (dc_ == 16) KM_LAUNCH(1, SQ, 16, grid, __VA_ARGS__);                                    \
-      else KM_LAUNCH(1, SQ, 32, grid, __VA_ARGS__);                                                   \
-    }                                                                                                 \
-  } while (0)
+// k_kernel_matrix<KE, SQ, DC, EXACT> (SQ: the symmetric form K(X, X); EXACT: d fills the cap DC) on `stream`
+template <bool SQ, typename KE, typename DC, typename... Args>
+static void launch_kernel_matrix(KE, DC, int d, dim3 grid, hipStream_t stream, Args... args) {
+  auto kernel = d == DC::value ? k_kernel_matrix<KE::value, SQ, DC::value, true>
+                               : k_kernel_matrix<KE::value, SQ, DC::value, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, args...);
+}
 
 void bobe_gp::kernel_matrix_cross(const double* AT, int64_t lda, int64_t na, int64_t napad, const double* BT,
                                   int64_t ldb, int64_t nbv, int64_t nbpad, const Hyper& h, double* out, int64_t ldo,
                                   const double* wv, double* prt, int64_t ldp) {
   const dim3 grid((unsigned)(nbpad / TILE), (unsigned)(napad / TILE));
-  KM_DISPATCH(false, grid, AT, lda, na, BT, ldb, nbv, h, out, ldo, (const Hyper*)nullptr, (int64_t)0, (int64_t)0, wv, prt,
-              ldp);
+  auto launch = [&](auto KE, auto DC) {
+    launch_kernel_matrix<false>(KE, DC, h.d, grid, stream, AT, lda, na, BT, ldb, nbv, h, out, ldo, (const Hyper*)nullptr,
+                                (int64_t)0, (int64_t)0, wv, prt, ldp);
+  };
+  if (h.kern == 2)                       // dist_sq (kernel_eval): the squared distance itself, this cross form only
+    with_dcap(h.d, [&](auto DC) { launch(std::integral_constant<int, 2>{}, DC); });
+  else
+    with_kern_dcap(h.kern, h.d, launch);
   LAUNCH_CHECK();
 }
 
@@ -244,13 +217,13 @@ void bobe_gp::assemble_kxx(const Hyper& h, const double* xst, double* a, const H
                            int64_t bsA) {
   const dim3 grid((unsigned)(2 * nb * (nb + 1)), (unsigned)B);   // four workgroups per lower 128x128 tile
   prof_begin(BOBE_PROF_KXX);
-  KM_DISPATCH(true, grid, xst, Np, N, xst, Np, N, h, a, Np, hdev, bsX, bsA, (const double*)nullptr, (double*)nullptr,
-              (int64_t)0);
+  with_kern_dcap(h.kern, h.d, [&](auto KE, auto DC) {
+    launch_kernel_matrix<true>(KE, DC, h.d, grid, stream, xst, Np, N, xst, Np, N, h, a, Np, hdev, bsX, bsA,
+                               (const double*)nullptr, (double*)nullptr, (int64_t)0);
+  });
   prof_end(BOBE_PROF_KXX);
   LAUNCH_CHECK();
 }
-#undef KM_DISPATCH
-#undef KM_LAUNCH
 
 // Trailing update with the panels of 128-blocks [k0, k1): colmode 0 = every lower tile from 128-block `first`
 // on, colmode 1 = only 128-block column `first` (rows from `first` down).  A tile's time is set by its MFMAs
@@ -576,16 +549,15 @@ void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, in
 // scratch (an Np x Np matrix per slot, stride bsS): small launches - fewer 64 x 64 tiles than four per CU - form K^-1 on
 // 32 x 32 tiles into it first (k_lauum_tiles) and run the gradient epilogue from there: N = 1024 in a batch of four,
 // 77 -> 36 us (the fused launch is as long as its longest tile, K = 1024 on one CU).  Same partial sums, same bits.
-int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out, int dcap,
+int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
                    const Hyper* hdev, double* gp_out, int B, int64_t bsL, int64_t bsV, int64_t bsX, int64_t bsP,
                    double* scratch, int64_t bsS) {
   // (the tile size fixes the order of the gradient's partial sums: it depends on N only, so that an evaluation
   // returns the same bits alone, on a slot and in a batch)
-  const bool small = nb * (nb + 1) / 2 < LAUUM64_BELOW;
-  const int nt = small ? 2 * nb : nb;
-  const int ntiles = nt * (nt + 1) / 2;
+  const LauumTiling t = lauum_tiling(nb);
+  const int ntiles = t.ntiles;
   double* gpo = gp_out ? gp_out : gpart.d();
-  const bool split = small && scratch && !kinv_out && B * ntiles < 4 * std::max(num_cus, 1);
+  const bool split = t.small && scratch && !kinv_out && B * ntiles < 4 * std::max(num_cus, 1);
   double* kio = split ? scratch : kinv_out;
   const int64_t bsK = split ? bsS : 0;
   prof_begin(BOBE_PROF_LAUUM);
@@ -593,26 +565,12 @@ int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const d
     hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, linv, Np, Np, scratch, Np,
                        bsL, bsS, B);
   }
-  // (BOBE_GEMM64_GLDS selects the core of the 64 x 64 tiles; the 128 x 128 ones are register-staged)
-#define LG(KE, DC, TT, GL)                                                                                            \
-  hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT, GL>), dim3(ntiles * B), dim3(256),                                     \
-                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst, Np, h, gpo, \
-                     kio, Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK)
-#define LGD(KE, TT, GL)                                                                                 \
-  do {                                                                                                  \
-    if (dcap == 8) LG(KE, 8, TT, GL); else if (dcap == 16) LG(KE, 16, TT, GL); else LG(KE, 32, TT, GL); \
-  } while (0)
-#define LGT(KE)                                                          \
-  do {                                                                   \
-    if (!small) LGD(KE, 128, false);                                     \
-    else if (tuning().gemm64_glds) LGD(KE, 64, true);                    \
-    else LGD(KE, 64, false);                                             \
-  } while (0)
-  if (h.kern == 0) LGT(0); else LGT(1);
+  with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT, auto GL) {
+    hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT, GL>), dim3(ntiles * B), dim3(256),
+                       (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst, Np, h, gpo, kio,
+                       Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK);
+  });
   prof_end(BOBE_PROF_LAUUM);
-#undef LGT
-#undef LGD
-#undef LG
   LAUNCH_CHECK();
   return ntiles;
 }
@@ -698,10 +656,10 @@ void bobe_gp::mll_enqueue_body(const Hyper& h, bool want_grad, const Hyper* hdev
   if (hdev) HIPCHK(hipMemcpyAsync(eg.hyp_dev.p, eg.h_hyp, sizeof(Hyper), hipMemcpyHostToDevice, stream));
   factor_into(h, XsT2.d(), A2.d(), Linv2.d(), w2.d(), alpha2.d(), hdev);
   if (want_grad) {
-    const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-    const int ntiles = lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), nullptr, dcap, hdev, nullptr, 1, 0, 0, 0, 0, Tmp.d(), 0);
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2), dim3(256), 0, stream, (const double*)gpart.d(), ntiles, dcap + 1, d,
-                       dcap, res.d(), (const double*)w2.d(), (const double*)A2.d(), Np, Np, (const int*)info.p);
+    const int ntiles = lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), nullptr, hdev, nullptr, 1, 0, 0, 0, 0, Tmp.d(), 0);
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2), dim3(256), 0, stream, (const double*)gpart.d(), ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), res.d(), (const double*)w2.d(), (const double*)A2.d(), Np, Np,
+                       (const int*)info.p);
   } else {
     hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w2.d(), (const double*)A2.d(), Np, Np,
                        res.d(), (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
@@ -836,12 +794,11 @@ void bobe_gp::mll_lockstep_enqueue(int B, const Hyper* hs, bool want_grad) {
   solve_alpha(bw.Linv.d(), bw.w.d(), bw.alpha.d(), bw.part.d(), B, mat, vec, prt);
   // (the info word of slot b rides in res[b * 128 + 100]: one copy brings everything to the host)
   if (want_grad) {
-    const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-    const int ntiles = lauum(hs[0], bw.Linv.d(), bw.alpha.d(), bw.XsT.d(), nullptr, dcap, hdev, bw.gpart.d(), B, mat, vec,
+    const int ntiles = lauum(hs[0], bw.Linv.d(), bw.alpha.d(), bw.XsT.d(), nullptr, hdev, bw.gpart.d(), B, mat, vec,
                              xs, gps, bw.Tmp.d(), mat);
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)bw.gpart.d(), ntiles, dcap + 1,
-                       d, dcap, bw.res.d(), (const double*)bw.w.d(), (const double*)bw.A.d(), Np, Np, (const int*)inf, gps,
-                       (int64_t)128, vec, mat);
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)bw.gpart.d(), ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), bw.res.d(), (const double*)bw.w.d(), (const double*)bw.A.d(), Np, Np,
+                       (const int*)inf, gps, (int64_t)128, vec, mat);
   } else {
     hipLaunchKernelGGL(k_mll_terms, dim3(B), dim3(256), 0, stream, (const double*)bw.w.d(), (const double*)bw.A.d(), Np, Np,
                        bw.res.d(), vec, mat, (int64_t)128, (const int*)inf);
@@ -1266,7 +1223,7 @@ void bobe_gp::chol_row_update(const double* L, int64_t n, const double* k, doubl
 void bobe_gp::kinv_debug(double* Kinv) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   use();
-  lauum(hyp, Linv.d(), alpha.d(), XsT.d(), Tmp.d(), 32);
+  lauum(hyp, Linv.d(), alpha.d(), XsT.d(), Tmp.d());
   // symmetrise on the host side of the copy
   std::vector<double> full((size_t)N * N);
   HIPCHK(hipMemcpy2DAsync(full.data(), (size_t)N * 8, Tmp.p, (size_t)Np * 8, (size_t)N * 8, (size_t)N, hipMemcpyDeviceToHost,

@@ -26,6 +26,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gemm_f64.hpp"
@@ -136,8 +137,53 @@ struct Tuning {
 };
 const Tuning& tuning();
 
+// ---- kernel variants.  The kernels that read coordinates are templates over the family KE (0 RBF, anything else Matern)
+// and the cap DC on d (8 / 16 / 32).  The host picks the instantiation here and nowhere else: f receives the choice as
+// std::integral_constant values, which convert to int in template-argument position,
+//   with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) { hipLaunchKernelGGL((k_x<KE, DC>), ...); });
+inline int dcap_of(int d) { return d <= 8 ? 8 : (d <= 16 ? 16 : 32); }
+template <typename F>
+inline void with_dcap(int d, F&& f) {
+  switch (dcap_of(d)) {
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    default: f(std::integral_constant<int, 32>{}); break;
+  }
+}
+template <typename F>
+inline void with_kern_dcap(int kern, int d, F&& f) {
+  with_dcap(d, [&](auto DC) {
+    if (kern == 0) f(std::integral_constant<int, 0>{}, DC);
+    else f(std::integral_constant<int, 1>{}, DC);
+  });
+}
+template <typename F>
+inline void for_each_kern_dcap(F&& f) {          // all six (KE, DC), for the configure_*_kernels functions
+  for (int kern = 0; kern < 2; ++kern)
+    for (int d : {8, 16, 32}) with_kern_dcap(kern, d, f);
+}
+
 constexpr int LAUUM64_BELOW = 1200;   // lower 128-tile count below which K^-1 runs on 64x64 tiles (fixes the order of the
                                       // gradient's partial sums: a function of N only)
+// The tiles of K^-1 = Linv^T Linv over nb 128-blocks (k_lauum_grad, k_loo_grad): 64 x 64 tiles below LAUUM64_BELOW lower
+// 128-tiles, 128 x 128 above; nt tiles per side, ntiles lower ones = the number of the gradient's partial sums.
+struct LauumTiling { bool small; int nt, ntiles; };
+inline LauumTiling lauum_tiling(int nb) {
+  const bool small = nb * (nb + 1) / 2 < LAUUM64_BELOW;
+  const int nt = small ? 2 * nb : nb;
+  return {small, nt, nt * (nt + 1) / 2};
+}
+// with_kern_dcap extended by the tile size TT and its core GL: f(KE, DC, TT, GL).  BOBE_GEMM64_GLDS selects the core of the
+// 64 x 64 tiles; the 128 x 128 ones are register-staged.
+template <typename F>
+inline void with_lauum_variant(int kern, int d, const LauumTiling& t, F&& f) {
+  with_kern_dcap(kern, d, [&](auto KE, auto DC) {
+    if (!t.small) f(KE, DC, std::integral_constant<int, 128>{}, std::false_type{});
+    else if (tuning().gemm64_glds) f(KE, DC, std::integral_constant<int, 64>{}, std::true_type{});
+    else f(KE, DC, std::integral_constant<int, 64>{}, std::false_type{});
+  });
+}
+
 constexpr int FILL_NEAR = 2;          // the last panels of a block column always come from the update launches
 constexpr int FILL_CHUNK = 3;         // panels per filler visit of a tile (a filler must not outlast the panel, ~28 us)
 constexpr int FILL_SLACK = 16;        // caught-up work the plan accepts per deferred unit (1 / 16)
@@ -158,10 +204,17 @@ void configure_sweep_kernels();
 void configure_consumer_kernels();
 void configure_posterior_kernels();
 void configure_loo_kernels();
+// their guard: true on the first call on the current device only (`done`: the translation unit's own flag per device)
+inline bool first_use_on_device(bool (&done)[64]) {
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || done[dev]) return false;
+  return done[dev] = true;
+}
 
 struct Depth { int first, count, nblocks; };
 
-// Retention buffers of a sweep (bobe_gp::sweep's last argument; bobe_gp_wip_select_batch, gp_batch.hip): the caller's
+// Retention buffers of a sweep (SweepReq::keep; bobe_gp_wip_select_batch, gp_batch.hip): the caller's
 // device buffers, all with leading dimension ld = C rounded up to 128, that receive what the sweep otherwise keeps per chunk
 // or per super-chunk in the handle's workspace - CsT [d x ld] scaled candidates, V [Np x ld] = L^-1 K(X, C), crossT [Mp x ld],
 // sc [ld] = s_c.  The launches and their order are the sweep's own; only the addresses they write to differ.
@@ -175,6 +228,28 @@ struct SweepKeep {
   int64_t ld = 0;
   const double* V_used = nullptr;
   int64_t ldv_used = 0;
+};
+
+// What bobe_gp::sweep is asked for: C candidates, optionally scored against M integration points Z (Z = NULL: prediction
+// only).  Every output may be NULL (host or device memory otherwise; the argmin / min ones are host scalars).
+struct SweepReq {
+  const double* cand = nullptr;
+  int64_t C = 0;
+  const double* Z = nullptr;
+  int64_t M = 0;
+  double y_std = 1.0;
+  double* wipv = nullptr;
+  double* wipstd = nullptr;
+  double* mean = nullptr;
+  double* var = nullptr;
+  int policy = 1;                   // k_predict_finalize's NaN policy for the variance
+  int64_t* argmin_v = nullptr;
+  double* min_v = nullptr;
+  int64_t* argmin_s = nullptr;
+  double* min_s = nullptr;
+  double* fantasy_out = nullptr;    // C x M fantasy variances, dense
+  bool gated = false;               // apply the classifier gate (when one is set) to mean / var (the predict family)
+  SweepKeep* keep = nullptr;
 };
 
 // What an evaluation workspace (a lock-step batch slot, an evaluation slot, the single evaluation's own A2 / Linv2 / ...)
@@ -457,7 +532,7 @@ struct bobe_gp {
   int aside_first = 1 << 30;       // set by potrf(defer_diag = true), consumed by the next trtri()
   const double* aside_dg = nullptr;
   void trtri(double* a, double* linv, double* tmp, int B = 1, int64_t bsA = 0, int64_t bsL = 0, int64_t bsT = 0);
-  int lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out, int dcap,
+  int lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
             const Hyper* hdev = nullptr, double* gp_out = nullptr, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
             int64_t bsX = 0, int64_t bsP = 0, double* scratch = nullptr, int64_t bsS = 0);
   // wv = Linv rhs, al = Linv^T wv (rhs: y unless given; bsY: its stride per batch member)
@@ -492,10 +567,7 @@ struct bobe_gp {
   void prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w);
   void wip_score(const double* crossT, int64_t ldx, const double* cst, const double* scs, const double* bz, int64_t ns,
                  int64_t M, int64_t Mp, double y_std, double* wv, double* ws, double* vo);
-  // gated: apply the classifier gate (when one is set) to the mean / var outputs (the predict family, not the sweep)
-  void sweep(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv, double* wipstd,
-             double* mean, double* var, int policy, int64_t* argmin_v, double* min_v, int64_t* argmin_s, double* min_s,
-             double* fantasy_out, bool gated = false, bobe::SweepKeep* keep = nullptr);
+  void sweep(const bobe::SweepReq& r);
   void wip_grad(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv, double* wipstd,
                 double* dwipv, double* dwipstd);
   void predict_grad(const double* Xq, int64_t C, double* mean, double* var, double* dmean, double* dvar);

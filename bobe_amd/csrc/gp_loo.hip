@@ -11,28 +11,12 @@ namespace bobe {
 
 void configure_loo_kernels() {
   static bool done[64] = {false};
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || done[dev]) return;
-  allow_big_lds(k_loo_grad<0, 8, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 16, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 32, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 8, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 16, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 32, 64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 8, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 16, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 32, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 8, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 16, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 32, 64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 8, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 16, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<0, 32, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 8, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 16, 128>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_loo_grad<1, 32, 128>, GEMM_SMEM_BYTES);
-  done[dev] = true;
+  if (!first_use_on_device(done)) return;
+  for_each_kern_dcap([](auto KE, auto DC) {
+    allow_big_lds((k_loo_grad<KE, DC, 64>), GEMM64_SMEM_BYTES);
+    allow_big_lds((k_loo_grad<KE, DC, 64, true>), GEMM64_SMEM_BYTES);
+    allow_big_lds((k_loo_grad<KE, DC, 128>), GEMM_SMEM_BYTES);
+  });
 }
 
 }  // namespace bobe
@@ -90,8 +74,7 @@ int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
   loo_terms(Linv2.d(), alpha2.d(), grad != nullptr, res.d() + 102);
   if (grad) {
     double* ws = loo_ws.d();
-    const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
-    (void)lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), Tmp.d(), dcap);      // K^-1's lower tiles -> Tmp (its partial sums go unused)
+    (void)lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), Tmp.d());      // K^-1's lower tiles -> Tmp (its partial sums go unused)
     const int nt32 = (int)(Np / 32);
     hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2)), dim3(256), 0, stream, (const double*)Tmp.d(), Np,
                        (const double*)(ws + 4 * Np), A2.d());
@@ -99,35 +82,18 @@ int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
                        0, (const double*)(ws + 5 * Np), part.d(), Np, (int64_t)0, (int64_t)0, (int64_t)0);
     hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), 1u), dim3(256), 0, stream, (const double*)part.d(), Np,
                        nb, 0, Np, ws + 6 * Np, (int64_t)0, (int64_t)0);
-    // (the tile size fixes the order of the partial sums: a function of N only, lauum's rule)
-    const bool small = nb * (nb + 1) / 2 < LAUUM64_BELOW;
-    const int nt = small ? 2 * nb : nb;
-    const int ntiles = nt * (nt + 1) / 2;
+    const LauumTiling t = lauum_tiling(nb);       // (the dense B^T B on the tiles and the tile core K^-1 was formed on)
     prof_begin(BOBE_PROF_LAUUM);
-    // (BOBE_GEMM64_GLDS selects the core of the 64 x 64 tiles; the 128 x 128 ones are register-staged: lauum's rule)
-#define LG(KE, DC, TT, GL)                                                                                             \
-  hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(ntiles), dim3(256),                                            \
-                     (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)A2.d(), Np, Np, N,      \
-                     (const double*)alpha2.d(), (const double*)(ws + 6 * Np), (const double*)XsT2.d(), Np, h, gpart.d())
-#define LGD(KE, TT, GL)                                                                                 \
-  do {                                                                                                  \
-    if (dcap == 8) LG(KE, 8, TT, GL); else if (dcap == 16) LG(KE, 16, TT, GL); else LG(KE, 32, TT, GL); \
-  } while (0)
-#define LGT(KE)                                                          \
-  do {                                                                   \
-    if (!small) LGD(KE, 128, false);                                     \
-    else if (tuning().gemm64_glds) LGD(KE, 64, true);                    \
-    else LGD(KE, 64, false);                                             \
-  } while (0)
-    if (h.kern == 0) LGT(0); else LGT(1);
-#undef LGT
-#undef LGD
-#undef LG
+    with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT, auto GL) {
+      hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(t.ntiles), dim3(256),
+                         (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)A2.d(), Np, Np, N,
+                         (const double*)alpha2.d(), (const double*)(ws + 6 * Np), (const double*)XsT2.d(), Np, h, gpart.d());
+    });
     prof_end(BOBE_PROF_LAUUM);
     // (d + 1 workgroups: the gradient components; the scalar terms were reduced above)
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1), dim3(256), 0, stream, (const double*)gpart.d(), ntiles, dcap + 1, d, dcap,
-                       res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np, (const int*)nullptr, (int64_t)0,
-                       (int64_t)0, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1), dim3(256), 0, stream, (const double*)gpart.d(), t.ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np,
+                       (const int*)nullptr, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0);
     LAUNCH_CHECK();
   }
   HIPCHK(hipMemcpyAsync(h_res, res.p, 103 * sizeof(double), hipMemcpyDeviceToHost, stream));

@@ -14,13 +14,10 @@ using namespace bobe;
 namespace bobe {
 void configure_posterior_kernels() {
   static bool done[64] = {false};
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || done[dev]) return;
+  if (!first_use_on_device(done)) return;
   allow_big_lds(k_sigma_tiles<0>, GEMM_SMEM_BYTES);
   allow_big_lds(k_sigma_tiles<1>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trmm_draws, GEMM_SMEM_BYTES);
-  done[dev] = true;
 }
 }  // namespace bobe
 

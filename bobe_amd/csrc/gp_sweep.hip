@@ -9,9 +9,7 @@ using namespace bobe;
 namespace bobe {
 void configure_sweep_kernels() {
   static bool done[64] = {false};
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || done[dev]) return;
+  if (!first_use_on_device(done)) return;
   allow_big_lds(k_trimul<true>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul<false>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul_t, GEMM_SMEM_BYTES);
@@ -24,7 +22,6 @@ void configure_sweep_kernels() {
   allow_big_lds(k_cross_vv<128, false>, GEMM_SMEM_BYTES);
   allow_big_lds(k_cross_vv<64, true>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_cross_vv<64, false>, GEMM64_SMEM_BYTES);
-  done[dev] = true;
 }
 
 // the sweep's 128-tile GEMM kernels on the tile core BOBE_GEMM_GLDS selects (a function pointer: pass every argument)
@@ -104,24 +101,17 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
   scale(zin, M, Mp, hyp, ZsT.d(), Mp);
   kernel_matrix_cross(XsT.d(), Np, N, Np, ZsT.d(), Mp, M, Mp, hyp, kXZ.d(), Mp);
   // few integration points: 64 x 64 tiles (8 x 2 nb of them at M = 512) fill the chip where 4 x nb tiles of 128 x 128 do not
-  if (refine_v) {
-    solve_v(kXZ.d(), Mp, Mp, VZ.d(), Mp, qpart.d(), Mp);
-    hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
-                       (const double*)qpart.d(), Mp, nb, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
-  } else if (few) {
-    const int nt = 2 * nb;
+  // (the substitution of an ill-conditioned factor comes first: it has no 64-tile form)
+  int nt = nb;                                     // row tiles whose column sums of squares qpart holds
+  if (few && !refine_v) {
+    nt = 2 * nb;
     hipLaunchKernelGGL(trimul_v64_kernel(), dim3((unsigned)(Mp / 64), (unsigned)nt), dim3(256), GEMM64_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nt, (const double*)kXZ.d(), Mp, VZ.d(), Mp, qpart.d(), Mp);
-    hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
-                       (const double*)qpart.d(), Mp, nt, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
   } else {
-    hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)(Mp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
-                       (const double*)Linv.d(), Np, nb, (const double*)kXZ.d(), Mp, VZ.d(), Mp, qpart.d(), Mp,
-                       (const double*)nullptr, (int64_t)0, 0, (double*)nullptr, (int64_t)0, (const double*)nullptr,
-                       (int64_t)0, 0, 1 << 30);
-    hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
-                       (const double*)qpart.d(), Mp, nb, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
+    solve_v(kXZ.d(), Mp, Mp, VZ.d(), Mp, qpart.d(), Mp);
   }
+  hipLaunchKernelGGL(k_predict_finalize, dim3((unsigned)((Mp + 255) / 256)), dim3(256), 0, stream,
+                     (const double*)qpart.d(), Mp, nt, Mp, hyp.kvar + hyp.noise, 0, basez.d(), (double*)nullptr);
   LAUNCH_CHECK();
   if (need_w) make_w();
   if (host_z) z_seen_m = M;
@@ -130,23 +120,31 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
 // the scoring launch of ns candidates (k_wip_score): crossT and the scaled candidates CsT with leading dimension ldx, s_c, base_z
 void bobe_gp::wip_score(const double* crossT, int64_t ldx, const double* cst, const double* scs, const double* bz, int64_t ns,
                         int64_t M, int64_t Mp, double y_std, double* wv, double* ws, double* vo) {
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
   const dim3 grid((unsigned)((ns + 63) / 64));
   const size_t sm = (size_t)(d + 1) * 128 * sizeof(double);
-#define WS(KE, DC)                                                                                                        \
-  hipLaunchKernelGGL((k_wip_score<KE, DC>), grid, dim3(256), sm, stream, crossT, ldx, cst, ldx, (const double*)ZsT.d(), Mp, M, \
-                     scs, bz, ns, hyp, y_std * y_std, wv, ws, vo, M)
-  if (hyp.kern == 0) {
-    if (dcap == 8) WS(0, 8); else if (dcap == 16) WS(0, 16); else WS(0, 32);
-  } else {
-    if (dcap == 8) WS(1, 8); else if (dcap == 16) WS(1, 16); else WS(1, 32);
-  }
-#undef WS
+  with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+    hipLaunchKernelGGL((k_wip_score<KE, DC>), grid, dim3(256), sm, stream, crossT, ldx, cst, ldx, (const double*)ZsT.d(), Mp,
+                       M, scs, bz, ns, hyp, y_std * y_std, wv, ws, vo, M);
+  });
 }
 
-void bobe_gp::sweep(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv,
-                    double* wipstd, double* mean, double* var, int policy, int64_t* argmin_v, double* min_v,
-                    int64_t* argmin_s, double* min_s, double* fantasy_out, bool gated, bobe::SweepKeep* keep) {
+void bobe_gp::sweep(const SweepReq& r) {
+  const double* const cand = r.cand;
+  const double* const Z = r.Z;
+  const int64_t C = r.C, M = r.M;
+  const double y_std = r.y_std;
+  double* const wipv = r.wipv;
+  double* const wipstd = r.wipstd;
+  double* const mean = r.mean;
+  double* const var = r.var;
+  const int policy = r.policy;
+  int64_t* const argmin_v = r.argmin_v;
+  int64_t* const argmin_s = r.argmin_s;
+  double* const min_v = r.min_v;
+  double* const min_s = r.min_s;
+  double* const fantasy_out = r.fantasy_out;
+  const bool gated = r.gated;
+  SweepKeep* const keep = r.keep;
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   if (C <= 0) throw Err(BOBE_ERR_ARG, "C must be positive");
   const bool do_wip = (Z != nullptr);
@@ -345,7 +343,6 @@ void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M
   double* d_s = out_dev(wipstd, C, o_wipstd);
   double* d_dv = out_dev(dwipv, (size_t)C * d, o_mean);
   double* d_ds = out_dev(dwipstd, (size_t)C * d, o_var);
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
   if (few_path) {
     double* cdev = nullptr;                        // device copy of pinned-host coordinates, written by the first stage
     if (cand_pinned) {
@@ -374,37 +371,31 @@ void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M
     double* t3 = t2 + n_vec;
     const Hyper& h = hyp;
     const double* li = Linv.d();
-#define FEW(KE, DC)                                                                                                      \
-  do {                                                                                                                   \
-    hipLaunchKernelGGL((k_wg_col<KE, DC>), dim3((unsigned)(Np / 256 + 1), (unsigned)C), dim3(256), 0, stream,           \
-                       (const double*)XsT.d(), Np, N, Np, cfirst, h, kc, cdev);                                        \
-    solve_alpha(li, vv, uu, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)kc, Np);                             \
-    if (refine_v) {   /* one step of iterative refinement in vector form: v += Linv (k - L v), u += Linv^T of the same */   \
-      const unsigned gv_ = (unsigned)((n_vec + 255) / 256);                                                              \
-      hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), (unsigned)C), dim3(256), 0, stream, (const double*)A.d(), \
-                         Np, Np, (const double*)vv, t1, (int64_t)0, Np, Np);                                             \
-      hipLaunchKernelGGL(k_vec_axpy, dim3(gv_), dim3(256), 0, stream, t1, (const double*)kc, (const double*)t1, -1.0,    \
-                         (int64_t)n_vec);                                                                                \
-      solve_alpha(li, t2, t3, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)t1, Np);                         \
-      hipLaunchKernelGGL(k_vec_axpy, dim3(gv_), dim3(256), 0, stream, vv, (const double*)vv, (const double*)t2, 1.0,     \
-                         (int64_t)n_vec);                                                                                \
-      hipLaunchKernelGGL(k_vec_axpy, dim3(gv_), dim3(256), 0, stream, uu, (const double*)uu, (const double*)t3, 1.0,     \
-                         (int64_t)n_vec);                                                                                \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((k_wg_cross<KE, DC>), dim3((unsigned)nzw, (unsigned)C), dim3(256), (size_t)N * sizeof(double),     \
-                       stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np,                  \
-                       (const double*)kc, (const double*)vv, cin, h, kself, (const double*)basez.d(), y_std * y_std,   \
-                       a1, b1, Mp, pz);                                                                                  \
-    hipLaunchKernelGGL((k_wg_rows<KE, DC>), dim3((unsigned)nnw, (unsigned)C), dim3(256), 0, stream,                    \
-                       (const double*)XsT.d(), Np, N, Np, cin, h, (const double*)WZ.d(), Mp, Mp,                    \
-                       (const double*)a1, (const double*)b1, Mp, (const double*)uu, pn);                                  \
-  } while (0)
-    if (h.kern == 0) {
-      if (dcap == 8) FEW(0, 8); else if (dcap == 16) FEW(0, 16); else FEW(0, 32);
-    } else {
-      if (dcap == 8) FEW(1, 8); else if (dcap == 16) FEW(1, 16); else FEW(1, 32);
+    with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
+      hipLaunchKernelGGL((k_wg_col<KE, DC>), dim3((unsigned)(Np / 256 + 1), (unsigned)C), dim3(256), 0, stream,
+                         (const double*)XsT.d(), Np, N, Np, cfirst, h, kc, cdev);
+    });
+    solve_alpha(li, vv, uu, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)kc, Np);
+    if (refine_v) {   // one step of iterative refinement in vector form: v += Linv (k - L v), u += Linv^T of the same
+      const unsigned gv = (unsigned)((n_vec + 255) / 256);
+      hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), (unsigned)C), dim3(256), 0, stream, (const double*)A.d(),
+                         Np, Np, (const double*)vv, t1, (int64_t)0, Np, Np);
+      hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, t1, (const double*)kc, (const double*)t1, -1.0,
+                         (int64_t)n_vec);
+      solve_alpha(li, t2, t3, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)t1, Np);
+      hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, vv, (const double*)vv, (const double*)t2, 1.0,
+                         (int64_t)n_vec);
+      hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, uu, (const double*)uu, (const double*)t3, 1.0,
+                         (int64_t)n_vec);
     }
-#undef FEW
+    with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
+      hipLaunchKernelGGL((k_wg_cross<KE, DC>), dim3((unsigned)nzw, (unsigned)C), dim3(256), (size_t)N * sizeof(double),
+                         stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)kc,
+                         (const double*)vv, cin, h, kself, (const double*)basez.d(), y_std * y_std, a1, b1, Mp, pz);
+      hipLaunchKernelGGL((k_wg_rows<KE, DC>), dim3((unsigned)nnw, (unsigned)C), dim3(256), 0, stream,
+                         (const double*)XsT.d(), Np, N, Np, cin, h, (const double*)WZ.d(), Mp, Mp, (const double*)a1,
+                         (const double*)b1, Mp, (const double*)uu, pn);
+    });
     const size_t n_out = (size_t)C * (2 + 2 * d);
     const bool packed = n_out <= 96 && !(wipv && is_device_ptr(wipv)) && !(wipstd && is_device_ptr(wipstd)) &&
                         !(dwipv && is_device_ptr(dwipv)) && !(dwipstd && is_device_ptr(dwipstd));
@@ -440,19 +431,13 @@ void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M
                        (const double*)qpart.d(), CH, nb, nc, kself, 1, sc.d(), (double*)nullptr);
     hipLaunchKernelGGL(k_trimul_t, dim3((unsigned)(ncp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nb, (const double*)pv.d(), CH, ps.d(), CH);
-#define WG(KE, DC)                                                                                                   \
-  hipLaunchKernelGGL((k_wip_grad<KE, DC>), dim3((unsigned)nc), dim3(256), 0, stream, (const double*)XsT.d(), Np,  \
-                     N, (const double*)CsT.d(), CH, (const double*)ZsT.d(), Mp, M, (const double*)WZ.d(),  \
-                     Mp, (const double*)ps.d(), CH, (const double*)VZ.d(), (const double*)pv.d(), CH,         \
-                     (const double*)sc.d(), (const double*)basez.d(), hyp,                                        \
-                     y_std * y_std, d_v ? d_v + c0 : nullptr, d_s ? d_s + c0 : nullptr, d_dv ? d_dv + c0 * d : nullptr, \
-                     d_ds ? d_ds + c0 * d : nullptr)
-    if (hyp.kern == 0) {
-      if (dcap == 8) WG(0, 8); else if (dcap == 16) WG(0, 16); else WG(0, 32);
-    } else {
-      if (dcap == 8) WG(1, 8); else if (dcap == 16) WG(1, 16); else WG(1, 32);
-    }
-#undef WG
+    with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+      hipLaunchKernelGGL((k_wip_grad<KE, DC>), dim3((unsigned)nc), dim3(256), 0, stream, (const double*)XsT.d(), Np, N,
+                         (const double*)CsT.d(), CH, (const double*)ZsT.d(), Mp, M, (const double*)WZ.d(), Mp,
+                         (const double*)ps.d(), CH, (const double*)VZ.d(), (const double*)pv.d(), CH, (const double*)sc.d(),
+                         (const double*)basez.d(), hyp, y_std * y_std, d_v ? d_v + c0 : nullptr, d_s ? d_s + c0 : nullptr,
+                         d_dv ? d_dv + c0 * d : nullptr, d_ds ? d_ds + c0 * d : nullptr);
+    });
     LAUNCH_CHECK();
   }
   out_finish(wipv, C, o_wipv);
@@ -475,23 +460,16 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
     CsT.ensure((size_t)d * std::max<int64_t>(CH, chunk) * sizeof(double));
     double* d_mean = out_dev(mean, C, o_mean);
     double* d_dm = out_dev(dmean, (size_t)C * d, o_wipv);
-    const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
     for (int64_t c0 = 0; c0 < C; c0 += CH) {
       const int64_t nc = std::min<int64_t>(CH, C - c0), ncp = round_up(nc, TILE);
       scale(cin + c0 * d, nc, ncp, hyp, CsT.d(), CH);
       const dim3 grid((unsigned)((nc + 63) / 64));
       const size_t sm = (size_t)(d + 1) * 128 * sizeof(double);
-#define PGM(KE, DC)                                                                                                  \
-  hipLaunchKernelGGL((k_predict_grad<KE, DC>), grid, dim3(256), sm, stream, (const double*)XsT.d(), Np, N,    \
-                     (const double*)CsT.d(), CH, nc, (const double*)alpha.d(), (const double*)nullptr,           \
-                     (int64_t)0, (const double*)nullptr, hyp, d_dm + c0 * d, (double*)nullptr,                     \
-                     d_mean ? d_mean + c0 : nullptr)
-      if (hyp.kern == 0) {
-        if (dcap == 8) PGM(0, 8); else if (dcap == 16) PGM(0, 16); else PGM(0, 32);
-      } else {
-        if (dcap == 8) PGM(1, 8); else if (dcap == 16) PGM(1, 16); else PGM(1, 32);
-      }
-#undef PGM
+      with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+        hipLaunchKernelGGL((k_predict_grad<KE, DC>), grid, dim3(256), sm, stream, (const double*)XsT.d(), Np, N,
+                           (const double*)CsT.d(), CH, nc, (const double*)alpha.d(), (const double*)nullptr, (int64_t)0,
+                           (const double*)nullptr, hyp, d_dm + c0 * d, (double*)nullptr, d_mean ? d_mean + c0 : nullptr);
+      });
       LAUNCH_CHECK();
     }
     // (classifier gate, clf_gp.py:173-205: gated points carry mean = -inf and a zero gradient)
@@ -513,7 +491,6 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
   double* d_var = out_dev(var, C, o_var);
   double* d_dm = out_dev(dmean, (size_t)C * d, o_wipv);
   double* d_dv = out_dev(dvar, (size_t)C * d, o_wipstd);
-  const int dcap = d <= 8 ? 8 : (d <= 16 ? 16 : 32);
   for (int64_t c0 = 0; c0 < C; c0 += CH) {
     const int64_t nc = std::min<int64_t>(CH, C - c0), ncp = round_up(nc, TILE);
     scale(cin + c0 * d, nc, ncp, hyp, CsT.d(), CH);
@@ -530,16 +507,11 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
                        (const double*)Linv.d(), Np, nb, (const double*)VZ.d(), CH, WZ.d(), CH);
     const dim3 grid((unsigned)((nc + 63) / 64));
     const size_t sm = (size_t)(d + 1) * 128 * sizeof(double);
-#define PG(KE, DC)                                                                                                  \
-  hipLaunchKernelGGL((k_predict_grad<KE, DC>), grid, dim3(256), sm, stream, (const double*)XsT.d(), Np, N,    \
-                     (const double*)CsT.d(), CH, nc, (const double*)alpha.d(), (const double*)WZ.d(), CH,     \
-                     (const double*)sc.d(), hyp, d_dm + c0 * d, d_dv + c0 * d)
-    if (hyp.kern == 0) {
-      if (dcap == 8) PG(0, 8); else if (dcap == 16) PG(0, 16); else PG(0, 32);
-    } else {
-      if (dcap == 8) PG(1, 8); else if (dcap == 16) PG(1, 16); else PG(1, 32);
-    }
-#undef PG
+    with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+      hipLaunchKernelGGL((k_predict_grad<KE, DC>), grid, dim3(256), sm, stream, (const double*)XsT.d(), Np, N,
+                         (const double*)CsT.d(), CH, nc, (const double*)alpha.d(), (const double*)WZ.d(), CH,
+                         (const double*)sc.d(), hyp, d_dm + c0 * d, d_dv + c0 * d);
+    });
     LAUNCH_CHECK();
   }
   if (gate_on(gate)) gate_apply(cin, C, nullptr, nullptr, d_mean, d_var, d_dm, d_dv);

@@ -577,7 +577,7 @@ def test_config4_candidate_count_single_gpu():
     assert r["argmin_s"] == int(np.argmin(r["wipstd"])) and np.all(np.isfinite(r["wipv"]))
 
 
-@pytest.mark.parametrize("kernel,d", [("rbf", 3), ("matern", 5), ("rbf", 12)])
+@pytest.mark.parametrize("kernel,d", [("rbf", 3), ("matern", 5), ("rbf", 12), ("matern", 9), ("rbf", 17), ("matern", 17)])
 def test_predict_grad_against_central_differences(kernel, d):
     """bobe_gp_predict_grad = the JAX autodiff of gp.predict_single in the reference (acquisition.py:246-253)."""
     X, y = smooth_data(180, d, seed=40 + d)
@@ -873,7 +873,8 @@ def test_first_order_fit_paths():
     assert -r["mll"] == pytest.approx(fs, rel=1e-12)
 
 
-@pytest.mark.parametrize("kernel,d,m", [("rbf", 3, 70), ("matern", 5, 300), ("rbf", 12, 33)])
+@pytest.mark.parametrize("kernel,d,m", [("rbf", 3, 70), ("matern", 5, 300), ("rbf", 12, 33), ("matern", 9, 33), ("rbf", 17, 33),
+                                        ("matern", 17, 33)])
 def test_wip_gradient_against_values_and_central_differences(kernel, d, m):
     """bobe_gp_wip_grad: the scores equal the sweep's, the gradients equal central differences of the ORACLE's
     WIPV / WIPStd (the reference differentiates the same functions with jax.grad, acquisition.py:403-412)."""
