@@ -204,8 +204,8 @@ int bobe_gp_mll(bobe_gp_t* g, const double* ls, double kvar, double* mll, double
   Hyper h = g->hyp;
   for (int j = 0; j < g->d; ++j) h.ls[j] = ls[j];
   h.kvar = kvar;
-  g->mll_enqueue(h, grad != nullptr);
-  return g->mll_collect(mll, grad);
+  g->eval_start(g->own, 1, &h, grad != nullptr);
+  return g->eval_collect(g->own, 1, mll, grad, nullptr);
   API_END
 }
 

@@ -445,8 +445,7 @@ void bobe_gp::clone_from(bobe_gp& src) {
 void bobe_gp::release_all() {
   (void)hipSetDevice(device);
   if (stream) (void)hipStreamSynchronize(stream);
-  DBuf* bufs[] = {&X, &y, &XsT, &XsT2, &A, &Linv, &A2, &Linv2, &Tmp, &alpha, &w, &alpha2, &w2, &part, &gpart, &res, &info,
-                  &probs, &flags, &diag, &in_stage, &z_stage, &CsT, &ZsT, &kXC, &kXZ, &VZ, &WZ, &basez, &sc, &qpart, &pv,
+  DBuf* bufs[] = {&X, &y, &XsT, &A, &Linv, &Tmp, &alpha, &w, &part, &gpart, &res, &info, &probs, &diag, &in_stage, &z_stage, &CsT, &ZsT, &kXC, &kXZ, &VZ, &WZ, &basez, &sc, &qpart, &pv,
                   &ps, &o_mean, &o_var, &o_wipv, &o_wipstd, &o_misc, &kin_a, &kin_b, &kout, &wg_ws, &gate_sv, &gate_dual, &gate_ell, &ell_ws, &ell_perm,
                   &vxc, &vxc2, &loo_ws};
   for (DBuf* b : bufs) b->release();
@@ -461,29 +460,13 @@ void bobe_gp::release_all() {
     (void)hipStreamSynchronize(st);
     (void)hipStreamDestroy(st);
   }
-  auto free_eg = [](EvalGraph& e) {
-    for (int w_ = 0; w_ < 2; ++w_)
-      if (e.exec[w_]) (void)hipGraphExecDestroy(e.exec[w_]);
-    if (e.h_hyp) (void)hipHostFree(e.h_hyp);
-    e.hyp_dev.release();
-  };
-  free_eg(eg);
-  for (Slot* sl : slots) {
-    free_eg(sl->eg);
-    DBuf* sb[] = {&sl->XsT2, &sl->A2, &sl->Linv2, &sl->Tmp, &sl->alpha2, &sl->w2, &sl->part, &sl->gpart, &sl->res,
-                  &sl->info, &sl->flags, &sl->diag};
-    for (DBuf* b : sb) b->release();
-    if (sl->h_res) (void)hipHostFree(sl->h_res);
-    if (sl->ev) (void)hipEventDestroy(sl->ev);
+  own.release();
+  batch.release();
+  for (EvalWs* sl : slots) {
+    sl->release();
     delete sl;
   }
   slots.clear();
-  {
-    DBuf* bb[] = {&bw.A, &bw.Linv, &bw.Tmp, &bw.XsT, &bw.w, &bw.alpha, &bw.part, &bw.gpart, &bw.res, &bw.info, &bw.hyp, &bw.diag};
-    for (DBuf* b : bb) b->release();
-    if (bw.h_hyp) (void)hipHostFree(bw.h_hyp);
-    if (bw.h_res) (void)hipHostFree(bw.h_res);
-  }
   for (auto& kv : chol_plans) {
     kv.second.d_jobs.release();
     kv.second.d_colk0.release();

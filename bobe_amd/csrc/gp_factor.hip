@@ -157,30 +157,67 @@ void bobe_gp::build_probs() {
 }
 
 void bobe_gp::alloc_for_n() {
+  own.ensure(*this, 1);
   const size_t mat = (size_t)Np * Np * sizeof(double);
   const size_t vec = (size_t)Np * sizeof(double);
   A.ensure(mat);
   Linv.ensure(mat);
-  A2.ensure(mat);
-  Linv2.ensure(mat);
   Tmp.ensure(mat);
   y.ensure(vec);
   alpha.ensure(vec);
   w.ensure(vec);
-  alpha2.ensure(vec);
-  w2.ensure(vec);
   XsT.ensure((size_t)d * vec);
-  XsT2.ensure((size_t)d * vec);
-  const int64_t pw = Np > chunk ? Np : chunk;
+  const int64_t pw = Np > chunk ? Np : chunk;        // (the sweep's partial sums: a chunk wide)
   part.ensure((size_t)nb * pw * sizeof(double));
-  gpart.ensure((size_t)(2 * nb) * (2 * nb + 1) / 2 * (MAX_D + 1) * sizeof(double));
+  gpart.ensure((size_t)own.gps() * sizeof(double));   // (kinv_debug's lauum)
   res.ensure(128 * sizeof(double));
   info.ensure(sizeof(int));
-  flags.ensure((size_t)nb * sizeof(int));
   diag.ensure((size_t)nb * TILE * TILE * sizeof(double));
   build_probs();
   build_plans();
   forget_evals();
+}
+
+// Room for B members at the handle's current sizes.  The only place that knows what an evaluation workspace is made of.
+void bobe_gp::EvalWs::ensure(const bobe_gp& g, int B) {
+  if (!h_res) {
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_res), (size_t)width * (128 * sizeof(double) + sizeof(Hyper)),
+                         hipHostMallocDefault));
+    h_hyp = reinterpret_cast<Hyper*>(h_res + (size_t)width * 128);
+  }
+  if (B > cap || g.Np != Np) {            // (buffers reallocated or their member stride changed)
+    for (bobe::EvalTag& t : tag) t.clear();
+    cap = g.Np != Np ? B : std::max(cap, B);
+  }
+  Np = g.Np;
+  nb = g.nb;
+  d = g.d;
+  const size_t n = (size_t)B * sizeof(double);
+  A.ensure(n * mat());
+  Linv.ensure(n * mat());
+  Tmp.ensure(n * mat());
+  XsT.ensure(n * xs());
+  w.ensure(n * vec());
+  alpha.ensure(n * vec());
+  part.ensure(n * prt());
+  gpart.ensure(n * gps());
+  res.ensure(n * 128);
+  diag.ensure(n * nb * TILE * TILE);
+  info.ensure((size_t)width * sizeof(int));
+  hyp.ensure((size_t)width * sizeof(Hyper));
+}
+
+void bobe_gp::EvalWs::release() {
+  for (DBuf* b : {&XsT, &A, &Linv, &Tmp, &w, &alpha, &part, &gpart, &res, &info, &diag, &hyp}) b->release();
+  for (hipGraphExec_t& e : eg.exec) {
+    if (e) (void)hipGraphExecDestroy(e);
+    e = nullptr;
+  }
+  if (h_res) (void)hipHostFree(h_res);
+  h_res = nullptr;
+  h_hyp = nullptr;
+  if (ev) (void)hipEventDestroy(ev);
+  ev = nullptr;
 }
 
 void bobe_gp::scale(const double* in, int64_t n, int64_t npad, const Hyper& h, double* out, int64_t ldo,
@@ -276,7 +313,7 @@ int bobe_gp::panel_strips(int B, int rr) const {
 // everywhere, BOBE_FILL=0 off.
 bool bobe_gp::fill_pays(int B) const {
   const int f = tuning().fill;
-  if (f == 0 || in_slot) return false;
+  if (f == 0 || on_slot()) return false;
   if (f == 2) return true;
   return nb >= 28 && 20 * B * panel_workgroups(nb - 1, panel_strips(B, nb - 1)) <= 7 * std::max(num_cus, 1);
 }
@@ -411,7 +448,7 @@ const bobe_gp::CholPlan& bobe_gp::chol_plan(int B, bool fill) {
 void bobe_gp::build_plans() {
   if (nb <= 0) return;
   (void)chol_plan(1, false);
-  if (!in_slot && fill_pays(1)) (void)chol_plan(1, true);
+  if (fill_pays(1)) (void)chol_plan(1, true);
 }
 
 // Blocked right-looking Cholesky (NB = 128) of B matrices in lock step on one stream; every launch carries the slot
@@ -486,12 +523,12 @@ void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, 
   }
   // (the scratch blocks of the k_chol_panel steps; k_potf2 steps wrote in place, and come first:
   // B * npanel and rem only shrink with k)
-  aside_first = 1 << 30;
-  aside_dg = nullptr;
+  cur->aside_first = 1 << 30;
+  cur->aside_dg = nullptr;
   if (first_aside < nb) {
     if (defer_diag) {
-      aside_first = first_aside;
-      aside_dg = dg;
+      cur->aside_first = first_aside;
+      cur->aside_dg = dg;
     } else {
       hipLaunchKernelGGL(k_copy_diag, dim3(nb - first_aside, B), dim3(256), 0, stream, a, Np, bsA, (const double*)dg, bsD,
                          first_aside);
@@ -504,10 +541,10 @@ void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, 
 void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, int64_t bsL, int64_t bsT) {
   const Tuning& tu = tuning();
   prof_begin(BOBE_PROF_TRTRI);
-  hipLaunchKernelGGL(k_trti_diag, dim3(nb, B), dim3(256), POTF2_SMEM_BYTES, stream, a, Np, linv, Np, bsA, bsL, aside_dg,
-                     (int64_t)nb * TILE * TILE, aside_first);
-  aside_first = 1 << 30;
-  aside_dg = nullptr;
+  hipLaunchKernelGGL(k_trti_diag, dim3(nb, B), dim3(256), POTF2_SMEM_BYTES, stream, a, Np, linv, Np, bsA, bsL, cur->aside_dg,
+                     (int64_t)nb * TILE * TILE, cur->aside_first);
+  cur->aside_first = 1 << 30;
+  cur->aside_dg = nullptr;
   prof_end(BOBE_PROF_TRTRI);
   for (int dd = (int)depths.size() - 1; dd >= 0; --dd) {
     const Depth& D = depths[dd];
@@ -586,13 +623,27 @@ void bobe_gp::solve_alpha(const double* linv, double* wv, double* al, double* pr
   LAUNCH_CHECK();
 }
 
-void bobe_gp::factor_into(const Hyper& h, double* xst, double* a, double* linv, double* wv, double* al,
-                          const Hyper* hdev) {
-  scale(X.d(), N, Np, h, xst, Np, hdev, 1, 0, static_cast<int*>(info.p));
-  assemble_kxx(h, xst, a, hdev);
-  potrf(a, linv, static_cast<int*>(info.p), 1, 0, 0, nullptr, true);
-  trtri(a, linv, Tmp.d());
-  solve_alpha(linv, wv, al, part.d());
+void bobe_gp::chol_solve(const FactorBufs& f, int B, const double* rhs) {
+  potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag, true);
+  trtri(f.a, f.linv, f.tmp, B, f.mat, f.mat, f.mat);
+  solve_alpha(f.linv, f.w, f.alpha, f.part, B, f.mat, f.vec, f.prt, rhs, 0);
+}
+
+void bobe_gp::factor_into(const Hyper& h, const FactorBufs& f, const Hyper* hdev, int B) {
+  scale(X.d(), N, Np, h, f.xst, Np, hdev, B, f.xs, f.info);      // (also arms the B info words)
+  assemble_kxx(h, f.xst, f.a, hdev, B, f.xs, f.mat);
+  chol_solve(f, B);
+}
+
+void bobe_gp::mll_terms(const double* wv, const double* a, double* res_dev, const int* info_dev) {
+  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, wv, a, Np, Np, res_dev, (int64_t)0, (int64_t)0, (int64_t)0,
+                     info_dev);
+  LAUNCH_CHECK();
+}
+
+void bobe_gp::res_to_host(const double* res_dev, double* h, int n) {
+  HIPCHK(hipMemcpyAsync(h, res_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
 }
 
 // the text of a BOBE_NOT_PD status: a non-positive pivot (the factorisation's info word), or pivots below pivot_floor
@@ -606,27 +657,6 @@ std::string bobe_gp::not_pd_text(int inf, double min_diag) const {
                   "kernel matrix numerically singular: smallest pivot %.3g is below %g ulp of its diagonal (rank test)",
                   min_diag * min_diag, pivot_ulp);
   return buf;
-}
-
-void bobe_gp::ensure_slots(int n) {
-  if (!ev_batch) HIPCHK(hipEventCreateWithFlags(&ev_batch, hipEventDisableTiming));
-  while ((int)slots.size() < n) {
-    Slot* sl = new Slot();
-    slots.push_back(sl);
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&sl->h_res), 128 * sizeof(double), hipHostMallocDefault));
-  }
-  const size_t mat = (size_t)Np * Np * sizeof(double), vec = (size_t)Np * sizeof(double);
-  for (int i = 0; i < n; ++i) {
-    Slot& sl = *slots[i];
-    sl.A2.ensure(mat); sl.Linv2.ensure(mat); sl.Tmp.ensure(mat);
-    sl.alpha2.ensure(vec); sl.w2.ensure(vec); sl.XsT2.ensure((size_t)d * vec);
-    sl.part.ensure((size_t)nb * Np * sizeof(double));
-    sl.gpart.ensure((size_t)(2 * nb) * (2 * nb + 1) / 2 * (MAX_D + 1) * sizeof(double));
-    sl.res.ensure(128 * sizeof(double));
-    sl.info.ensure(sizeof(int));
-    sl.flags.ensure((size_t)nb * sizeof(int));
-    sl.diag.ensure((size_t)nb * TILE * TILE * sizeof(double));
-  }
 }
 
 // The slots' streams are made through the CU-mask entry point with every CU enabled: such a stream gets a
@@ -650,46 +680,56 @@ const std::vector<hipStream_t>& bobe_gp::slot_stream_set() {
   return v;
 }
 
-// value (+ gradient) pipeline of one hyper-parameter vector on the current stream / workspace; results land in
-// the pinned h_res: [0] y^T K^-1 y, [1] sum log L_ii, [2..2+d] gradient, [100] the factorisation's info word
-void bobe_gp::mll_enqueue_body(const Hyper& h, bool want_grad, const Hyper* hdev) {
-  if (hdev) HIPCHK(hipMemcpyAsync(eg.hyp_dev.p, eg.h_hyp, sizeof(Hyper), hipMemcpyHostToDevice, stream));
-  factor_into(h, XsT2.d(), A2.d(), Linv2.d(), w2.d(), alpha2.d(), hdev);
+void bobe_gp::ensure_slots(int n) {
+  if (!ev_batch) HIPCHK(hipEventCreateWithFlags(&ev_batch, hipEventDisableTiming));
+  const std::vector<hipStream_t>& sts = slot_stream_set();
+  while ((int)slots.size() < n) {
+    slots.push_back(new EvalWs(1));
+    slots.back()->stream = sts[slots.size() - 1];
+  }
+  for (int i = 0; i < n; ++i) slots[i]->ensure(*this, 1);
+}
+
+void bobe_gp::ensure_batch(int B) {
+  batch.ensure(*this, B);
+  (void)chol_plan(B, fill_pays(B));      // (uploads its tables on first use: here, not between the launches of a batch)
+}
+
+// The launches of B value (+ gradient) evaluations on ws, on the current stream: the single evaluation and a slot (B = 1,
+// stride 0 - plain or under capture) and the lock-step batch (every launch widened by the member dimension).  Results land
+// in the pinned ws.h_res[b * 128 + ...]; the info word of member b rides in res[b * 128 + 100], so one copy brings
+// everything to the host.
+void bobe_gp::eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev) {
+  const FactorBufs f = ws.bufs();
+  const int64_t gps = ws.stride(ws.gps()), rs = ws.stride(128);
+  if (hdev) HIPCHK(hipMemcpyAsync(ws.hyp.p, ws.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
+  factor_into(hs[0], f, hdev, B);
   if (want_grad) {
-    const int ntiles = lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), nullptr, hdev, nullptr, 1, 0, 0, 0, 0, Tmp.d(), 0);
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2), dim3(256), 0, stream, (const double*)gpart.d(), ntiles,
-                       dcap_of(d) + 1, d, dcap_of(d), res.d(), (const double*)w2.d(), (const double*)A2.d(), Np, Np,
-                       (const int*)info.p);
+    const int ntiles = lauum(hs[0], f.linv, f.alpha, f.xst, nullptr, hdev, ws.gpart.d(), B, f.mat, f.vec, f.xs, gps, f.tmp,
+                             f.mat);
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)ws.gpart.d(), ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)f.w, (const double*)f.a, Np, Np,
+                       (const int*)f.info, gps, rs, f.vec, f.mat);
   } else {
-    hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w2.d(), (const double*)A2.d(), Np, Np,
-                       res.d(), (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
+    hipLaunchKernelGGL(k_mll_terms, dim3(B), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, ws.res.d(),
+                       f.vec, f.mat, rs, (const int*)f.info);
   }
   LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(h_res, res.p, 102 * sizeof(double), hipMemcpyDeviceToHost, stream));   // [100] = info, [101] = min L_jj
+  // ([100] = info, [101] = min L_jj are the last a member writes; the batch brings its members' whole blocks)
+  HIPCHK(hipMemcpyAsync(ws.h_res, ws.res.p, (size_t)(ws.width > 1 ? B * 128 : 102) * sizeof(double), hipMemcpyDeviceToHost,
+                        stream));
 }
 
-void bobe_gp::mll_enqueue(const Hyper& h, bool want_grad) {
-  tag2.clear();                             // (the workspace's factor is being overwritten; armed once the pipeline is queued)
-  mll_enqueue_pipeline(h, want_grad);
-  tag2.arm(h, data_gen, Np);
-}
-
-void bobe_gp::mll_enqueue_pipeline(const Hyper& h, bool want_grad) {
-  const Tuning& tu = tuning();
-  h_res[110] = pivot_floor(h);              // (host side of the pinned block, beyond what the device copy writes: read at collect)
-  // Up to graph_max_n points an evaluation is tens of kernels of a few microseconds each, and with several slots
-  // in flight the host cannot enqueue them as fast as the GPU retires them: a slot replays its pipeline as one
-  // graph (N = 64 / 512 / 2048 with four in flight: 42 / 107 / 419 us per evaluation instead of 66 / 141 / 553).
-  // A lone evaluation on the handle's stream is NOT faster as a graph (125 vs 107 us at N = 64) and stays a
-  // plain launch sequence; so does everything while a kernel class is being timed (events are not captured).
-  if (!in_slot || N > tu.graph_max_n || prof_tag != 0) {
-    mll_enqueue_body(h, want_grad, nullptr);
-    return;
-  }
-  if (!eg.h_hyp) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&eg.h_hyp), sizeof(Hyper), hipHostMallocDefault));
-  eg.hyp_dev.ensure(sizeof(Hyper));
+// Up to graph_max_n points an evaluation is tens of kernels of a few microseconds each, and with several slots
+// in flight the host cannot enqueue them as fast as the GPU retires them: a slot replays its pipeline as one
+// graph (N = 64 / 512 / 2048 with four in flight: 42 / 107 / 419 us per evaluation instead of 66 / 141 / 553).
+void bobe_gp::eval_replay(EvalWs& ws, const Hyper* hs, bool want_grad) {
+  EvalGraph& eg = ws.eg;
   const int w = want_grad ? 1 : 0;
-  const std::array<const void*, 16> sig = eval_signature();
+  const std::array<const void*, 16> sig = {ws.XsT.p, ws.A.p, ws.Linv.p, ws.Tmp.p, ws.w.p, ws.alpha.p, ws.part.p, ws.gpart.p,
+                                           ws.res.p, ws.info.p, X.p, y.p, probs.p, static_cast<const void*>(ws.h_res),
+                                           reinterpret_cast<const void*>(static_cast<uintptr_t>(N)),
+                                           static_cast<const void*>(stream)};
   if (!eg.exec[w] || eg.sig[w] != sig) {     // first use, or N / a buffer changed since the capture
     if (eg.exec[w]) {
       (void)hipGraphExecDestroy(eg.exec[w]);
@@ -698,7 +738,7 @@ void bobe_gp::mll_enqueue_pipeline(const Hyper& h, bool want_grad) {
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     try {
-      mll_enqueue_body(h, want_grad, static_cast<const Hyper*>(eg.hyp_dev.p));
+      eval_enqueue(ws, 1, hs, want_grad, static_cast<const Hyper*>(ws.hyp.p));
     } catch (...) {
       (void)hipStreamEndCapture(stream, &graph);
       if (graph) (void)hipGraphDestroy(graph);
@@ -713,18 +753,29 @@ void bobe_gp::mll_enqueue_pipeline(const Hyper& h, bool want_grad) {
     }
     eg.sig[w] = sig;
   }
-  *eg.h_hyp = h;            // read by the graph's first node when it executes; the caller collects before reusing it
-  HIPCHK(hipGraphLaunch(eg.exec[w], stream));
+  HIPCHK(hipGraphLaunch(eg.exec[w], stream));      // (its first node reads ws.h_hyp when it executes; the caller collects before reusing it)
 }
 
-int bobe_gp::slot_collect(Slot& sl, double* mll, double* grad) {
-  // touches only the slot's own stream and pinned results: safe while another thread submits to another slot
-  HIPCHK(hipStreamSynchronize(sl.stream));
-  const double* hr = sl.h_res;
-  sl.tag.collected(hr);
+// Queue the evaluation of hs[0 .. B) on ws (B = 1 unless ws is the batch) and record what its members will hold.
+void bobe_gp::eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad) {
+  UseWs use_ws(*this, ws);
+  for (int b = 0; b < B; ++b) {
+    ws.tag[b].clear();                      // (the member's factor is being overwritten; armed once the pipeline is queued)
+    ws.h_hyp[b] = hs[b];
+    ws.floor[b] = pivot_floor(hs[b]);
+  }
+  // A lone evaluation on the handle's stream is NOT faster as a graph (125 vs 107 us at N = 64) and stays a
+  // plain launch sequence; so does everything while a kernel class is being timed (events are not captured).
+  if (ws.width > 1) eval_enqueue(ws, B, hs, want_grad, static_cast<const Hyper*>(ws.hyp.p));
+  else if (!on_slot() || N > tuning().graph_max_n || prof_tag != 0) eval_enqueue(ws, 1, hs, want_grad, nullptr);
+  else eval_replay(ws, hs, want_grad);
+  for (int b = 0; b < B; ++b) ws.tag[b].arm(hs[b], data_gen, Np);
+}
+
+int bobe_gp::eval_result(const double* hr, double floor, double* mll, double* grad) const {
   int inf;
   std::memcpy(&inf, hr + 100, sizeof(int));
-  if (inf != 0x7f7f7f7f || !pivots_resolved(hr[101], hr[110])) {
+  if (inf != 0x7f7f7f7f || !pivots_resolved(hr[101], floor)) {
     *mll = std::nan("");
     if (grad)
       for (int j = 0; j <= d; ++j) grad[j] = std::nan("");
@@ -737,100 +788,17 @@ int bobe_gp::slot_collect(Slot& sl, double* mll, double* grad) {
   return BOBE_OK;
 }
 
-int bobe_gp::mll_collect(double* mll, double* grad) {
-  sync();
-  tag2.collected(h_res);
-  int inf;
-  std::memcpy(&inf, h_res + 100, sizeof(int));
-  if (inf != 0x7f7f7f7f || !pivots_resolved(h_res[101], h_res[110])) {
-    *mll = std::nan("");
-    if (grad)
-      for (int j = 0; j <= d; ++j) grad[j] = std::nan("");
-    g_err = not_pd_text(inf, h_res[101]);
-    return BOBE_NOT_PD;
-  }
-  *mll = -0.5 * h_res[0] - h_res[1] - 0.5 * (double)N * std::log(2.0 * M_PI);
-  if (grad)
-    for (int j = 0; j <= d; ++j) grad[j] = h_res[2 + j];
-  return BOBE_OK;
-}
-
-void bobe_gp::ensure_batch(int B) {
-  if (!bw.h_hyp) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&bw.h_hyp), BOBE_MAX_MLL_SLOTS * sizeof(Hyper), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&bw.h_res), BOBE_MAX_MLL_SLOTS * 128 * sizeof(double), hipHostMallocDefault));
-  }
-  const size_t mat = (size_t)Np * Np * sizeof(double), vec = (size_t)Np * sizeof(double);
-  const size_t nB = (size_t)B;
-  if (B > bw.cap || Np != bw.Np)          // (buffers reallocated or their slot stride changed)
-    for (bobe::EvalTag& t : bw.tag) t.clear();
-  bw.A.ensure(nB * mat); bw.Linv.ensure(nB * mat); bw.Tmp.ensure(nB * mat);
-  bw.XsT.ensure(nB * d * vec); bw.w.ensure(nB * vec); bw.alpha.ensure(nB * vec);
-  bw.part.ensure(nB * nb * vec);
-  bw.gpart.ensure(nB * (size_t)gpart_stride() * sizeof(double));
-  bw.res.ensure(nB * 128 * sizeof(double));
-  bw.info.ensure(BOBE_MAX_MLL_SLOTS * sizeof(int));
-  bw.diag.ensure(nB * (size_t)nb * TILE * TILE * sizeof(double));
-  bw.hyp.ensure(BOBE_MAX_MLL_SLOTS * sizeof(Hyper));
-  bw.cap = std::max(bw.cap, B);
-  bw.Np = Np;
-  (void)chol_plan(B, fill_pays(B));      // (uploads its tables on first use: here, not between the launches of a batch)
-}
-
-// B value(+gradient) evaluations in lock step: the pipeline of mll_enqueue_body with every launch widened by the
-// slot dimension.  Results land in the pinned bw.h_res[b*128 + ...] (layout of mll_enqueue_body, the info word at [100]).
-void bobe_gp::mll_lockstep_enqueue(int B, const Hyper* hs, bool want_grad) {
-  ensure_batch(B);
-  const int64_t mat = Np * Np, vec = Np, xs = (int64_t)d * Np, prt = (int64_t)nb * Np, gps = gpart_stride();
-  for (int b = 0; b < B; ++b) bw.tag[b].clear();
-  for (int b = 0; b < B; ++b) bw.h_hyp[b] = hs[b];
-  HIPCHK(hipMemcpyAsync(bw.hyp.p, bw.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
-  const Hyper* hdev = static_cast<const Hyper*>(bw.hyp.p);
-  int* inf = static_cast<int*>(bw.info.p);
-  scale(X.d(), N, Np, hs[0], bw.XsT.d(), Np, hdev, B, xs, inf);      // (also arms the B info words)
-  assemble_kxx(hs[0], bw.XsT.d(), bw.A.d(), hdev, B, xs, mat);
-  potrf(bw.A.d(), bw.Linv.d(), inf, B, mat, mat, bw.diag.d(), true);
-  trtri(bw.A.d(), bw.Linv.d(), bw.Tmp.d(), B, mat, mat, mat);
-  solve_alpha(bw.Linv.d(), bw.w.d(), bw.alpha.d(), bw.part.d(), B, mat, vec, prt);
-  // (the info word of slot b rides in res[b * 128 + 100]: one copy brings everything to the host)
-  if (want_grad) {
-    const int ntiles = lauum(hs[0], bw.Linv.d(), bw.alpha.d(), bw.XsT.d(), nullptr, hdev, bw.gpart.d(), B, mat, vec,
-                             xs, gps, bw.Tmp.d(), mat);
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)bw.gpart.d(), ntiles,
-                       dcap_of(d) + 1, d, dcap_of(d), bw.res.d(), (const double*)bw.w.d(), (const double*)bw.A.d(), Np, Np,
-                       (const int*)inf, gps, (int64_t)128, vec, mat);
-  } else {
-    hipLaunchKernelGGL(k_mll_terms, dim3(B), dim3(256), 0, stream, (const double*)bw.w.d(), (const double*)bw.A.d(), Np, Np,
-                       bw.res.d(), vec, mat, (int64_t)128, (const int*)inf);
-  }
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(bw.h_res, bw.res.p, (size_t)B * 128 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  for (int b = 0; b < B; ++b) bw.tag[b].arm(hs[b], data_gen, Np);
-}
-
-int bobe_gp::mll_lockstep_collect(int B, double* mll, double* grad, int* status) {
-  sync();
+// A slot's collect touches only the slot's own stream, records and pinned results: safe while another thread submits to
+// another slot.
+int bobe_gp::eval_collect(EvalWs& ws, int B, double* mll, double* grad, int* status) {
+  HIPCHK(hipStreamSynchronize(ws.stream ? ws.stream : stream));
   int worst = BOBE_OK;
   for (int b = 0; b < B; ++b) {
-    const double* hr = bw.h_res + (size_t)b * 128;
-    bw.tag[b].collected(hr);
-    double* gb = grad ? grad + (size_t)b * (d + 1) : nullptr;
-    int st = BOBE_OK;
-    int inf_b;
-    std::memcpy(&inf_b, hr + 100, sizeof(int));
-    if (inf_b != 0x7f7f7f7f || !pivots_resolved(hr[101], pivot_floor(bw.h_hyp[b]))) {
-      mll[b] = std::nan("");
-      if (gb)
-        for (int j = 0; j <= d; ++j) gb[j] = std::nan("");
-      g_err = not_pd_text(inf_b, hr[101]);
-      st = BOBE_NOT_PD;
-      worst = st;
-    } else {
-      mll[b] = -0.5 * hr[0] - hr[1] - 0.5 * (double)N * std::log(2.0 * M_PI);
-      if (gb)
-        for (int j = 0; j <= d; ++j) gb[j] = hr[2 + j];
-    }
+    const double* hr = ws.h_res + (size_t)b * 128;
+    ws.tag[b].collected(hr);
+    const int st = eval_result(hr, ws.floor[b], mll + b, grad ? grad + (size_t)b * (d + 1) : nullptr);
     if (status) status[b] = st;
+    if (st != BOBE_OK) worst = st;
   }
   return worst;
 }
@@ -865,9 +833,9 @@ void bobe_gp::set_data(const double* Xin, const double* ys, int64_t n) {
 }
 
 void bobe_gp::forget_evals() {
-  tag2.clear();
-  for (Slot* sl : slots) sl->tag.clear();
-  for (bobe::EvalTag& t : bw.tag) t.clear();
+  for (bobe::EvalTag& t : own.tag) t.clear();
+  for (bobe::EvalTag& t : batch.tag) t.clear();
+  for (EvalWs* sl : slots) sl->tag[0].clear();
 }
 
 // The fit has usually just evaluated the hyper-parameters bobe_gp_factor is asked for (the best restart's last iterate; the
@@ -875,47 +843,38 @@ void bobe_gp::forget_evals() {
 // compute again (2 ms at N = 4096).  A workspace whose record matches hyp bit for bit, the data generation and Np is copied
 // into the handle's buffers instead (k_copy_factor: the lower tiles, ~0.1 ms); anything else factorises.
 const bobe::EvalTag* bobe_gp::adopt_factor() {
-  if (!tuning().factor_reuse || in_slot) return nullptr;
-  auto match = [&](const bobe::EvalTag& t) { return t.valid && t.gen == data_gen && t.Np == Np && bobe::same_hyper(t.h, hyp); };
-  const size_t mat = (size_t)Np * Np, vec = (size_t)Np, xs = (size_t)d * Np;
-  const bobe::EvalTag* tag = nullptr;
-  const double *sA = nullptr, *sL = nullptr, *sal = nullptr, *sw = nullptr, *sx = nullptr;
-  int src = 0;
-  if (bw.Np == Np)
-    for (int b = 0; b < bw.cap && b < BOBE_MAX_MLL_SLOTS && !tag; ++b) {
-      const size_t b1 = (size_t)b + 1;
-      if (!match(bw.tag[b]) || bw.A.bytes < b1 * mat * 8 || bw.Linv.bytes < b1 * mat * 8 || bw.alpha.bytes < b1 * vec * 8 ||
-          bw.w.bytes < b1 * vec * 8 || bw.XsT.bytes < b1 * xs * 8)
-        continue;
-      tag = &bw.tag[b];
-      sA = bw.A.d() + b * mat; sL = bw.Linv.d() + b * mat; sal = bw.alpha.d() + b * vec; sw = bw.w.d() + b * vec;
-      sx = bw.XsT.d() + b * xs;
-      src = 1;
+  if (!tuning().factor_reuse || on_slot()) return nullptr;
+  // the first matching member, in this order: the batch's members ascending, the slots that are not in flight, the handle's own
+  const EvalWs* ws = nullptr;
+  int b = 0, src = 0;
+  auto find = [&](const EvalWs& c, int source) {
+    for (int i = 0; !ws && c.Np == Np && i < c.cap; ++i) {      // (members [0, cap) fit c's buffers at c.Np: EvalWs::ensure)
+      const bobe::EvalTag& t = c.tag[i];
+      if (!(t.valid && t.gen == data_gen && t.Np == Np && bobe::same_hyper(t.h, hyp))) continue;
+      ws = &c;
+      b = i;
+      src = source;
     }
-  if (!tag) {
+  };
+  find(batch, 1);
+  if (!ws) {
     std::lock_guard<std::mutex> lock(submit_mutex);      // (the slot table grows under this mutex)
-    for (Slot* sl : slots)
-      if (!sl->busy && match(sl->tag)) {
-        tag = &sl->tag;
-        sA = sl->A2.d(); sL = sl->Linv2.d(); sal = sl->alpha2.d(); sw = sl->w2.d(); sx = sl->XsT2.d();
-        src = 2;
-        break;
-      }
+    for (const EvalWs* sl : slots)
+      if (!sl->busy) find(*sl, 2);
   }
-  if (!tag && match(tag2)) {
-    tag = &tag2;
-    sA = A2.d(); sL = Linv2.d(); sal = alpha2.d(); sw = w2.d(); sx = XsT2.d();
-    src = 3;
-  }
-  if (!tag) return nullptr;
-  const int vgroups = (int)std::min<int64_t>(64, ((int64_t)xs + 255) / 256);
-  hipLaunchKernelGGL(k_copy_factor, dim3((unsigned)(nb * (nb + 1) + vgroups)), dim3(256), 0, stream, sA, A.d(), sL, Linv.d(),
-                     nb, sal, alpha.d(), sw, w.d(), sx, XsT.d(), Np, (int64_t)xs);
+  find(own, 3);
+  if (!ws) return nullptr;
+  const int64_t xs = ws->xs();
+  const int vgroups = (int)std::min<int64_t>(64, (xs + 255) / 256);
+  hipLaunchKernelGGL(k_copy_factor, dim3((unsigned)(nb * (nb + 1) + vgroups)), dim3(256), 0, stream,
+                     (const double*)ws->A.d() + b * ws->mat(), A.d(), (const double*)ws->Linv.d() + b * ws->mat(), Linv.d(), nb,
+                     (const double*)ws->alpha.d() + b * ws->vec(), alpha.d(), (const double*)ws->w.d() + b * ws->vec(), w.d(),
+                     (const double*)ws->XsT.d() + b * xs, XsT.d(), Np, xs);
   LAUNCH_CHECK();
   sync();
   factor_source = src;
   if (tuning().trace) std::fprintf(stderr, "[bobe] factor: adopted the factor of an evaluation (source %d)\n", src);
-  return tag;
+  return &ws->tag[b];
 }
 
 int bobe_gp::factor_state() {
@@ -926,13 +885,10 @@ int bobe_gp::factor_state() {
     inf = t->info;
     min_diag = t->min_diag;
   } else {
-    factor_into(hyp, XsT.d(), A.d(), Linv.d(), w.d(), alpha.d());
+    factor_into(hyp, state_bufs());
     // the info word and the smallest pivot's root in one copy (k_mll_terms: res[100], res[101])
-    hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w.d(), (const double*)A.d(), Np, Np, res.d(),
-                       (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(h_res, res.p, 102 * sizeof(double), hipMemcpyDeviceToHost, stream));
-    sync();
+    mll_terms(w.d(), A.d(), res.d(), static_cast<const int*>(info.p));
+    res_to_host(res.d(), h_res, 102);
     std::memcpy(&inf, h_res + 100, sizeof(int));
     min_diag = h_res[101];
     factor_source = 0;
@@ -972,8 +928,9 @@ int bobe_gp::mll_batch(int64_t B, const double* ls, const double* kvar, double* 
         for (int j = 0; j < d; ++j) hs[i].ls[j] = ls[(b0 + i) * d + j];
         hs[i].kvar = kvar[b0 + i];
       }
-      mll_lockstep_enqueue(nbat, hs, grad != nullptr);
-      const int st = mll_lockstep_collect(nbat, mll + b0, grad ? grad + b0 * (d + 1) : nullptr, status ? status + b0 : nullptr);
+      ensure_batch(nbat);
+      eval_start(batch, nbat, hs, grad != nullptr);
+      const int st = eval_collect(batch, nbat, mll + b0, grad ? grad + b0 * (d + 1) : nullptr, status ? status + b0 : nullptr);
       if (st != BOBE_OK) worst = st;
     }
     return worst;
@@ -984,53 +941,26 @@ int bobe_gp::mll_batch(int64_t B, const double* ls, const double* kvar, double* 
   for (int64_t b0 = 0; b0 < B; b0 += width) {
     const int nbat = (int)std::min<int64_t>(width, B - b0);
     const auto t_start = std::chrono::steady_clock::now();
-    if (nbat == 1) {   // a lone evaluation owns the whole chip on the handle's stream
-      Hyper h = hyp;
-      for (int j = 0; j < d; ++j) h.ls[j] = ls[b0 * d + j];
-      h.kvar = kvar[b0];
-      mll_enqueue(h, grad != nullptr);
-    } else {
+    // (a lone evaluation owns the whole chip on the handle's stream)
+    auto ws_of = [&](int i) -> EvalWs& { return nbat == 1 ? own : *slots[i]; };
+    if (nbat > 1) {
       ensure_slots(nbat);
       for (int i = 0; i < nbat; ++i)
         if (slots[i]->busy)
           throw Err(BOBE_ERR_STATE, "an evaluation submitted with bobe_gp_mll_submit is still in flight on a slot this batch needs");
-      const std::vector<hipStream_t>& sts = slot_stream_set();
       // the batch streams start after everything already queued on the handle's stream (data uploads)
       HIPCHK(hipEventRecord(ev_batch, stream));
-      for (int i = 0; i < nbat; ++i) {
-        Hyper h = hyp;
-        for (int j = 0; j < d; ++j) h.ls[j] = ls[(b0 + i) * d + j];
-        h.kvar = kvar[b0 + i];
-        Slot& sl = *slots[i];
-        sl.stream = sts[i];
-        HIPCHK(hipStreamWaitEvent(sl.stream, ev_batch, 0));
-        swap_slot(sl);
-        try {
-          mll_enqueue(h, grad != nullptr);
-        } catch (...) {
-          swap_slot(sl);
-          throw;
-        }
-        swap_slot(sl);
-      }
+    }
+    for (int i = 0; i < nbat; ++i) {
+      Hyper h = hyp;
+      for (int j = 0; j < d; ++j) h.ls[j] = ls[(b0 + i) * d + j];
+      h.kvar = kvar[b0 + i];
+      if (nbat > 1) HIPCHK(hipStreamWaitEvent(slots[i]->stream, ev_batch, 0));
+      eval_start(ws_of(i), 1, &h, grad != nullptr);
     }
     const auto t_enq = std::chrono::steady_clock::now();
     for (int i = 0; i < nbat; ++i) {
-      double* gi = grad ? grad + (b0 + i) * (d + 1) : nullptr;
-      int st;
-      if (nbat == 1) {
-        st = mll_collect(mll + b0, gi);
-      } else {
-        Slot& sl = *slots[i];
-        swap_slot(sl);
-        try {
-          st = mll_collect(mll + b0 + i, gi);
-        } catch (...) {
-          swap_slot(sl);
-          throw;
-        }
-        swap_slot(sl);
-      }
+      const int st = eval_collect(ws_of(i), 1, mll + b0 + i, grad ? grad + (b0 + i) * (d + 1) : nullptr, nullptr);
       if (status) status[b0 + i] = st;
       if (st != BOBE_OK) worst = st;
     }
@@ -1048,32 +978,23 @@ void bobe_gp::mll_submit(int slot, const double* ls, double kvar, int want_grad)
   std::lock_guard<std::mutex> lock(submit_mutex);
   use();
   ensure_slots(slot + 1);
-  const std::vector<hipStream_t>& sts = slot_stream_set();
   Hyper h = hyp;
   for (int j = 0; j < d; ++j) h.ls[j] = ls[j];
   h.kvar = kvar;
-  Slot& sl = *slots[slot];
+  EvalWs& sl = *slots[slot];
   if (sl.busy)      // its pinned inputs / workspace / results are still in use by the evaluation not yet collected
     throw Err(BOBE_ERR_STATE, "slot already has an evaluation in flight: call bobe_gp_mll_wait first");
-  sl.stream = sts[slot];
   // ordered after whatever is queued on the handle's stream (data uploads); the event is private to the slot
   if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
   HIPCHK(hipEventRecord(sl.ev, stream));
   HIPCHK(hipStreamWaitEvent(sl.stream, sl.ev, 0));
-  swap_slot(sl);
-  try {
-    mll_enqueue(h, want_grad != 0);
-  } catch (...) {
-    swap_slot(sl);
-    throw;
-  }
-  swap_slot(sl);
+  eval_start(sl, 1, &h, want_grad != 0);
   sl.busy = true;
   sl.want_grad = want_grad != 0;
 }
 
 int bobe_gp::mll_wait(int slot, double* mll, double* grad) {
-  Slot* slp = nullptr;
+  EvalWs* slp = nullptr;
   {
     std::lock_guard<std::mutex> lock(submit_mutex);    // (the slot table grows under this mutex)
     if (slot < 0 || slot >= (int)slots.size() || !slots[slot]->busy)
@@ -1081,12 +1002,12 @@ int bobe_gp::mll_wait(int slot, double* mll, double* grad) {
     slp = slots[slot];
   }
   HIPCHK(hipSetDevice(device));
-  Slot& sl = *slp;
+  EvalWs& sl = *slp;
   struct Release {                                        // the slot is free again once its stream has drained
-    Slot& s;
+    EvalWs& s;
     ~Release() { s.busy = false; }
   } release{sl};
-  return slot_collect(sl, mll, sl.want_grad ? grad : nullptr);
+  return eval_collect(sl, 1, mll, sl.want_grad ? grad : nullptr, nullptr);
 }
 
 void bobe_gp::copy_out_matrix(const double* src, double* dst, int lower_only) {
@@ -1135,11 +1056,8 @@ void bobe_gp::set_chol(const double* L, const double* alpha_in) {
 
 // the smallest L_jj of the factor in A (k_mll_terms without a right-hand side); synchronises
 double bobe_gp::min_pivot_root() {
-  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)nullptr, (const double*)A.d(), Np, Np, res.d(),
-                     (int64_t)0, (int64_t)0, (int64_t)0, (const int*)nullptr);
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(h_res, res.p, 102 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  sync();
+  mll_terms(nullptr, A.d(), res.d(), nullptr);
+  res_to_host(res.d(), h_res, 102);
   return h_res[101];
 }
 
@@ -1163,31 +1081,20 @@ int bobe_gp::mll_from_k(const double* K, int64_t n, const double* yv, double* ml
   use();
   sync();
   size_workspace(n);
-  forget_evals();                                  // (A2 / Linv2 / w2 / alpha2 hold this matrix's factor from here on)
+  forget_evals();                                  // (the handle's own workspace holds this matrix's factor from here on)
+  const FactorBufs f = own.bufs();
   const double* k_in = fetch(K, (size_t)n * n, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, k_in, n,
-                     A2.d(), Np, Np, 1);
+                     f.a, Np, Np, 1);
   HIPCHK(hipMemsetAsync(w.p, 0, (size_t)Np * sizeof(double), stream));            // (w: the padded right-hand side)
   HIPCHK(hipMemcpyAsync(w.p, yv, (size_t)n * sizeof(double),
                         is_device_ptr(yv) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(info.p, 0x7f, sizeof(int), stream));
-  potrf(A2.d(), Linv2.d(), static_cast<int*>(info.p), 1, 0, 0, nullptr, true);
-  trtri(A2.d(), Linv2.d(), Tmp.d());
-  solve_alpha(Linv2.d(), w2.d(), alpha2.d(), part.d(), 1, 0, 0, 0, w.d(), 0);
-  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w2.d(), (const double*)A2.d(), Np, Np, res.d(),
-                     (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(h_res, res.p, 102 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  sync();
-  int inf;
-  std::memcpy(&inf, h_res + 100, sizeof(int));
-  if (inf != 0x7f7f7f7f || !(h_res[101] > 0.0)) {
-    *mll = std::nan("");
-    g_err = not_pd_text(inf, h_res[101]);
-    return BOBE_NOT_PD;
-  }
-  *mll = -0.5 * h_res[0] - h_res[1] - 0.5 * (double)n * std::log(2.0 * M_PI);
-  return BOBE_OK;
+  HIPCHK(hipMemsetAsync(f.info, 0x7f, sizeof(int), stream));
+  chol_solve(f, 1, w.d());
+  mll_terms(f.w, f.a, own.res.d(), f.info);
+  res_to_host(own.res.d(), own.h_res, 102);
+  // (this entry's own rule instead of a floor: min L_jj > 0; a NaN floor fails whatever the pivot)
+  return eval_result(own.h_res, own.h_res[101] > 0.0 ? 0.0 : std::nan(""), mll, nullptr);
 }
 
 // fast_update_cholesky(L, k, k_self) (gp.py:181-197): v = L^-1 k and the new diagonal entry sqrt(k_self - v.v) (NaN when
@@ -1197,27 +1104,24 @@ void bobe_gp::chol_row_update(const double* L, int64_t n, const double* k, doubl
   sync();
   size_workspace(n);
   forget_evals();
+  const FactorBufs f = own.bufs();
   const double* l_in = fetch(L, (size_t)n * n, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, l_in, n,
-                     A2.d(), Np, Np, 0);
+                     f.a, Np, Np, 0);
   HIPCHK(hipMemsetAsync(w.p, 0, (size_t)Np * sizeof(double), stream));
   HIPCHK(hipMemcpyAsync(w.p, k, (size_t)n * sizeof(double),
                         is_device_ptr(k) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
   for (int kb = 0; kb < nb; ++kb)                      // the 16 x 16 diagonal inverses the block inverse starts from
-    hipLaunchKernelGGL(k_potf2<false>, dim3(1), dim3(256), POTF2_SMEM_BYTES, stream, A2.d(), Np, Linv2.d(), Np, kb,
-                       static_cast<int*>(info.p));
+    hipLaunchKernelGGL(k_potf2<false>, dim3(1), dim3(256), POTF2_SMEM_BYTES, stream, f.a, Np, f.linv, Np, kb, f.info);
   LAUNCH_CHECK();
-  trtri(A2.d(), Linv2.d(), Tmp.d());
-  hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), 1u), dim3(256), 0, stream, (const double*)Linv2.d(), Np, Np,
-                     (const double*)w.d(), w2.d(), (int64_t)0, (int64_t)0, (int64_t)0);
-  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w2.d(), (const double*)A2.d(), Np, Np, res.d(),
-                     (int64_t)0, (int64_t)0, (int64_t)0, (const int*)nullptr);
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(h_res, res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));      // [0] = v.v
-  HIPCHK(hipMemcpyAsync(v, w2.p, (size_t)n * sizeof(double),
+  trtri(f.a, f.linv, f.tmp);
+  hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), 1u), dim3(256), 0, stream, (const double*)f.linv, Np, Np,
+                     (const double*)w.d(), f.w, (int64_t)0, (int64_t)0, (int64_t)0);
+  mll_terms(f.w, f.a, own.res.d(), nullptr);
+  HIPCHK(hipMemcpyAsync(v, f.w, (size_t)n * sizeof(double),
                         is_device_ptr(v) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-  sync();
-  *diag_out = std::sqrt(k_self - h_res[0]);
+  res_to_host(own.res.d(), own.h_res, 2);                                                        // [0] = v.v
+  *diag_out = std::sqrt(k_self - own.h_res[0]);
 }
 
 void bobe_gp::kinv_debug(double* Kinv) {
@@ -1257,24 +1161,50 @@ struct EventPair {
 };
 }  // namespace
 
-double bobe_gp::time_potrf(int reps) {
-  if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
-  use();
-  forget_evals();                                              // (the timers factorise into the evaluation workspaces)
+// one untimed pass, then reps timed ones: prep() queues what a pass factorises, run(e0) the factorisation (e0: recorded on
+// the handle's stream just before it); the time is taken on the handle's stream
+template <typename Prep, typename Run>
+static double timed_passes(hipStream_t stream, int reps, Prep prep, Run run) {
   EventPair ev;
   double total = 0.0;
-  scale(X.d(), N, Np, hyp, XsT2.d(), Np);
-  for (int r = -1; r < reps; ++r) {                            // (pass -1 is untimed)
-    assemble_kxx(hyp, XsT2.d(), A2.d());
-    HIPCHK(hipMemsetAsync(info.p, 0x7f, sizeof(int), stream));
+  for (int r = -1; r < reps; ++r) {                            // (pass -1 is untimed: first touch of the workspace, clocks)
+    prep();
     HIPCHK(hipEventRecord(ev.e0, stream));
-    potrf(A2.d(), Linv2.d(), static_cast<int*>(info.p));
+    run(ev.e0);
     HIPCHK(hipEventRecord(ev.e1, stream));
     const double t = ev.ms();
     if (r >= 0) total += t;
   }
   return total / reps;
 }
+
+// B factorisations through one launch sequence on the handle's stream: the handle's own workspace (B = 1, the plain call)
+// or the lock-step batch (the fit's restarts from lockstep_min_n points up)
+double bobe_gp::time_potrf_wide(EvalWs& ws, int B, int reps) {
+  if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  use();
+  forget_evals();                                              // (the timers factorise into the evaluation workspaces)
+  if (ws.width > 1) ensure_batch(B);
+  UseWs use_ws(*this, ws);
+  const FactorBufs f = ws.bufs();
+  const Hyper* hdev = nullptr;
+  if (ws.width > 1) {
+    for (int b = 0; b < B; ++b) ws.h_hyp[b] = hyp;
+    HIPCHK(hipMemcpyAsync(ws.hyp.p, ws.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
+    hdev = static_cast<const Hyper*>(ws.hyp.p);
+  }
+  scale(X.d(), N, Np, hyp, f.xst, Np, hdev, B, f.xs);
+  return timed_passes(
+      stream, reps,
+      [&] {
+        assemble_kxx(hyp, f.xst, f.a, hdev, B, f.xs, f.mat);
+        HIPCHK(hipMemsetAsync(f.info, 0x7f, (size_t)B * sizeof(int), stream));
+      },
+      [&](hipEvent_t) { potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag); });
+}
+
+double bobe_gp::time_potrf(int reps) { return time_potrf_wide(own, 1, reps); }
+double bobe_gp::time_potrf_lockstep(int B, int reps) { return time_potrf_wide(batch, B, reps); }
 
 // B factorisations in flight at once, one evaluation slot each (the state of the fit's concurrent restarts):
 // device time from the first to the last factorisation kernel, averaged over reps, for all B together
@@ -1283,64 +1213,31 @@ double bobe_gp::time_potrf_batch(int B, int reps) {
   use();
   forget_evals();
   ensure_slots(B);
-  const std::vector<hipStream_t>& sts = slot_stream_set();
-  EventPair ev;
   std::vector<hipEvent_t> done(B);
   for (auto& e : done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  double total = 0.0;
-  for (int r = -1; r < reps; ++r) {                            // (pass -1 is untimed)
-    for (int i = 0; i < B; ++i) {      // K(X,X) of every slot, on the handle's stream
-      Slot& sl = *slots[i];
-      scale(X.d(), N, Np, hyp, sl.XsT2.d(), Np);
-      assemble_kxx(hyp, sl.XsT2.d(), sl.A2.d());
-      HIPCHK(hipMemsetAsync(sl.info.p, 0x7f, sizeof(int), stream));
-    }
-    HIPCHK(hipEventRecord(ev.e0, stream));
-    for (int i = 0; i < B; ++i) {
-      Slot& sl = *slots[i];
-      sl.stream = sts[i];
-      HIPCHK(hipStreamWaitEvent(sl.stream, ev.e0, 0));
-      swap_slot(sl);
-      try {
-        potrf(A2.d(), Linv2.d(), static_cast<int*>(info.p));
-      } catch (...) {
-        swap_slot(sl);
-        throw;
-      }
-      swap_slot(sl);
-      HIPCHK(hipEventRecord(done[i], sl.stream));
-      HIPCHK(hipStreamWaitEvent(stream, done[i], 0));
-    }
-    HIPCHK(hipEventRecord(ev.e1, stream));
-    const double t = ev.ms();
-    if (r >= 0) total += t;
-  }
+  const double ms = timed_passes(
+      stream, reps,
+      [&] {
+        for (int i = 0; i < B; ++i) {      // K(X,X) of every slot, on the handle's stream
+          const FactorBufs f = slots[i]->bufs();
+          scale(X.d(), N, Np, hyp, f.xst, Np);
+          assemble_kxx(hyp, f.xst, f.a);
+          HIPCHK(hipMemsetAsync(f.info, 0x7f, sizeof(int), stream));
+        }
+      },
+      [&](hipEvent_t e0) {
+        for (int i = 0; i < B; ++i) {
+          EvalWs& sl = *slots[i];
+          const FactorBufs f = sl.bufs();
+          HIPCHK(hipStreamWaitEvent(sl.stream, e0, 0));
+          {
+            UseWs use_ws(*this, sl);
+            potrf(f.a, f.linv, f.info, 1, 0, 0, f.diag);
+          }
+          HIPCHK(hipEventRecord(done[i], sl.stream));
+          HIPCHK(hipStreamWaitEvent(stream, done[i], 0));
+        }
+      });
   for (auto& e : done) (void)hipEventDestroy(e);
-  return total / reps;
-}
-
-// the same B factorisations advancing in lock step through one batched launch sequence (the fit's restarts from
-// lockstep_min_n points up)
-double bobe_gp::time_potrf_lockstep(int B, int reps) {
-  if (!have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
-  use();
-  forget_evals();
-  ensure_batch(B);
-  const int64_t mat = Np * Np, xs = (int64_t)d * Np;
-  for (int b = 0; b < B; ++b) bw.h_hyp[b] = hyp;
-  HIPCHK(hipMemcpyAsync(bw.hyp.p, bw.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
-  const Hyper* hdev = static_cast<const Hyper*>(bw.hyp.p);
-  EventPair ev;
-  double total = 0.0;
-  scale(X.d(), N, Np, hyp, bw.XsT.d(), Np, hdev, B, xs);
-  for (int r = -1; r < reps; ++r) {                            // (pass -1 is untimed: first touch of the workspace, clocks)
-    assemble_kxx(hyp, bw.XsT.d(), bw.A.d(), hdev, B, xs, mat);
-    HIPCHK(hipMemsetAsync(bw.info.p, 0x7f, (size_t)B * sizeof(int), stream));
-    HIPCHK(hipEventRecord(ev.e0, stream));
-    potrf(bw.A.d(), bw.Linv.d(), static_cast<int*>(bw.info.p), B, mat, mat, bw.diag.d());
-    HIPCHK(hipEventRecord(ev.e1, stream));
-    const double t = ev.ms();
-    if (r >= 0) total += t;
-  }
-  return total / reps;
+  return ms;
 }

@@ -252,7 +252,7 @@ struct SweepReq {
   SweepKeep* keep = nullptr;
 };
 
-// What an evaluation workspace (a lock-step batch slot, an evaluation slot, the single evaluation's own A2 / Linv2 / ...)
+// What a member of an evaluation workspace (bobe_gp::EvalWs: the lock-step batch, an evaluation slot, the handle's own)
 // holds once its evaluation was collected: the factor of `h` on data generation `gen` at padded size `Np`, and the
 // factorisation's info word and smallest pivot root (res[100], res[101]).  The pipeline of an evaluation is factor_into's
 // on the same data (same bits in every form), and what follows it - lauum, k_mll_grad_reduce / k_mll_terms - writes only
@@ -334,7 +334,9 @@ struct bobe_gp {
   int64_t chunk = 8192;
   bool chunk_set = false;       // bobe_gp_set_chunk was called: the caller's chunk holds for the substitution path too
 
-  DBuf X, y, XsT, XsT2, A, Linv, A2, Linv2, Tmp, alpha, w, alpha2, w2, part, gpart, res, info, probs, flags, diag;
+  // the data, the installed factor (XsT, A, Linv, alpha, w) and the scratch of what works on it - bobe_gp_factor, the sweep,
+  // append, set_chol, bobe_gp_loo.  The evaluations have workspaces of their own (EvalWs below).
+  DBuf X, y, XsT, A, Linv, Tmp, alpha, w, part, gpart, res, info, probs, diag;
   int num_cus = 0;
   // sweep / predict workspace
   DBuf wg_ws;     // workspace of bobe_gp_wip_grad's few-candidates path
@@ -392,71 +394,99 @@ struct bobe_gp {
   // strips per workgroup of the panel launch with `rr` blocks below the diagonal block (chol_kernels.hpp, panel_workgroups)
   int panel_strips(int B, int rr) const;
 
-  // ---- evaluation slots of bobe_gp_mll_batch / _submit: a private stream + workspace per concurrently evaluated
-  // hyper-parameter vector.  Slot 0 is the handle's own (stream, XsT2, A2, ...) set; a slot is made current by
-  // swapping its members in, so every pipeline stage runs unchanged on it.
-  // Replayable evaluation pipeline (launch-bound sizes): the kernels of one value(+gradient) evaluation captured
-  // into a hipGraph per (workspace, data generation, with/without gradient).  The hyper-parameters reach the
-  // kernels through a device-resident copy that the graph's first node refreshes from pinned host memory.
+  // ---- evaluation workspaces.  One value(+gradient) evaluation of a hyper-parameter vector needs the scaled coordinates,
+  // K -> L, Linv, a scratch matrix, w, alpha, the partial sums, the results and the factorisation's info word and diagonal
+  // scratch blocks.  An EvalWs holds that for `width` members; member b lives at b * (elements per member) of every buffer.
+  // The handle has three kinds: `own` (width 1, the handle's stream: bobe_gp_mll, the LOO objective, the free functions),
+  // `slots` (width 1 each, a private stream: bobe_gp_mll_submit / _wait and the batches below BOBE_LOCKSTEP_MIN_N) and
+  // `batch` (up to BOBE_MAX_MLL_SLOTS members advancing through ONE launch sequence on the handle's stream, every kernel
+  // taking the member from its last grid dimension).
+  // Replayable pipeline (launch-bound sizes): the kernels of one evaluation captured into a hipGraph per (workspace,
+  // with / without gradient).  The hyper-parameters reach the kernels through the workspace's device copy, which the
+  // graph's first node refreshes from the pinned one.
   struct EvalGraph {
     hipGraphExec_t exec[2] = {nullptr, nullptr};    // [want_grad]
     std::array<const void*, 16> sig[2] = {};        // every address / size the captured kernels were given
-    Hyper* h_hyp = nullptr;                         // pinned
-    DBuf hyp_dev;
   };
-  struct Slot {
-    hipStream_t stream = nullptr;
-    DBuf XsT2, A2, Linv2, Tmp, alpha2, w2, part, gpart, res, info, flags, diag;
+  // what the factorisation front (factor_into / chol_solve) works on: a workspace's buffers with its member strides, or
+  // the installed factor's with stride 0
+  struct FactorBufs {
+    double *xst, *a, *linv, *tmp, *w, *alpha, *part, *diag;
+    int* info;
+    int64_t mat, vec, xs, prt;
+  };
+  struct EvalWs {
+    explicit EvalWs(int width_) : width(width_), tag(width_), floor(width_, 0.0) {}
+    const int width;                 // members it may hold
+    int cap = 0;                     // members [0, cap) fit the buffers at Np (ensure)
+    int64_t Np = 0;
+    int nb = 0, d = 0;
+    DBuf XsT, A, Linv, Tmp, w, alpha, part, gpart, res, info, diag, hyp;
+    double* h_res = nullptr;         // pinned [width][128]: [0] y^T K^-1 y, [1] sum log L_ii, [2..2+d] gradient, [100] the
+                                     // factorisation's info word, [101] min L_jj
+    Hyper* h_hyp = nullptr;          // pinned [width] (the same allocation)
     EvalGraph eg;
-    double* h_res = nullptr;
+    std::vector<bobe::EvalTag> tag;  // per member: what it holds
+    std::vector<double> floor;       // per member: the rank test's floor of the evaluation in flight (read at collect)
+    int aside_first = 1 << 30;       // set by potrf(defer_diag = true) on this workspace, consumed by the next trtri()
+    const double* aside_dg = nullptr;
+    // evaluation slots only: the private stream (the handle's, of slot_stream_set) and the state of submit / wait
+    hipStream_t stream = nullptr;
     hipEvent_t ev = nullptr;
     bool busy = false, want_grad = false;
-    bobe::EvalTag tag;
+    // elements per member
+    int64_t mat() const { return Np * Np; }
+    int64_t vec() const { return Np; }
+    int64_t xs() const { return (int64_t)d * Np; }
+    int64_t prt() const { return (int64_t)nb * Np; }
+    int64_t gps() const { return (int64_t)(2 * nb) * (2 * nb + 1) / 2 * (bobe::MAX_D + 1); }
+    // the strides the launches are given: a width-1 workspace is the plain call (B = 1, stride 0)
+    int64_t stride(int64_t per_member) const { return width > 1 ? per_member : 0; }
+    FactorBufs bufs() const {
+      return {XsT.d(), A.d(), Linv.d(), Tmp.d(), w.d(), alpha.d(), part.d(), diag.d(), static_cast<int*>(info.p),
+              stride(mat()), stride(vec()), stride(xs()), stride(prt())};
+    }
+    void ensure(const bobe_gp& g, int B);      // room for B members at the handle's Np / nb / d
+    void release();
   };
-  EvalGraph eg;                    // of the handle's own workspace (swapped with a slot's like the buffers)
-  bobe::EvalTag tag2;              // what the handle's own A2 / Linv2 / alpha2 / w2 / XsT2 hold (swapped like them)
-  std::array<const void*, 16> eval_signature() const {
-    return {XsT2.p, A2.p, Linv2.p, Tmp.p, w2.p, alpha2.p, part.p, gpart.p, res.p, info.p, X.p, y.p, probs.p,
-            static_cast<const void*>(h_res), reinterpret_cast<const void*>(static_cast<uintptr_t>(N)),
-            static_cast<const void*>(stream)};
+  EvalWs own{1}, batch{BOBE_MAX_MLL_SLOTS};
+  std::vector<EvalWs*> slots;                // (reserved once: bobe_gp_mll_wait reads it without the submit mutex)
+  // The workspace the stage functions run on: potrf / trtri keep their hand-over (aside_*) there, and on a slot the
+  // handle's `stream` is the slot's.  UseWs makes one current for a scope; nothing else of the handle changes.
+  EvalWs* cur = &own;
+  bool on_slot() const { return cur->stream != nullptr; }
+  struct UseWs {
+    bobe_gp& g;
+    EvalWs* const prev;
+    const hipStream_t prev_stream;
+    UseWs(bobe_gp& g_, EvalWs& ws) : g(g_), prev(g_.cur), prev_stream(g_.stream) {
+      g.cur = &ws;
+      if (ws.stream) g.stream = ws.stream;
+    }
+    ~UseWs() {
+      g.cur = prev;
+      g.stream = prev_stream;
+    }
+    UseWs(const UseWs&) = delete;
+    UseWs& operator=(const UseWs&) = delete;
+  };
+  FactorBufs state_bufs() const {
+    return {XsT.d(), A.d(), Linv.d(), Tmp.d(), w.d(), alpha.d(), part.d(), diag.d(), static_cast<int*>(info.p), 0, 0, 0, 0};
   }
-  void mll_enqueue_body(const Hyper& h, bool want_grad, const Hyper* hdev);
-  std::vector<Slot*> slots;
   std::vector<hipStream_t> slot_streams;     // one per evaluation slot, created on first use
   const std::vector<hipStream_t>& slot_stream_set();
   hipEvent_t ev_batch = nullptr;
-  bool in_slot = false;
-  void swap_slot(Slot& s) {
-    std::swap(stream, s.stream);
-    std::swap(XsT2, s.XsT2); std::swap(A2, s.A2); std::swap(Linv2, s.Linv2); std::swap(Tmp, s.Tmp);
-    std::swap(alpha2, s.alpha2); std::swap(w2, s.w2); std::swap(part, s.part); std::swap(gpart, s.gpart);
-    std::swap(res, s.res); std::swap(info, s.info); std::swap(flags, s.flags); std::swap(diag, s.diag);
-    std::swap(h_res, s.h_res);
-    std::swap(eg, s.eg);
-    std::swap(tag2, s.tag);
-    in_slot = !in_slot;
-  }
-  // Lock-step batch workspace (bobe_gp_mll_batch; from BOBE_LOCKSTEP_MIN_N points up when that is set): the B evaluations of a batch go
-  // through ONE launch sequence on the handle's stream, every kernel taking the slot from its last grid dimension;
-  // slot b lives at offset b * stride of each of these contiguous buffers.
-  struct BatchWs {
-    int cap = 0;
-    int64_t Np = 0;
-    DBuf A, Linv, Tmp, XsT, w, alpha, part, gpart, res, info, hyp, diag;
-    Hyper* h_hyp = nullptr;      // pinned [BOBE_MAX_MLL_SLOTS]
-    double* h_res = nullptr;     // pinned [BOBE_MAX_MLL_SLOTS][128]
-    std::array<bobe::EvalTag, BOBE_MAX_MLL_SLOTS> tag;
-  } bw;
-  int64_t gpart_stride() const { return (int64_t)(2 * nb) * (2 * nb + 1) / 2 * (bobe::MAX_D + 1); }
-  void ensure_batch(int B);
-  void mll_lockstep_enqueue(int B, const Hyper* hs, bool want_grad);
-  int mll_lockstep_collect(int B, double* mll, double* grad, int* status);
-  std::mutex submit_mutex;          // serialises bobe_gp_mll_submit (the slot swap is not re-entrant)
+  std::mutex submit_mutex;          // serialises bobe_gp_mll_submit (it makes a slot current on the handle)
   void ensure_slots(int n);
-  void mll_enqueue(const Hyper& h, bool want_grad);   // (records what the current workspace will hold: tag2)
-  void mll_enqueue_pipeline(const Hyper& h, bool want_grad);
-  int slot_collect(Slot& sl, double* mll, double* grad);
-  int mll_collect(double* mll, double* grad);
+  void ensure_batch(int B);
+  // the launches of B evaluations on ws (hdev: the device copy of the hyper-parameters, refreshed first; NULL: the kernels
+  // take hs[0] by value); eval_start picks the form (plain, graph replay, lock step) and keeps the members' records
+  void eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev);
+  void eval_replay(EvalWs& ws, const Hyper* hs, bool want_grad);
+  void eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad);
+  int eval_collect(EvalWs& ws, int B, double* mll, double* grad, int* status);
+  // hr: an evaluation's pinned results; NaN outputs, g_err and BOBE_NOT_PD when the factorisation failed or a pivot is below floor
+  int eval_result(const double* hr, double floor, double* mll, double* grad) const;
   int mll_batch(int64_t B, const double* ls, const double* kvar, double* mll, double* grad, int* status);
   void mll_submit(int slot, const double* ls, double kvar, int want_grad);
   int mll_wait(int slot, double* mll, double* grad);
@@ -529,8 +559,6 @@ struct bobe_gp {
   // defer_diag: leave the L_kk scratch blocks where they are; the trtri() that follows puts them in place (one launch less)
   void potrf(double* a, double* linv, int* info_dev, int B = 1, int64_t bsA = 0, int64_t bsL = 0, double* dg = nullptr,
              bool defer_diag = false);
-  int aside_first = 1 << 30;       // set by potrf(defer_diag = true), consumed by the next trtri()
-  const double* aside_dg = nullptr;
   void trtri(double* a, double* linv, double* tmp, int B = 1, int64_t bsA = 0, int64_t bsL = 0, int64_t bsT = 0);
   int lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
             const Hyper* hdev = nullptr, double* gp_out = nullptr, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
@@ -538,8 +566,12 @@ struct bobe_gp {
   // wv = Linv rhs, al = Linv^T wv (rhs: y unless given; bsY: its stride per batch member)
   void solve_alpha(const double* linv, double* wv, double* al, double* prt, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
                    int64_t bsP = 0, const double* rhs = nullptr, int64_t bsY = 0);
-  void factor_into(const Hyper& h, double* xst, double* a, double* linv, double* wv, double* al,
-                   const Hyper* hdev = nullptr);
+  // scale, K(X, X), chol_solve on f's buffers; chol_solve: potrf, trtri, w / alpha of the right-hand side (y unless given)
+  void factor_into(const Hyper& h, const FactorBufs& f, const Hyper* hdev = nullptr, int B = 1);
+  void chol_solve(const FactorBufs& f, int B = 1, const double* rhs = nullptr);
+  // k_mll_terms of one factor (w may be NULL: the pivots only) into res; res_to_host: its first n doubles, synchronised
+  void mll_terms(const double* wv, const double* a, double* res_dev, const int* info_dev);
+  void res_to_host(const double* res_dev, double* h, int n);
   std::string not_pd_text(int inf, double min_diag) const;
   // gp_mll(k, train_y, num_points) / fast_update_cholesky(L, k, k_self) on caller-supplied matrices (gp.py:170-197)
   void size_workspace(int64_t n);
@@ -561,6 +593,7 @@ struct bobe_gp {
   double time_potrf(int reps);
   double time_potrf_batch(int B, int reps);
   double time_potrf_lockstep(int B, int reps);
+  double time_potrf_wide(EvalWs& ws, int B, int reps);
   void fill(double* p, int64_t n, double v);
 
   // ---- gp_sweep.hip

@@ -58,57 +58,48 @@ int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) 
   return BOBE_OK;
 }
 
-// bobe_gp_loo_objective: bobe_gp_mll's pipeline on the evaluation workspace up to Linv2 / alpha2, then
+// bobe_gp_loo_objective: the front of bobe_gp_mll's pipeline on the handle's own evaluation workspace (factor_into: up to
+// Linv / alpha), then
 //   value     a, the per-point terms, the fixed-order sum                                    (loo_terms)
-//   gradient  K^-1 stored by the existing lauum into Tmp, B = diag(sqrt c) K^-1 into A2 (the factor L is no longer
+//   gradient  K^-1 stored by the existing lauum into Tmp, B = diag(sqrt c) K^-1 into A (the factor L is no longer
 //             needed), w = B^T (b / sqrt c), the dense B^T B tiles with the gradient epilogue, k_mll_grad_reduce.
-// The workspace ends up holding no factor (A2 is overwritten): its record is cleared, bobe_gp_factor will not adopt it.
+// The workspace ends up holding no factor (A is overwritten): its record is cleared, bobe_gp_factor will not adopt it.
 int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
   use();
-  tag2.clear();
+  EvalWs& ws = own;
+  const FactorBufs f = ws.bufs();
+  ws.tag[0].clear();
   const double floor_h = pivot_floor(h);
-  factor_into(h, XsT2.d(), A2.d(), Linv2.d(), w2.d(), alpha2.d());
-  // the info word and the smallest pivot's root (res[100], res[101]), while A2 still holds L
-  hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)w2.d(), (const double*)A2.d(), Np, Np, res.d(),
-                     (int64_t)0, (int64_t)0, (int64_t)0, (const int*)info.p);
-  loo_terms(Linv2.d(), alpha2.d(), grad != nullptr, res.d() + 102);
+  factor_into(h, f);
+  // the info word and the smallest pivot's root (res[100], res[101]), while A still holds L
+  mll_terms(f.w, f.a, ws.res.d(), f.info);
+  loo_terms(f.linv, f.alpha, grad != nullptr, ws.res.d() + 102);
   if (grad) {
-    double* ws = loo_ws.d();
-    (void)lauum(h, Linv2.d(), alpha2.d(), XsT2.d(), Tmp.d());      // K^-1's lower tiles -> Tmp (its partial sums go unused)
+    double* lw = loo_ws.d();
+    (void)lauum(h, f.linv, f.alpha, f.xst, f.tmp, nullptr, ws.gpart.d());      // K^-1's lower tiles -> Tmp (its partial sums go unused)
     const int nt32 = (int)(Np / 32);
-    hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2)), dim3(256), 0, stream, (const double*)Tmp.d(), Np,
-                       (const double*)(ws + 4 * Np), A2.d());
-    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Np / 64), (unsigned)nb, 1u), dim3(256), 0, stream, (const double*)A2.d(), Np,
-                       0, (const double*)(ws + 5 * Np), part.d(), Np, (int64_t)0, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2)), dim3(256), 0, stream, (const double*)f.tmp, Np,
+                       (const double*)(lw + 4 * Np), f.a);
+    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Np / 64), (unsigned)nb, 1u), dim3(256), 0, stream, (const double*)f.a, Np,
+                       0, (const double*)(lw + 5 * Np), part.d(), Np, (int64_t)0, (int64_t)0, (int64_t)0);
     hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), 1u), dim3(256), 0, stream, (const double*)part.d(), Np,
-                       nb, 0, Np, ws + 6 * Np, (int64_t)0, (int64_t)0);
+                       nb, 0, Np, lw + 6 * Np, (int64_t)0, (int64_t)0);
     const LauumTiling t = lauum_tiling(nb);       // (the dense B^T B on the tiles and the tile core K^-1 was formed on)
     prof_begin(BOBE_PROF_LAUUM);
     with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT, auto GL) {
       hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(t.ntiles), dim3(256),
-                         (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)A2.d(), Np, Np, N,
-                         (const double*)alpha2.d(), (const double*)(ws + 6 * Np), (const double*)XsT2.d(), Np, h, gpart.d());
+                         (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)f.a, Np, Np, N,
+                         (const double*)f.alpha, (const double*)(lw + 6 * Np), (const double*)f.xst, Np, h, ws.gpart.d());
     });
     prof_end(BOBE_PROF_LAUUM);
     // (d + 1 workgroups: the gradient components; the scalar terms were reduced above)
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1), dim3(256), 0, stream, (const double*)gpart.d(), t.ntiles,
-                       dcap_of(d) + 1, d, dcap_of(d), res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np,
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1), dim3(256), 0, stream, (const double*)ws.gpart.d(), t.ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np,
                        (const int*)nullptr, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0);
     LAUNCH_CHECK();
   }
-  HIPCHK(hipMemcpyAsync(h_res, res.p, 103 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  sync();
-  int inf;
-  std::memcpy(&inf, h_res + 100, sizeof(int));
-  if (inf != 0x7f7f7f7f || !pivots_resolved(h_res[101], floor_h)) {
-    *loo = std::nan("");
-    if (grad)
-      for (int j = 0; j <= d; ++j) grad[j] = std::nan("");
-    g_err = not_pd_text(inf, h_res[101]);
-    return BOBE_NOT_PD;
-  }
-  *loo = h_res[102];
-  if (grad)
-    for (int j = 0; j <= d; ++j) grad[j] = h_res[2 + j];
-  return BOBE_OK;
+  res_to_host(ws.res.d(), ws.h_res, 103);
+  const int st = eval_result(ws.h_res, floor_h, loo, grad);      // (bobe_gp_mll's rule; the value is the LOO sum instead)
+  if (st == BOBE_OK) *loo = ws.h_res[102];
+  return st;
 }

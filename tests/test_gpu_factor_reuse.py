@@ -258,3 +258,80 @@ def test_the_process_switch_turns_adoption_off():
                              timeout=300)
         assert out.returncode == 0, out.stderr[-2000:]
         assert f"source {want}" in out.stdout, (env, out.stdout)
+
+
+def _mll(h, ls, kv, d):
+    L, lib = _lib()
+    m, g = C.c_double(), np.empty(d + 1)
+    L.check(lib.bobe_gp_mll(h, _p(ls), float(kv), C.byref(m), _p(g)), "mll")
+    return m.value, g
+
+
+def _walk(batch_on_slots):
+    """One handle through a change of Np, then a change of N at the same Np; after each, an evaluation on slot 1, a batch of
+    three and a single evaluation, then bobe_gp_factor at one theta of each.  Runs in a process of its own (__main__ below)."""
+    L, lib = _lib()
+    d, noise = 3, 1e-6
+    ls, kv = _thetas(d, 5, seed=12)
+    rng = np.random.default_rng(13)
+    cand, Z = np.ascontiguousarray(rng.uniform(size=(256, d))), np.ascontiguousarray(rng.uniform(size=(32, d)))
+    # theta 2 is member 1 of the batch: batch member 1 in lock step; slot 1 when the batch runs on slots (member i takes slot
+    # i), where it overwrote theta 0's factor - no workspace holds theta 0 then.  Theta 4 stays in the handle's own workspace.
+    want = {2: SLOT if batch_on_slots else BATCH, 0: FACTORISED if batch_on_slots else SLOT, 4: SINGLE}
+    X0, y0 = _problem(200, d, seed=14)            # Np 256
+    X1, y1 = _problem(300, d, seed=15)            # Np 384: every workspace reallocates, a captured graph's signature is stale
+    X2, y2 = _problem(302, d, seed=15)            # the same rows and two more: Np stays, only N changes
+    assert np.array_equal(X2[:300], X1)
+    h = _handle(X0, y0, noise)
+    try:
+        for step, (X, y) in enumerate(((X0, y0), (X1, y1), (X2, y2))):
+            n = X.shape[0]
+            if step == 1:
+                L.check(lib.bobe_gp_set_data(h, _p(X), _p(y), n), "set_data")
+            elif step == 2:
+                L.check(lib.bobe_gp_append(h, _p(np.ascontiguousarray(X[300:])), 2, _p(y)), "append")
+            got = {}
+            m, g = C.c_double(), np.empty(d + 1)
+            L.check(lib.bobe_gp_mll_submit(h, 1, _p(ls[0]), float(kv[0]), 1), "submit")
+            L.check(lib.bobe_gp_mll_wait(h, 1, C.byref(m), _p(g)), "wait")
+            got[0] = (m.value, g)
+            mb, gb, st = np.empty(3), np.empty((3, d + 1)), np.zeros(3, np.int32)
+            L.check(lib.bobe_gp_mll_batch(h, 3, _p(ls[1:4]), _p(kv[1:4]), _p(mb), _p(gb), C.c_void_p(st.ctypes.data)), "batch")
+            assert (st == 0).all()
+            for k in range(3):
+                got[1 + k] = (mb[k], gb[k])
+            got[4] = _mll(h, ls[4], kv[4], d)
+            ref = _handle(X, y, noise)
+            try:
+                for k in range(5):
+                    mr, gr = _mll(ref, ls[k], kv[k], d)
+                    assert got[k][0] == mr and np.array_equal(got[k][1], gr), (step, k, got[k], mr, gr)
+            finally:
+                lib.bobe_gp_destroy(ref)
+            for k in (2, 0, 4):
+                st_, txt, src = _factor(h, ls[k], kv[k], noise)
+                assert (st_, src) == (0, want[k]), (step, k, st_, src)
+                fst, ftxt, fresh = _fresh(X, y, ls[k], kv[k], noise, cand, Z)
+                assert (st_, txt) == (fst, ftxt)
+                _same(_state(h, n, cand, Z), fresh)
+    finally:
+        lib.bobe_gp_destroy(h)
+    print("walk ok")
+
+
+@pytest.mark.parametrize("env", [{}, {"BOBE_LOCKSTEP_MIN_N": "100000"}], ids=["lockstep", "slots"])
+def test_one_handle_keeps_its_workspaces_right_across_a_change_of_np_and_of_n(env):
+    """set_data to another Np, then an append that changes N alone: the slot, the batch and the handle's own workspace must
+    each return the bits of bobe_gp_mll on a fresh handle and hand bobe_gp_factor the bits of a fresh factorisation.  With
+    BOBE_LOCKSTEP_MIN_N above the sizes the batch runs on the evaluation slots (as graph replays at these sizes).  The library
+    reads its environment once per process: each form runs in a child."""
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "walk", "slots" if env else "lockstep"],
+                         env=dict(os.environ, **env), cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
+    assert "walk ok" in out.stdout
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+    assert sys.argv[1] == "walk"
+    _walk(sys.argv[2] == "slots")
