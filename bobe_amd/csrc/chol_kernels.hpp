@@ -949,7 +949,7 @@ __global__ __launch_bounds__(256, 2) void k_lauum_tiles32(const double* __restri
 // ---- K^-1 = Linv^T Linv fused with the MLL gradient reduction ------------------------------------------
 // lower T x T tile (ti >= tj): Kinv = sum_{k >= ti*T} Linv[k][ti]^T Linv[k][tj];  W = alpha alpha^T - Kinv.
 // partial[tile*(DCAP+1) + j] = sum_ab W_ab dK_ab/dlog ls_j (j < d), [DCAP] = sum_ab W_ab Kt_ab,
-// off-diagonal tiles weighted x2.  Optionally stores Kinv (lower tiles) for tests.
+// off-diagonal tiles weighted x2.  Optionally stores Kinv (lower tiles, slot stride bsK): tests, and the LOO objective.
 // from_kinv: the tiles of K^-1 are already in Kinv (k_lauum_tiles, slot stride bsK): only the gradient epilogue runs, each
 // thread on the elements it would own after the GEMM - the partial sums are the fused kernel's, bit for bit.
 // GLDS: the tile core as in k_syrk_trail; the host asks for it on 64 x 64 tiles only.
@@ -980,7 +980,7 @@ __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict_
   } else {
     acc_zero(acc);
     tile_gemm<GLDS, RC, RC, T>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np, smem);
-    if (Kinv) store_tile<T, T>(acc, Kinv, ldk, (int64_t)ti * T, (int64_t)tj * T, 1.0, 0.0);
+    if (Kinv) store_tile<T, T>(acc, Kinv + slot * bsK, ldk, (int64_t)ti * T, (int64_t)tj * T, 1.0, 0.0);
   }
   // stage coordinates and alpha in the (now free) GEMM LDS
   double* xa = smem;                  // [d][T]

@@ -227,6 +227,16 @@ int bobe_gp_loo_objective(bobe_gp_t* g, const double* ls, double kvar, double* l
   API_END
 }
 
+int bobe_gp_loo_objective_batch(bobe_gp_t* g, int64_t B, const double* ls, const double* kvar, double* loo, double* grad,
+                                int* status) {
+  API_BEGIN
+  NEED(g && ls && kvar && loo, "NULL argument");
+  NEED(B >= 1, "B must be >= 1");
+  if (!g->have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  return g->loo_batch(B, ls, kvar, loo, grad, status);
+  API_END
+}
+
 int bobe_gp_mll_batch(bobe_gp_t* g, int64_t B, const double* ls, const double* kvar, double* mll, double* grad,
                       int* status) {
   API_BEGIN

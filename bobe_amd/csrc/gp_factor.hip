@@ -203,12 +203,13 @@ void bobe_gp::EvalWs::ensure(const bobe_gp& g, int B) {
   gpart.ensure(n * gps());
   res.ensure(n * 128);
   diag.ensure(n * nb * TILE * TILE);
+  loo.ensure(n * lvs());
   info.ensure((size_t)width * sizeof(int));
   hyp.ensure((size_t)width * sizeof(Hyper));
 }
 
 void bobe_gp::EvalWs::release() {
-  for (DBuf* b : {&XsT, &A, &Linv, &Tmp, &w, &alpha, &part, &gpart, &res, &info, &diag, &hyp}) b->release();
+  for (DBuf* b : {&XsT, &A, &Linv, &Tmp, &w, &alpha, &part, &gpart, &res, &info, &diag, &hyp, &loo}) b->release();
   for (hipGraphExec_t& e : eg.exec) {
     if (e) (void)hipGraphExecDestroy(e);
     e = nullptr;
@@ -586,9 +587,10 @@ void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, in
 // scratch (an Np x Np matrix per slot, stride bsS): small launches - fewer 64 x 64 tiles than four per CU - form K^-1 on
 // 32 x 32 tiles into it first (k_lauum_tiles) and run the gradient epilogue from there: N = 1024 in a batch of four,
 // 77 -> 36 us (the fused launch is as long as its longest tile, K = 1024 on one CU).  Same partial sums, same bits.
+// bsK: the member stride of kinv_out (the batched LOO objective keeps every member's K^-1).
 int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
                    const Hyper* hdev, double* gp_out, int B, int64_t bsL, int64_t bsV, int64_t bsX, int64_t bsP,
-                   double* scratch, int64_t bsS) {
+                   double* scratch, int64_t bsS, int64_t bsKout) {
   // (the tile size fixes the order of the gradient's partial sums: it depends on N only, so that an evaluation
   // returns the same bits alone, on a slot and in a batch)
   const LauumTiling t = lauum_tiling(nb);
@@ -596,7 +598,7 @@ int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const d
   double* gpo = gp_out ? gp_out : gpart.d();
   const bool split = t.small && scratch && !kinv_out && B * ntiles < 4 * std::max(num_cus, 1);
   double* kio = split ? scratch : kinv_out;
-  const int64_t bsK = split ? bsS : 0;
+  const int64_t bsK = split ? bsS : bsKout;
   prof_begin(BOBE_PROF_LAUUM);
   if (split) {
     hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, linv, Np, Np, scratch, Np,

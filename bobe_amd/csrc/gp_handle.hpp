@@ -400,7 +400,7 @@ struct bobe_gp {
   // The handle has three kinds: `own` (width 1, the handle's stream: bobe_gp_mll, the LOO objective, the free functions),
   // `slots` (width 1 each, a private stream: bobe_gp_mll_submit / _wait and the batches below BOBE_LOCKSTEP_MIN_N) and
   // `batch` (up to BOBE_MAX_MLL_SLOTS members advancing through ONE launch sequence on the handle's stream, every kernel
-  // taking the member from its last grid dimension).
+  // taking the member from its last grid dimension: bobe_gp_mll_batch, bobe_gp_loo_objective_batch).
   // Replayable pipeline (launch-bound sizes): the kernels of one evaluation captured into a hipGraph per (workspace,
   // with / without gradient).  The hyper-parameters reach the kernels through the workspace's device copy, which the
   // graph's first node refreshes from the pinned one.
@@ -422,8 +422,10 @@ struct bobe_gp {
     int64_t Np = 0;
     int nb = 0, d = 0;
     DBuf XsT, A, Linv, Tmp, w, alpha, part, gpart, res, info, diag, hyp;
+    DBuf loo;                        // the LOO objective's seven vectors per member (gp_loo.hip): diag K^-1, mean, var, lpd,
+                                     // sqrt c, b / sqrt c, w
     double* h_res = nullptr;         // pinned [width][128]: [0] y^T K^-1 y, [1] sum log L_ii, [2..2+d] gradient, [100] the
-                                     // factorisation's info word, [101] min L_jj
+                                     // factorisation's info word, [101] min L_jj, [102] the LOO sum (LOO evaluations)
     Hyper* h_hyp = nullptr;          // pinned [width] (the same allocation)
     EvalGraph eg;
     std::vector<bobe::EvalTag> tag;  // per member: what it holds
@@ -440,6 +442,7 @@ struct bobe_gp {
     int64_t xs() const { return (int64_t)d * Np; }
     int64_t prt() const { return (int64_t)nb * Np; }
     int64_t gps() const { return (int64_t)(2 * nb) * (2 * nb + 1) / 2 * (bobe::MAX_D + 1); }
+    int64_t lvs() const { return 7 * Np; }
     // the strides the launches are given: a width-1 workspace is the plain call (B = 1, stride 0)
     int64_t stride(int64_t per_member) const { return width > 1 ? per_member : 0; }
     FactorBufs bufs() const {
@@ -562,7 +565,7 @@ struct bobe_gp {
   void trtri(double* a, double* linv, double* tmp, int B = 1, int64_t bsA = 0, int64_t bsL = 0, int64_t bsT = 0);
   int lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
             const Hyper* hdev = nullptr, double* gp_out = nullptr, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
-            int64_t bsX = 0, int64_t bsP = 0, double* scratch = nullptr, int64_t bsS = 0);
+            int64_t bsX = 0, int64_t bsP = 0, double* scratch = nullptr, int64_t bsS = 0, int64_t bsK = 0);
   // wv = Linv rhs, al = Linv^T wv (rhs: y unless given; bsY: its stride per batch member)
   void solve_alpha(const double* linv, double* wv, double* al, double* prt, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
                    int64_t bsP = 0, const double* rhs = nullptr, int64_t bsY = 0);
@@ -611,11 +614,19 @@ struct bobe_gp {
   int posterior_sample(const double* Xq, int64_t C, int64_t S, uint64_t seed, const double* z, int centered, double* draws,
                        double* jitter_out);
 
-  // ---- gp_loo.hip (loo_ws: seven vectors of Np - diag K^-1, mean, var, lpd, sqrt c, b / sqrt c, w)
+  // ---- gp_loo.hip (loo_ws: seven vectors of Np - diag K^-1, mean, var, lpd, sqrt c, b / sqrt c, w - of the state form;
+  // an evaluation works on its workspace's own)
   DBuf loo_ws;
-  void loo_terms(const double* linv, const double* al, bool with_grad_terms, double* sum_out);
+  // The LOO terms of B factors: their inverse factors (stride bsL), alphas (bsA), partial sums (bsP), seven-vector blocks
+  // lw (bsV); the sums land in sum_out + b * bsO
+  void loo_terms(const double* linv, const double* al, double* prt, double* lw, bool with_grad_terms, double* sum_out,
+                 int B = 1, int64_t bsL = 0, int64_t bsA = 0, int64_t bsP = 0, int64_t bsV = 0, int64_t bsO = 0);
   int loo_state(double* mean, double* var, double* lpd, double* sum_lpd);
+  // the launches of B LOO evaluations on ws (eval_enqueue's counterpart), and their start-to-collect on ws
+  void loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev);
+  int loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* grad, int* status);
   int loo_objective(const Hyper& h, double* loo, double* grad);
+  int loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status);
 
   // ---- gp_batch.hip (call-local buffers only; the handle's Z-side state is read, never written)
   int wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,

@@ -1,6 +1,7 @@
 // libbobe_gp.so, leave-one-out unit: the LOO predictive terms of the factorised state (bobe_gp_loo) and the LOO log
-// pseudo-likelihood with its gradient at a hyper-parameter vector (bobe_gp_loo_objective).  Kernels: loo_kernels.hpp; the
-// factorisation, the triangular inverse and K^-1 are gp_factor.hip's (factor_into, lauum).
+// pseudo-likelihood with its gradient at a hyper-parameter vector (bobe_gp_loo_objective) or at several in lock step
+// (bobe_gp_loo_objective_batch).  Kernels: loo_kernels.hpp; the factorisation, the triangular inverse and K^-1 are
+// gp_factor.hip's (factor_into, lauum).
 #include "gp_handle.hpp"
 
 #include "loo_kernels.hpp"
@@ -21,18 +22,19 @@ void configure_loo_kernels() {
 
 }  // namespace bobe
 
-// a = diag(K^-1) from the inverse factor `linv`, then mean / var / lpd (and sqrt c, b / sqrt c when `with_grad_terms`) into
-// loo_ws, and sum lpd into sum_out (device).  loo_ws: seven vectors of Np - a, mean, var, lpd, sqrt c, b / sqrt c, w.
-void bobe_gp::loo_terms(const double* linv, const double* al, bool with_grad_terms, double* sum_out) {
-  loo_ws.ensure((size_t)7 * Np * sizeof(double));
-  double* ws = loo_ws.d();
-  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb), dim3(256), 0, stream, linv, Np, part.d(), Np);
-  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), 1u), dim3(256), 0, stream, (const double*)part.d(), Np,
-                     nb, 1, Np, ws, (int64_t)0, (int64_t)0);
-  hipLaunchKernelGGL(k_loo_point, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, stream, (const double*)ws, al,
-                     (const double*)y.d(), N, Np, ws + Np, ws + 2 * Np, ws + 3 * Np, with_grad_terms ? ws + 4 * Np : nullptr,
-                     with_grad_terms ? ws + 5 * Np : nullptr);
-  hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, stream, (const double*)(ws + 3 * Np), N, sum_out);
+// a = diag(K^-1) from the inverse factors `linv`, then mean / var / lpd (and sqrt c, b / sqrt c when `with_grad_terms`) into
+// lw, and sum lpd into sum_out (device).  lw: seven vectors of Np per member - a, mean, var, lpd, sqrt c, b / sqrt c, w.
+void bobe_gp::loo_terms(const double* linv, const double* al, double* prt, double* lw, bool with_grad_terms, double* sum_out,
+                        int B, int64_t bsL, int64_t bsA, int64_t bsP, int64_t bsV, int64_t bsO) {
+  const unsigned nm = (unsigned)B;
+  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream, linv, Np, prt, Np, bsL,
+                     bsP);
+  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)prt, Np, nb, 1,
+                     Np, lw, bsP, bsV);
+  hipLaunchKernelGGL(k_loo_point, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)lw, al,
+                     (const double*)y.d(), N, Np, lw + Np, lw + 2 * Np, lw + 3 * Np, with_grad_terms ? lw + 4 * Np : nullptr,
+                     with_grad_terms ? lw + 5 * Np : nullptr, bsA, bsV);
+  hipLaunchKernelGGL(k_loo_sum, dim3(1, nm), dim3(256), 0, stream, (const double*)(lw + 3 * Np), N, sum_out, bsV, bsO);
   LAUNCH_CHECK();
 }
 
@@ -40,7 +42,8 @@ void bobe_gp::loo_terms(const double* linv, const double* al, bool with_grad_ter
 int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   use();
-  loo_terms(Linv.d(), alpha.d(), false, res.d() + 102);
+  loo_ws.ensure((size_t)7 * Np * sizeof(double));
+  loo_terms(Linv.d(), alpha.d(), part.d(), loo_ws.d(), false, res.d() + 102);
   const double* ws = loo_ws.d();
   double* outs[3] = {mean, var, lpd};
   for (int q = 0; q < 3; ++q)
@@ -58,48 +61,109 @@ int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) 
   return BOBE_OK;
 }
 
-// bobe_gp_loo_objective: the front of bobe_gp_mll's pipeline on the handle's own evaluation workspace (factor_into: up to
-// Linv / alpha), then
-//   value     a, the per-point terms, the fixed-order sum                                    (loo_terms)
-//   gradient  K^-1 stored by the existing lauum into Tmp, B = diag(sqrt c) K^-1 into A (the factor L is no longer
-//             needed), w = B^T (b / sqrt c), the dense B^T B tiles with the gradient epilogue, k_mll_grad_reduce.
-// The workspace ends up holding no factor (A is overwritten): its record is cleared, bobe_gp_factor will not adopt it.
-int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
-  use();
-  EvalWs& ws = own;
+// The launches of B LOO evaluations on ws, on the current stream - eval_enqueue's counterpart: the single evaluation (B = 1,
+// stride 0, h by value) and the lock-step batch (every launch widened by the member dimension, the hyper-parameters read
+// from the workspace's device copy).  The front of bobe_gp_mll's pipeline (factor_into: up to Linv / alpha), then
+//   value     the info word and the smallest pivot's root (res[100], res[101]) while A still holds L, a, the per-point
+//             terms, the fixed-order sum into res[102]                                                       (loo_terms)
+//   gradient  K^-1 stored by the existing lauum into Tmp (its partial sums go unused), B = diag(sqrt c) K^-1 into A (the
+//             factor L is no longer needed), w = B^T (b / sqrt c), the dense B^T B tiles with the gradient epilogue,
+//             k_mll_grad_reduce on the d + 1 gradient components.
+// Without a gradient the list stops after the value.  Results land in the pinned ws.h_res[b * 128 + ...].
+void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev) {
   const FactorBufs f = ws.bufs();
-  ws.tag[0].clear();
-  const double floor_h = pivot_floor(h);
-  factor_into(h, f);
-  // the info word and the smallest pivot's root (res[100], res[101]), while A still holds L
-  mll_terms(f.w, f.a, ws.res.d(), f.info);
-  loo_terms(f.linv, f.alpha, grad != nullptr, ws.res.d() + 102);
-  if (grad) {
-    double* lw = loo_ws.d();
-    (void)lauum(h, f.linv, f.alpha, f.xst, f.tmp, nullptr, ws.gpart.d());      // K^-1's lower tiles -> Tmp (its partial sums go unused)
+  const int64_t gps = ws.stride(ws.gps()), rs = ws.stride(128), lvs = ws.stride(ws.lvs());
+  double* lw = ws.loo.d();
+  const unsigned nm = (unsigned)B;
+  if (hdev) HIPCHK(hipMemcpyAsync(ws.hyp.p, ws.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
+  factor_into(hs[0], f, hdev, B);
+  hipLaunchKernelGGL(k_mll_terms, dim3(nm), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, ws.res.d(),
+                     f.vec, f.mat, rs, (const int*)f.info);
+  loo_terms(f.linv, f.alpha, f.part, lw, want_grad, ws.res.d() + 102, B, f.mat, f.vec, f.prt, lvs, rs);
+  if (want_grad) {
+    (void)lauum(hs[0], f.linv, f.alpha, f.xst, f.tmp, hdev, ws.gpart.d(), B, f.mat, f.vec, f.xs, gps, nullptr, 0, f.mat);
     const int nt32 = (int)(Np / 32);
-    hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2)), dim3(256), 0, stream, (const double*)f.tmp, Np,
-                       (const double*)(lw + 4 * Np), f.a);
-    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Np / 64), (unsigned)nb, 1u), dim3(256), 0, stream, (const double*)f.a, Np,
-                       0, (const double*)(lw + 5 * Np), part.d(), Np, (int64_t)0, (int64_t)0, (int64_t)0);
-    hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), 1u), dim3(256), 0, stream, (const double*)part.d(), Np,
-                       nb, 0, Np, lw + 6 * Np, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2), nm), dim3(256), 0, stream, (const double*)f.tmp, Np,
+                       (const double*)(lw + 4 * Np), f.a, f.mat, lvs);
+    hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream, (const double*)f.a, Np, 0,
+                       (const double*)(lw + 5 * Np), f.part, Np, f.mat, lvs, f.prt);
+    hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)f.part, Np,
+                       nb, 0, Np, lw + 6 * Np, f.prt, lvs);
     const LauumTiling t = lauum_tiling(nb);       // (the dense B^T B on the tiles and the tile core K^-1 was formed on)
     prof_begin(BOBE_PROF_LAUUM);
-    with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT, auto GL) {
-      hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(t.ntiles), dim3(256),
+    with_lauum_variant(hs[0].kern, hs[0].d, t, [&](auto KE, auto DC, auto TT, auto GL) {
+      hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(t.ntiles * B), dim3(256),
                          (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)f.a, Np, Np, N,
-                         (const double*)f.alpha, (const double*)(lw + 6 * Np), (const double*)f.xst, Np, h, ws.gpart.d());
+                         (const double*)f.alpha, (const double*)(lw + 6 * Np), (const double*)f.xst, Np, hs[0], ws.gpart.d(),
+                         hdev, f.mat, f.vec, lvs, f.xs, gps, B);
     });
     prof_end(BOBE_PROF_LAUUM);
-    // (d + 1 workgroups: the gradient components; the scalar terms were reduced above)
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1), dim3(256), 0, stream, (const double*)ws.gpart.d(), t.ntiles,
+    // (d + 1 workgroups per member: the gradient components; the scalar terms were reduced above)
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1, nm), dim3(256), 0, stream, (const double*)ws.gpart.d(), t.ntiles,
                        dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np,
-                       (const int*)nullptr, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0);
-    LAUNCH_CHECK();
+                       (const int*)nullptr, gps, rs, (int64_t)0, (int64_t)0);
   }
-  res_to_host(ws.res.d(), ws.h_res, 103);
-  const int st = eval_result(ws.h_res, floor_h, loo, grad);      // (bobe_gp_mll's rule; the value is the LOO sum instead)
-  if (st == BOBE_OK) *loo = ws.h_res[102];
-  return st;
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(ws.h_res, ws.res.p, (size_t)(ws.width > 1 ? B * 128 : 103) * sizeof(double), hipMemcpyDeviceToHost,
+                        stream));
+}
+
+// Start-to-collect of B LOO evaluations on ws.  With a gradient a member ends up holding no factor (A is overwritten): its
+// record is cleared - also one armed by an earlier bobe_gp_mll_batch on the same member - and stays cleared, so that
+// bobe_gp_factor never adopts it.  A member's status is bobe_gp_mll's rule (eval_result) on its own info word and
+// smallest pivot; the value is the LOO sum instead.
+int bobe_gp::loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* grad, int* status) {
+  UseWs use_ws(*this, ws);
+  for (int b = 0; b < B; ++b) {
+    ws.tag[b].clear();
+    ws.h_hyp[b] = hs[b];
+    ws.floor[b] = pivot_floor(hs[b]);
+  }
+  loo_enqueue(ws, B, hs, grad != nullptr, ws.width > 1 ? static_cast<const Hyper*>(ws.hyp.p) : nullptr);
+  sync();
+  int worst = BOBE_OK;
+  for (int b = 0; b < B; ++b) {
+    const double* hr = ws.h_res + (size_t)b * 128;
+    const int st = eval_result(hr, ws.floor[b], loo + b, grad ? grad + (size_t)b * (d + 1) : nullptr);
+    if (st == BOBE_OK) loo[b] = hr[102];
+    if (status) status[b] = st;
+    if (st != BOBE_OK) worst = st;
+  }
+  return worst;
+}
+
+// bobe_gp_loo_objective: the width-1, stride-0 case on the handle's own evaluation workspace
+int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
+  use();
+  return loo_eval(own, 1, &h, loo, grad, nullptr);
+}
+
+// bobe_gp_loo_objective_batch: BOBE_MAX_MLL_SLOTS members at a time in lock step on the batch workspace, as bobe_gp_mll_batch;
+// a lone member, and every member below BOBE_LOCKSTEP_MIN_N points, takes the single path (there is no slot form).
+int bobe_gp::loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status) {
+  use();
+  const bool lockstep = N >= tuning().lockstep_min_n;
+  int worst = BOBE_OK;
+  for (int64_t b0 = 0; b0 < B; b0 += BOBE_MAX_MLL_SLOTS) {
+    const int nbat = (int)std::min<int64_t>(BOBE_MAX_MLL_SLOTS, B - b0);
+    Hyper hs[BOBE_MAX_MLL_SLOTS];
+    for (int i = 0; i < nbat; ++i) {
+      hs[i] = hyp;
+      for (int j = 0; j < d; ++j) hs[i].ls[j] = ls[(b0 + i) * d + j];
+      hs[i].kvar = kvar[b0 + i];
+    }
+    double* gr = grad ? grad + b0 * (d + 1) : nullptr;
+    int* sts = status ? status + b0 : nullptr;
+    if (lockstep && nbat >= 2) {
+      ensure_batch(nbat);
+      const int st = loo_eval(batch, nbat, hs, loo + b0, gr, sts);
+      if (st != BOBE_OK) worst = st;
+      continue;
+    }
+    for (int i = 0; i < nbat; ++i) {
+      const int st = loo_eval(own, 1, hs + i, loo + b0 + i, gr ? gr + (size_t)i * (d + 1) : nullptr, sts ? sts + i : nullptr);
+      if (st != BOBE_OK) worst = st;
+    }
+  }
+  return worst;
 }

@@ -7,6 +7,9 @@
 // a_i is the column sum of squares of the triangular inverse factor (no product, no cancellation); A diag(c) A = B^T B with
 // B = diag(sqrt c) A is a dense tile product on the cores of gemm_f64.hpp, fused with the gradient epilogue of k_lauum_grad
 // (W there = 2 M here).  Every sum has a fixed order that depends on N only.
+// Every kernel takes the member of a lock-step batch from its last grid dimension (k_loo_grad: from blockIdx.x, as
+// k_lauum_grad) and works on base + member * stride of what it is given (strides in doubles); one member with stride 0 is
+// the plain call, and a member's arithmetic does not depend on the batch it runs in.
 #pragma once
 #include "kernels_common.hpp"
 
@@ -14,9 +17,13 @@ namespace bobe {
 
 // part[rb * ldp + c] = sum over the rows k >= c of row block rb (128 rows) of Linv[k][c]^2, row blocks rb >= c / 128 only:
 // the launch shape and the summation order of k_gemv_t_part (four runs of 32 rows, then ((r0 + r1) + r2) + r3), followed by
-// k_colsum_parts(lower = 1).  grid.x = column strips of 64, grid.y = row blocks.  Elements above the diagonal are never read.
+// k_colsum_parts(lower = 1).  grid.x = column strips of 64, grid.y = row blocks, grid.z = batch members.  Elements above the
+// diagonal are never read.
 static __global__ __launch_bounds__(256) void k_loo_colsq_part(const double* __restrict__ Linv, int64_t ld,
-                                                                double* __restrict__ part, int64_t ldp) {
+                                                                double* __restrict__ part, int64_t ldp, int64_t bsL = 0,
+                                                                int64_t bsP = 0) {
+  Linv += blockIdx.z * bsL;
+  part += blockIdx.z * bsP;
   __shared__ double red[4][64];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const int64_t c = (int64_t)blockIdx.x * 64 + cx;
@@ -37,12 +44,23 @@ static __global__ __launch_bounds__(256) void k_loo_colsq_part(const double* __r
 
 // The per-point terms from a (the diagonal of K^-1), alpha and y; one thread per padded point.  mean / var / lpd: [np]
 // (0 in the padding).  sqc / bs (both or neither): sqrt(c_i) and b_i / sqrt(c_i), 0 in the padding - the row scaling of B
-// and the vector whose product with B^T is w = A b.
+// and the vector whose product with B^T is w = A b.  grid.y = batch members: alpha strides by bsA, the six vectors of the
+// LOO block by bsV; y is shared.
 static __global__ __launch_bounds__(256) void k_loo_point(const double* __restrict__ a, const double* __restrict__ alpha,
                                                            const double* __restrict__ y, int64_t n, int64_t np,
                                                            double* __restrict__ mean, double* __restrict__ var,
                                                            double* __restrict__ lpd, double* __restrict__ sqc,
-                                                           double* __restrict__ bs) {
+                                                           double* __restrict__ bs, int64_t bsA = 0, int64_t bsV = 0) {
+  const int64_t mo = blockIdx.y * bsV;
+  a += mo;
+  alpha += blockIdx.y * bsA;
+  mean += mo;
+  var += mo;
+  lpd += mo;
+  if (sqc) {
+    sqc += mo;
+    bs += mo;
+  }
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= np) return;
   double m = 0.0, v = 0.0, l = 0.0, sc = 0.0, b = 0.0;
@@ -65,8 +83,12 @@ static __global__ __launch_bounds__(256) void k_loo_point(const double* __restri
   }
 }
 
-// *out = sum_{i < n} lpd[i]: one workgroup, thread-strided partial sums, wave_sum, ((w0 + w1) + w2) + w3
-static __global__ __launch_bounds__(256) void k_loo_sum(const double* __restrict__ lpd, int64_t n, double* __restrict__ out) {
+// *out = sum_{i < n} lpd[i]: one workgroup per batch member (grid.y), thread-strided partial sums, wave_sum,
+// ((w0 + w1) + w2) + w3
+static __global__ __launch_bounds__(256) void k_loo_sum(const double* __restrict__ lpd, int64_t n, double* __restrict__ out,
+                                                         int64_t bsV = 0, int64_t bsO = 0) {
+  lpd += blockIdx.y * bsV;
+  out += blockIdx.y * bsO;
   __shared__ double r[4];
   double s = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) s += lpd[i];
@@ -78,9 +100,13 @@ static __global__ __launch_bounds__(256) void k_loo_sum(const double* __restrict
 
 // B = diag(sqc) A, dense, from the LOWER triangle of A = K^-1 as k_lauum_grad stores it (elements above the diagonal of
 // Kinv are never read): workgroup = one lower 32 x 32 tile (ti >= tj), written scaled to B[ti][tj] and, transposed through
-// LDS, to B[tj][ti].  Kinv and B must not overlap.
+// LDS, to B[tj][ti].  Kinv and B must not overlap.  grid.y = batch members (Kinv and B stride by bsM, sqc by bsV).
 static __global__ __launch_bounds__(256) void k_loo_make_b(const double* __restrict__ Kinv, int64_t ld,
-                                                            const double* __restrict__ sqc, double* __restrict__ B) {
+                                                            const double* __restrict__ sqc, double* __restrict__ B,
+                                                            int64_t bsM = 0, int64_t bsV = 0) {
+  Kinv += blockIdx.y * bsM;
+  B += blockIdx.y * bsM;
+  sqc += blockIdx.y * bsV;
   __shared__ double s[32][33];
   int ti, tj;
   tri_decode((int)blockIdx.x, ti, tj);
@@ -112,14 +138,25 @@ static __global__ __launch_bounds__(256) void k_loo_make_b(const double* __restr
 // operand of k_lauum_grad);  W = 2 M = -2 G - (w alpha^T + alpha w^T) on the tile.
 // partial[tile * (DCAP + 1) + j] = sum_ab W_ab dK_ab / dlog ls_j (j < d), [DCAP] = sum_ab W_ab Kt_ab (Kt: without noise),
 // off-diagonal tiles weighted x2: the layout and the epilogue arithmetic of k_lauum_grad, reduced by k_mll_grad_reduce
-// (x 1/2).  One tile per workgroup, tile = blockIdx.x; GLDS: the tile core, as in k_lauum_grad.
+// (x 1/2).  One tile per workgroup; GLDS: the tile core, as in k_lauum_grad.
+// Batch: one grid dimension, tile-major - workgroup id = tile * nbatch + member, the order k_lauum_grad takes (here every
+// tile has the same K length, so the order is a convention, not a schedule).  hp: the members' hyper-parameters on the
+// device (NULL: h by value); B strides by bsB, alpha by bsV, w by bsW, XsT by bsX, partial by bsP.
 template <int KERN, int DCAP, int T, bool GLDS = false>
 __global__ __launch_bounds__(256, 2) void k_loo_grad(const double* __restrict__ B, int64_t ldb, int64_t np, int64_t n,
                                                      const double* __restrict__ alpha, const double* __restrict__ wv,
                                                      const double* __restrict__ XsT, int64_t ldx, Hyper h,
-                                                     double* __restrict__ partial) {
+                                                     double* __restrict__ partial, const Hyper* __restrict__ hp = nullptr,
+                                                     int64_t bsB = 0, int64_t bsV = 0, int64_t bsW = 0, int64_t bsX = 0,
+                                                     int64_t bsP = 0, int nbatch = 1) {
   extern __shared__ double smem[];
-  const int tile = (int)blockIdx.x;
+  const int tile = (int)(blockIdx.x / nbatch), slot = (int)(blockIdx.x % nbatch);
+  if (hp) h = hp[slot];
+  B += slot * bsB;
+  alpha += slot * bsV;
+  wv += slot * bsW;
+  XsT += slot * bsX;
+  partial += slot * bsP;
   int ti, tj;
   tri_decode(tile, ti, tj);
   v4d acc[T / 32][T / 32];

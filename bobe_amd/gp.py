@@ -408,9 +408,12 @@ class GP:
     def fit_objective(self) -> str:
         """What ``fit`` minimises: 'mll' (default) = -(MLL + log prior), the reference's objective, or 'loo' = -(L_LOO + log
         prior) with L_LOO the leave-one-out log pseudo-likelihood (``neg_loo_value_and_grad``), which is more robust to a
-        mis-specified kernel.  With 'loo' the restarts run one after another through the same ``mll_optimize`` driver (no
-        batch or slot form of the LOO objective exists), and the ``'mll'`` key of ``fit``'s result - callers read it -
-        holds ``-best_loss`` of the LOO objective, i.e. L_LOO + log prior at the optimum, not a marginal likelihood."""
+        mis-specified kernel.  With 'loo' the restarts go through the same ``mll_optimize`` driver and, under the
+        conditions of the MLL fit's lock-step mode, advance in lock step (``neg_loo_value_and_grad_batch``, one
+        ``bobe_gp_loo_objective_batch`` call per round); the LOO objective has no slot form, so ``restart_mode='slots'``
+        runs the restarts one after another.  Same iterates and result either way.  The ``'mll'`` key of ``fit``'s result
+        - callers read it - holds ``-best_loss`` of the LOO objective, i.e. L_LOO + log prior at the optimum, not a
+        marginal likelihood."""
         return self._fit_objective
 
     @fit_objective.setter
@@ -454,6 +457,21 @@ class GP:
                                                    _lib.ptr(grad)), "bobe_gp_loo_objective")
         return val.value, grad
 
+    def loo_data_batch(self, lengthscales, kernel_variances, want_grad=True):
+        """``loo_data`` for B hyper-parameter vectors evaluated in lock step on the GPU (``bobe_gp_loo_objective_batch``) -
+        the counterpart of ``mll_data_batch``.  Every member has the bits of its ``loo_data`` call; vectors whose kernel
+        matrix is not positive definite come back as NaN."""
+        ls = _lib.as_f64(lengthscales).reshape(-1, self.ndim)
+        B = ls.shape[0]
+        kv = _lib.as_f64(kernel_variances).reshape(B)
+        val = np.empty(B)
+        grad = np.empty((B, self.ndim + 1)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        st = self._lib.bobe_gp_loo_objective_batch(self._h, B, _lib.ptr(ls), _lib.ptr(kv), _lib.ptr(val), _lib.ptr(grad),
+                                                   C.c_void_p(status.ctypes.data))
+        _lib.check(st, "bobe_gp_loo_objective_batch")
+        return val, grad
+
     def neg_loo_value_and_grad(self, log_params, want_grad=True):
         """(f, df/dtheta) with f = -(L_LOO + log prior), theta = log hp: ``neg_mll_value_and_grad`` with the LOO log
         pseudo-likelihood in the place of the marginal likelihood (priors, a fixed kernel variance and tausq handled by the
@@ -463,22 +481,37 @@ class GP:
         val, g_data = self.loo_data(ls, kvar, want_grad)
         return self._assemble_objective(log_params, ls, kvar, tausq, val, g_data, want_grad)
 
+    def neg_loo_value_and_grad_batch(self, log_params_list, want_grad=True):
+        """``neg_loo_value_and_grad`` for several theta at once (the restarts of a ``fit_objective='loo'`` fit advancing in
+        lock step); returns a list of (f, grad) pairs with exactly the values of the one-at-a-time call."""
+        thetas = [np.asarray(t, dtype=np.float64) for t in log_params_list]
+        parsed = [self._parse_hyperparams(t) for t in thetas]
+        val, g_data = self.loo_data_batch(np.array([p[0] for p in parsed]), np.array([p[1] for p in parsed]), want_grad)
+        return [self._assemble_objective(t, p[0], p[1], p[2], float(val[i]), None if g_data is None else g_data[i],
+                                         want_grad) for i, (t, p) in enumerate(zip(thetas, parsed))]
+
     def fit(self, x0: np.ndarray = None, maxiter: int = 500) -> dict:
         """BOBE/gp.py:400-437.  With ``fit_objective='loo'`` the returned ``'mll'`` is L_LOO + log prior at the optimum."""
         if x0 is None:
             x0 = np.log(self.get_hyperparams())[None, :]
         x0 = np.atleast_2d(np.asarray(x0, dtype=np.float64))
         optimizer_options = dict(self.optimizer_options)
-        if self.fit_objective == "loo":
-            best_params_log, best_loss = self.mll_optimize(
-                self.neg_loo_value_and_grad, num_params=self.num_hyperparams, bounds=self.hyperparam_bounds, x0=x0,
-                maxiter=maxiter, n_restarts=x0.shape[0], optimizer_options=optimizer_options)
-            return {"mll": -best_loss, "params": best_params_log}
-        # restarts are independent L-BFGS-B runs: each gets a host thread and an evaluation slot of the library
+        # restarts are independent L-BFGS-B runs: they advance in lock step, or each gets a host thread and an evaluation
+        # slot of the library
         extra = {}
+        lockstep = False
         if self.concurrent_restarts and x0.shape[0] > 1 and self.mll_optimize is optimize_scipy:
             from .optim import _rc_available
-            if self.restart_mode == "lockstep" or (self.restart_mode == "auto" and _rc_available()):
+            lockstep = self.restart_mode == "lockstep" or (self.restart_mode == "auto" and _rc_available())
+        if self.fit_objective == "loo":
+            if lockstep:                       # (no slot form of the LOO objective: otherwise one restart after another)
+                extra = {"batch_value_and_grad": self.neg_loo_value_and_grad_batch}
+            best_params_log, best_loss = self.mll_optimize(
+                self.neg_loo_value_and_grad, num_params=self.num_hyperparams, bounds=self.hyperparam_bounds, x0=x0,
+                maxiter=maxiter, n_restarts=x0.shape[0], optimizer_options=optimizer_options, **extra)
+            return {"mll": -best_loss, "params": best_params_log}
+        if self.concurrent_restarts and x0.shape[0] > 1 and self.mll_optimize is optimize_scipy:
+            if lockstep:
                 extra = {"batch_value_and_grad": self.neg_mll_value_and_grad_batch}
             else:
                 extra = {"slot_value_and_grad": lambda x, slot: self.neg_mll_value_and_grad(x, slot=slot),

@@ -118,9 +118,20 @@ int bobe_gp_loo(bobe_gp_t* gp, double* mean, double* var, double* lpd, double* s
  * kernel_variance,
  *   dL_LOO / dtheta_j = sum_ab M_ab dK_ab / dtheta_j,   M = -A diag(c) A - 1/2 (w alpha^T + alpha w^T),
  *   c_i = 1 / (2 a_i) + alpha_i^2 / (2 a_i^2),   b_i = -alpha_i / a_i,   w = A b.
- * Runs on the evaluation workspace: does not disturb the state left by bobe_gp_factor.  One evaluation at a time (no slot,
- * batch or lock-step form).  BOBE_NOT_PD (the rank test of bobe_gp_set_pivot_floor_ulp included) -> *loo and grad are NaN. */
+ * Runs on the evaluation workspace: does not disturb the state left by bobe_gp_factor.  BOBE_NOT_PD (the rank test of
+ * bobe_gp_set_pivot_floor_ulp included) -> *loo and grad are NaN. */
 int bobe_gp_loo_objective(bobe_gp_t* gp, const double* lengthscales, double kernel_variance, double* loo, double* grad);
+
+/* bobe_gp_loo_objective for B >= 1 hyper-parameter vectors at once, the counterpart of bobe_gp_mll_batch: lengthscales is
+ * B x d, kernel_variance has B entries, loo B, grad (may be NULL: the values alone) B x (d+1), status (may be NULL) B
+ * per-vector codes (BOBE_OK / BOBE_NOT_PD).  Up to BOBE_MAX_MLL_SLOTS vectors advance together through ONE launch sequence
+ * on the handle's stream (every kernel takes the batch member from a grid dimension), with exactly the arithmetic of
+ * bobe_gp_loo_objective per member (bit-identical results); below BOBE_LOCKSTEP_MIN_N points the members run one after
+ * another (there is no slot form).  Does not disturb the state left by bobe_gp_factor, and leaves no factor behind that
+ * bobe_gp_factor could adopt.  Returns BOBE_NOT_PD when any vector was not positive definite (its outputs are NaN, the
+ * others' are unaffected), < 0 on usage / HIP errors. */
+int bobe_gp_loo_objective_batch(bobe_gp_t* gp, int64_t B, const double* lengthscales, const double* kernel_variance,
+                                double* loo, double* grad, int* status);
 
 /* GP.predict_mean_batched / predict_var_batched / predict_batched (gp.py:450-493) for C query points
  * Xq (C x d).  mean[c] = k_c^T alpha; var[c] = kvar + noise - |L^-1 k_c|^2 with
