@@ -48,6 +48,12 @@ SIGNATURES = [
     ("bobe_gp_loo_objective", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, c_double_p, C.c_void_p]),
     ("bobe_gp_loo_objective_batch", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
+    ("bobe_gp_mll_noise", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, c_double_p, C.c_void_p]),
+    ("bobe_gp_mll_noise_batch", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    ("bobe_gp_loo_objective_noise", C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, c_double_p, C.c_void_p]),
+    ("bobe_gp_loo_objective_noise_batch", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
     ("bobe_gp_predict", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     ("bobe_gp_wip_sweep", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -424,11 +424,15 @@ class BOBE:
             gp_fit(self.gp, n_restarts=n_restarts, maxiters=maxiter, rng=self.np_rng,
                    factorisable_start=self.factorisable_start)
             self.n_points_since_last_fit = 0
+            if verbose and getattr(self.gp, "fit_noise", False):
+                log.info(f"Refit done: fitted noise level {self.gp.noise:.4e} (standardised units)")
             if getattr(self, "loo_diagnostics", False):
                 self._record_loo()
         self.timing["GP Training"] += time.time() - t0
         self.gp_hyperparam_history.append({"iteration": int(step), "lengthscales": [float(v) for v in self.gp.lengthscales],
                                            "kernel_variance": float(self.gp.kernel_variance)})
+        if getattr(self.gp, "fit_noise", False):
+            self.gp_hyperparam_history[-1]["noise"] = float(self.gp.noise)
         if hasattr(self.gp, "train_classifier"):     # bo.py:673-676: the labels move with the best value seen
             t0 = time.time()
             self.gp.train_classifier()

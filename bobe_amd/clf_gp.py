@@ -62,8 +62,10 @@ class GPwithClassifier(GP):
                  kernel_variance_bounds=[1e-4, 1e8], lengthscale_bounds=[0.01, 5.0], tausq=None,
                  tausq_bounds=[1e-4, 1e4], kernel_variance_prior=None, lengthscale_prior=None, lengthscales=None,
                  kernel_variance=1.0, param_names=None, train_clf_on_init=True, device: int = 0,
-                 pivot_floor_ulp: Optional[float] = None, fit_objective: str = "mll"):
-        """Same keywords as clf_gp.py:15-30 (+ ``device``, ``pivot_floor_ulp``, ``fit_objective``: see ``GP``)."""
+                 pivot_floor_ulp: Optional[float] = None, fit_objective: str = "mll", fit_noise: bool = False,
+                 noise_bounds=[1e-10, 1e-1], noise_prior=None):
+        """Same keywords as clf_gp.py:15-30 (+ ``device``, ``pivot_floor_ulp``, ``fit_objective``, ``fit_noise``,
+        ``noise_bounds``, ``noise_prior``: see ``GP``)."""
         kind = str(clf_type).lower()
         if kind not in _CLF_KINDS:
             raise ValueError(f"Unsupported classifier type: {clf_type} (built: {', '.join(sorted(_CLF_KINDS))})")
@@ -85,7 +87,8 @@ class GPwithClassifier(GP):
                          lengthscale_prior=lengthscale_prior if lengthscale_prior is not None else "DSLP",
                          kernel_variance_prior=kernel_variance_prior, tausq=tausq, tausq_bounds=tausq_bounds,
                          param_names=param_names, device=device, pivot_floor_ulp=pivot_floor_ulp,
-                         fit_objective=fit_objective)
+                         fit_objective=fit_objective, fit_noise=fit_noise, noise_bounds=noise_bounds,
+                         noise_prior=noise_prior)
         self._gate_installed = False
         self._clf_predict_func: Optional[Callable] = None
         self.use_clf = self.clf_data_size >= self.clf_use_size
@@ -236,7 +239,9 @@ class GPwithClassifier(GP):
                 kernel_variance_prior=plain(state.get("kernel_variance_prior_spec")),
                 lengthscale_prior=plain(state.get("lengthscale_prior_spec")), tausq=plain(state.get("tausq", 1.0)),
                 tausq_bounds=list(np.asarray(state.get("tausq_bounds", [1e-4, 1e4])).tolist()),
-                train_clf_on_init=False, device=device)
+                train_clf_on_init=False, device=device, fit_noise=bool(plain(state.get("fit_noise", False))),
+                noise_bounds=list(np.asarray(state.get("noise_bounds", [1e-10, 1e-1])).tolist()),
+                noise_prior=plain(state.get("noise_prior")))
         g.clf_params = plain(state.get("clf_params"))
         g.clf_metrics = plain(state.get("clf_metrics", {})) or {}
         g.use_clf = bool(plain(state["use_clf"]))              # (the setter hands the restored parameters to the library)

@@ -247,6 +247,53 @@ int bobe_gp_mll_batch(bobe_gp_t* g, int64_t B, const double* ls, const double* k
   API_END
 }
 
+// ---- the noise level as a hyper-parameter: the namesakes above with an explicit noise and d + 2 gradient entries
+static bool noise_ok(double nu) { return std::isfinite(nu) && nu > 0.0; }
+
+int bobe_gp_mll_noise(bobe_gp_t* g, const double* ls, double kvar, double noise, double* mll, double* grad) {
+  API_BEGIN
+  NEED(g && ls && mll, "NULL argument");
+  NEED(noise_ok(noise), "noise must be finite and > 0");
+  if (!g->have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  return g->mll_noise_batch(1, ls, &kvar, &noise, mll, grad, nullptr);
+  API_END
+}
+
+int bobe_gp_mll_noise_batch(bobe_gp_t* g, int64_t B, const double* ls, const double* kvar, const double* noise, double* mll,
+                            double* grad, int* status) {
+  API_BEGIN
+  NEED(g && ls && kvar && noise && mll, "NULL argument");
+  NEED(B >= 1, "B must be >= 1");
+  for (int64_t b = 0; b < B; ++b) NEED(noise_ok(noise[b]), "noise must be finite and > 0");
+  if (!g->have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  return g->mll_noise_batch(B, ls, kvar, noise, mll, grad, status);
+  API_END
+}
+
+int bobe_gp_loo_objective_noise(bobe_gp_t* g, const double* ls, double kvar, double noise, double* loo, double* grad) {
+  API_BEGIN
+  NEED(g && ls && loo, "NULL argument");
+  NEED(noise_ok(noise), "noise must be finite and > 0");
+  if (!g->have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  Hyper h = g->hyp;
+  for (int j = 0; j < g->d; ++j) h.ls[j] = ls[j];
+  h.kvar = kvar;
+  h.noise = noise;
+  return g->loo_objective(h, loo, grad, true);
+  API_END
+}
+
+int bobe_gp_loo_objective_noise_batch(bobe_gp_t* g, int64_t B, const double* ls, const double* kvar, const double* noise,
+                                      double* loo, double* grad, int* status) {
+  API_BEGIN
+  NEED(g && ls && kvar && noise && loo, "NULL argument");
+  NEED(B >= 1, "B must be >= 1");
+  for (int64_t b = 0; b < B; ++b) NEED(noise_ok(noise[b]), "noise must be finite and > 0");
+  if (!g->have_data) throw Err(BOBE_ERR_STATE, "call bobe_gp_set_data first");
+  return g->loo_batch(B, ls, kvar, loo, grad, status, noise);
+  API_END
+}
+
 int bobe_gp_mll_submit(bobe_gp_t* g, int slot, const double* ls, double kvar, int want_grad) {
   API_BEGIN
   NEED(g && ls, "NULL argument");

@@ -700,8 +700,8 @@ void bobe_gp::ensure_batch(int B) {
 // The launches of B value (+ gradient) evaluations on ws, on the current stream: the single evaluation and a slot (B = 1,
 // stride 0 - plain or under capture) and the lock-step batch (every launch widened by the member dimension).  Results land
 // in the pinned ws.h_res[b * 128 + ...]; the info word of member b rides in res[b * 128 + 100], so one copy brings
-// everything to the host.
-void bobe_gp::eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev) {
+// everything to the host.  noise_grad: the launches of the gradient's noise component follow the others (gp_loo.hip).
+void bobe_gp::eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad) {
   const FactorBufs f = ws.bufs();
   const int64_t gps = ws.stride(ws.gps()), rs = ws.stride(128);
   if (hdev) HIPCHK(hipMemcpyAsync(ws.hyp.p, ws.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
@@ -712,6 +712,7 @@ void bobe_gp::eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, c
     hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)ws.gpart.d(), ntiles,
                        dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)f.w, (const double*)f.a, Np, Np,
                        (const int*)f.info, gps, rs, f.vec, f.mat);
+    if (noise_grad) mll_noise_tail(ws, B, hs, hdev);
   } else {
     hipLaunchKernelGGL(k_mll_terms, dim3(B), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, ws.res.d(),
                        f.vec, f.mat, rs, (const int*)f.info);
@@ -759,7 +760,8 @@ void bobe_gp::eval_replay(EvalWs& ws, const Hyper* hs, bool want_grad) {
 }
 
 // Queue the evaluation of hs[0 .. B) on ws (B = 1 unless ws is the batch) and record what its members will hold.
-void bobe_gp::eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad) {
+void bobe_gp::eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad, bool noise_grad) {
+  noise_grad = noise_grad && want_grad;
   UseWs use_ws(*this, ws);
   for (int b = 0; b < B; ++b) {
     ws.tag[b].clear();                      // (the member's factor is being overwritten; armed once the pipeline is queued)
@@ -768,37 +770,40 @@ void bobe_gp::eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad) {
   }
   // A lone evaluation on the handle's stream is NOT faster as a graph (125 vs 107 us at N = 64) and stays a
   // plain launch sequence; so does everything while a kernel class is being timed (events are not captured).
-  if (ws.width > 1) eval_enqueue(ws, B, hs, want_grad, static_cast<const Hyper*>(ws.hyp.p));
-  else if (!on_slot() || N > tuning().graph_max_n || prof_tag != 0) eval_enqueue(ws, 1, hs, want_grad, nullptr);
+  if (ws.width > 1) eval_enqueue(ws, B, hs, want_grad, static_cast<const Hyper*>(ws.hyp.p), noise_grad);
+  else if (noise_grad || !on_slot() || N > tuning().graph_max_n || prof_tag != 0)
+    eval_enqueue(ws, 1, hs, want_grad, nullptr, noise_grad);
   else eval_replay(ws, hs, want_grad);
   for (int b = 0; b < B; ++b) ws.tag[b].arm(hs[b], data_gen, Np);
 }
 
-int bobe_gp::eval_result(const double* hr, double floor, double* mll, double* grad) const {
+int bobe_gp::eval_result(const double* hr, double floor, double* mll, double* grad, bool noise_grad) const {
+  const int ng = d + 1 + (noise_grad ? 1 : 0);
   int inf;
   std::memcpy(&inf, hr + 100, sizeof(int));
   if (inf != 0x7f7f7f7f || !pivots_resolved(hr[101], floor)) {
     *mll = std::nan("");
     if (grad)
-      for (int j = 0; j <= d; ++j) grad[j] = std::nan("");
+      for (int j = 0; j < ng; ++j) grad[j] = std::nan("");
     g_err = not_pd_text(inf, hr[101]);
     return BOBE_NOT_PD;
   }
   *mll = -0.5 * hr[0] - hr[1] - 0.5 * (double)N * std::log(2.0 * M_PI);
   if (grad)
-    for (int j = 0; j <= d; ++j) grad[j] = hr[2 + j];
+    for (int j = 0; j < ng; ++j) grad[j] = hr[2 + j];
   return BOBE_OK;
 }
 
 // A slot's collect touches only the slot's own stream, records and pinned results: safe while another thread submits to
 // another slot.
-int bobe_gp::eval_collect(EvalWs& ws, int B, double* mll, double* grad, int* status) {
+int bobe_gp::eval_collect(EvalWs& ws, int B, double* mll, double* grad, int* status, bool noise_grad) {
+  const int ng = d + 1 + (noise_grad ? 1 : 0);
   HIPCHK(hipStreamSynchronize(ws.stream ? ws.stream : stream));
   int worst = BOBE_OK;
   for (int b = 0; b < B; ++b) {
     const double* hr = ws.h_res + (size_t)b * 128;
     ws.tag[b].collected(hr);
-    const int st = eval_result(hr, ws.floor[b], mll + b, grad ? grad + (size_t)b * (d + 1) : nullptr);
+    const int st = eval_result(hr, ws.floor[b], mll + b, grad ? grad + (size_t)b * ng : nullptr, noise_grad);
     if (status) status[b] = st;
     if (st != BOBE_OK) worst = st;
   }
@@ -971,6 +976,41 @@ int bobe_gp::mll_batch(int64_t B, const double* ls, const double* kvar, double* 
       std::fprintf(stderr, "[bobe] mll_batch B=%d: enqueue %.3f ms, total %.3f ms\n", nbat,
                    std::chrono::duration<double, std::milli>(t_enq - t_start).count(),
                    std::chrono::duration<double, std::milli>(t_end - t_start).count());
+    }
+  }
+  return worst;
+}
+
+// bobe_gp_mll_noise_batch: the members' own noise levels and d + 2 gradient entries; loo_batch's rule for the form - lock step
+// on `batch` BOBE_MAX_MLL_SLOTS at a time, a lone member and everything below BOBE_LOCKSTEP_MIN_N points singly on `own`.
+int bobe_gp::mll_noise_batch(int64_t B, const double* ls, const double* kvar, const double* noise, double* mll, double* grad,
+                             int* status) {
+  use();
+  const bool lockstep = N >= tuning().lockstep_min_n;
+  const bool want = grad != nullptr;
+  int worst = BOBE_OK;
+  for (int64_t b0 = 0; b0 < B; b0 += BOBE_MAX_MLL_SLOTS) {
+    const int nbat = (int)std::min<int64_t>(BOBE_MAX_MLL_SLOTS, B - b0);
+    Hyper hs[BOBE_MAX_MLL_SLOTS];
+    for (int i = 0; i < nbat; ++i) {
+      hs[i] = hyp;
+      for (int j = 0; j < d; ++j) hs[i].ls[j] = ls[(b0 + i) * d + j];
+      hs[i].kvar = kvar[b0 + i];
+      hs[i].noise = noise[b0 + i];
+    }
+    double* gr = grad ? grad + b0 * (d + 2) : nullptr;
+    int* sts = status ? status + b0 : nullptr;
+    if (lockstep && nbat >= 2) {
+      ensure_batch(nbat);
+      eval_start(batch, nbat, hs, want, true);
+      const int st = eval_collect(batch, nbat, mll + b0, gr, sts, true);
+      if (st != BOBE_OK) worst = st;
+      continue;
+    }
+    for (int i = 0; i < nbat; ++i) {
+      eval_start(own, 1, hs + i, want, true);
+      const int st = eval_collect(own, 1, mll + b0 + i, gr ? gr + (size_t)i * (d + 2) : nullptr, sts ? sts + i : nullptr, true);
+      if (st != BOBE_OK) worst = st;
     }
   }
   return worst;

@@ -256,8 +256,8 @@ struct SweepReq {
 // holds once its evaluation was collected: the factor of `h` on data generation `gen` at padded size `Np`, and the
 // factorisation's info word and smallest pivot root (res[100], res[101]).  The pipeline of an evaluation is factor_into's
 // on the same data (same bits in every form), and what follows it - lauum, k_mll_grad_reduce / k_mll_terms - writes only
-// Tmp, gpart and res: L (with its diagonal blocks back in place), Linv, alpha, w and the scaled coordinates stay intact
-// until the workspace is used again.  bobe_gp_factor adopts such a factor instead of recomputing it (factor_state).
+// Tmp, gpart and res, the noise component's launches (mll_noise_tail) in addition part and the member's LOO block: L (with
+// its diagonal blocks back in place), Linv, alpha, w and the scaled coordinates stay intact until the workspace is used again.  bobe_gp_factor adopts such a factor instead of recomputing it (factor_state).
 struct EvalTag {
   bool pending = false;     // enqueued, not collected yet
   bool valid = false;       // collected: info / min_diag are known
@@ -424,8 +424,9 @@ struct bobe_gp {
     DBuf XsT, A, Linv, Tmp, w, alpha, part, gpart, res, info, diag, hyp;
     DBuf loo;                        // the LOO objective's seven vectors per member (gp_loo.hip): diag K^-1, mean, var, lpd,
                                      // sqrt c, b / sqrt c, w
-    double* h_res = nullptr;         // pinned [width][128]: [0] y^T K^-1 y, [1] sum log L_ii, [2..2+d] gradient, [100] the
-                                     // factorisation's info word, [101] min L_jj, [102] the LOO sum (LOO evaluations)
+    double* h_res = nullptr;         // pinned [width][128]: [0] y^T K^-1 y, [1] sum log L_ii, [2..2+d] gradient, [2+d+1] its
+                                     // noise component (the *_noise calls), [100] the factorisation's info word,
+                                     // [101] min L_jj, [102] the LOO sum (LOO evaluations)
     Hyper* h_hyp = nullptr;          // pinned [width] (the same allocation)
     EvalGraph eg;
     std::vector<bobe::EvalTag> tag;  // per member: what it holds
@@ -484,13 +485,18 @@ struct bobe_gp {
   void ensure_batch(int B);
   // the launches of B evaluations on ws (hdev: the device copy of the hyper-parameters, refreshed first; NULL: the kernels
   // take hs[0] by value); eval_start picks the form (plain, graph replay, lock step) and keeps the members' records
-  void eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev);
+  // noise_grad (bobe_gp_mll_noise, with a gradient only): mll_noise_tail's launches are appended, the gradient has d + 2
+  // entries per member (the last from res[2 + d + 1]); never replayed as a graph
+  void eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad = false);
   void eval_replay(EvalWs& ws, const Hyper* hs, bool want_grad);
-  void eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad);
-  int eval_collect(EvalWs& ws, int B, double* mll, double* grad, int* status);
+  void eval_start(EvalWs& ws, int B, const Hyper* hs, bool want_grad, bool noise_grad = false);
+  int eval_collect(EvalWs& ws, int B, double* mll, double* grad, int* status, bool noise_grad = false);
   // hr: an evaluation's pinned results; NaN outputs, g_err and BOBE_NOT_PD when the factorisation failed or a pivot is below floor
-  int eval_result(const double* hr, double floor, double* mll, double* grad) const;
+  int eval_result(const double* hr, double floor, double* mll, double* grad, bool noise_grad = false) const;
   int mll_batch(int64_t B, const double* ls, const double* kvar, double* mll, double* grad, int* status);
+  // bobe_gp_mll_noise_batch: lock step on `batch`, a lone member and N < BOBE_LOCKSTEP_MIN_N singly on `own` (no slot form)
+  int mll_noise_batch(int64_t B, const double* ls, const double* kvar, const double* noise, double* mll, double* grad,
+                      int* status);
   void mll_submit(int slot, const double* ls, double kvar, int want_grad);
   int mll_wait(int slot, double* mll, double* grad);
 
@@ -623,10 +629,14 @@ struct bobe_gp {
                  int B = 1, int64_t bsL = 0, int64_t bsA = 0, int64_t bsP = 0, int64_t bsV = 0, int64_t bsO = 0);
   int loo_state(double* mean, double* var, double* lpd, double* sum_lpd);
   // the launches of B LOO evaluations on ws (eval_enqueue's counterpart), and their start-to-collect on ws
-  void loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev);
-  int loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* grad, int* status);
-  int loo_objective(const Hyper& h, double* loo, double* grad);
-  int loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status);
+  void loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad = false);
+  int loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* grad, int* status, bool noise_grad = false);
+  int loo_objective(const Hyper& h, double* loo, double* grad, bool noise_grad = false);
+  int loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status,
+                const double* noise = nullptr);
+  // the noise component of the gradient, d / d log nu: the launches appended to an MLL / a LOO evaluation with a gradient
+  void mll_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev);
+  void loo_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev);
 
   // ---- gp_batch.hip (call-local buffers only; the handle's Z-side state is read, never written)
   int wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,

@@ -1,7 +1,8 @@
 // libbobe_gp.so, leave-one-out unit: the LOO predictive terms of the factorised state (bobe_gp_loo) and the LOO log
 // pseudo-likelihood with its gradient at a hyper-parameter vector (bobe_gp_loo_objective) or at several in lock step
-// (bobe_gp_loo_objective_batch).  Kernels: loo_kernels.hpp; the factorisation, the triangular inverse and K^-1 are
-// gp_factor.hip's (factor_into, lauum).
+// (bobe_gp_loo_objective_batch), and the noise component that the *_noise entry points append to the gradient of either
+// objective (mll_noise_tail, loo_noise_tail).  Kernels: loo_kernels.hpp; the factorisation, the triangular inverse and K^-1
+// are gp_factor.hip's (factor_into, lauum).
 #include "gp_handle.hpp"
 
 #include "loo_kernels.hpp"
@@ -61,6 +62,36 @@ int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) 
   return BOBE_OK;
 }
 
+// The launches bobe_gp_mll_noise appends to an evaluation with a gradient (eval_enqueue, after everything it queues
+// otherwise): a = diag(K~^-1) from the members' inverse factors into their LOO blocks, then 1/2 nu (sum alpha^2 - sum a) into
+// res[2 + d + 1].  Writes part, the LOO block and that one result: L, Linv, alpha, w stay what bobe_gp_factor adopts.
+void bobe_gp::mll_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev) {
+  const FactorBufs f = ws.bufs();
+  const int64_t rs = ws.stride(128), lvs = ws.stride(ws.lvs());
+  const unsigned nm = (unsigned)B;
+  double* lw = ws.loo.d();
+  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream,
+                     (const double*)f.linv, Np, f.part, Np, f.mat, f.prt);
+  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)f.part, Np,
+                     nb, 1, Np, lw, f.prt, lvs);
+  hipLaunchKernelGGL(k_noise_mll_grad, dim3(1, nm), dim3(256), 0, stream, (const double*)lw, (const double*)f.alpha, N,
+                     hs[0].noise, hdev, ws.res.d() + 2 + d + 1, lvs, f.vec, rs);
+}
+
+// The launches bobe_gp_loo_objective_noise appends (loo_enqueue, after k_mll_grad_reduce): A holds the dense B = diag(sqrt c)
+// K~^-1, the LOO block w; |B|_F^2 over the true N x N block in two stages through part, then -nu (|B|_F^2 + w^T alpha) into
+// res[2 + d + 1].
+void bobe_gp::loo_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev) {
+  const FactorBufs f = ws.bufs();
+  const int64_t rs = ws.stride(128), lvs = ws.stride(ws.lvs());
+  const unsigned nm = (unsigned)B;
+  hipLaunchKernelGGL(k_loo_bsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream, (const double*)f.a, Np,
+                     N, f.part, Np, f.mat, f.prt);
+  hipLaunchKernelGGL(k_noise_loo_grad, dim3(1, nm), dim3(256), 0, stream, (const double*)f.part, Np, nb,
+                     (const double*)(ws.loo.d() + 6 * Np), (const double*)f.alpha, N, hs[0].noise, hdev,
+                     ws.res.d() + 2 + d + 1, f.prt, lvs, f.vec, rs);
+}
+
 // The launches of B LOO evaluations on ws, on the current stream - eval_enqueue's counterpart: the single evaluation (B = 1,
 // stride 0, h by value) and the lock-step batch (every launch widened by the member dimension, the hyper-parameters read
 // from the workspace's device copy).  The front of bobe_gp_mll's pipeline (factor_into: up to Linv / alpha), then
@@ -69,8 +100,9 @@ int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) 
 //   gradient  K^-1 stored by the existing lauum into Tmp (its partial sums go unused), B = diag(sqrt c) K^-1 into A (the
 //             factor L is no longer needed), w = B^T (b / sqrt c), the dense B^T B tiles with the gradient epilogue,
 //             k_mll_grad_reduce on the d + 1 gradient components.
-// Without a gradient the list stops after the value.  Results land in the pinned ws.h_res[b * 128 + ...].
-void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev) {
+// Without a gradient the list stops after the value.  noise_grad (with a gradient only): loo_noise_tail's launches follow.
+// Results land in the pinned ws.h_res[b * 128 + ...].
+void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad) {
   const FactorBufs f = ws.bufs();
   const int64_t gps = ws.stride(ws.gps()), rs = ws.stride(128), lvs = ws.stride(ws.lvs());
   double* lw = ws.loo.d();
@@ -102,6 +134,7 @@ void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, co
     hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1, nm), dim3(256), 0, stream, (const double*)ws.gpart.d(), t.ntiles,
                        dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np,
                        (const int*)nullptr, gps, rs, (int64_t)0, (int64_t)0);
+    if (noise_grad) loo_noise_tail(ws, B, hs, hdev);
   }
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(ws.h_res, ws.res.p, (size_t)(ws.width > 1 ? B * 128 : 103) * sizeof(double), hipMemcpyDeviceToHost,
@@ -111,20 +144,22 @@ void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, co
 // Start-to-collect of B LOO evaluations on ws.  With a gradient a member ends up holding no factor (A is overwritten): its
 // record is cleared - also one armed by an earlier bobe_gp_mll_batch on the same member - and stays cleared, so that
 // bobe_gp_factor never adopts it.  A member's status is bobe_gp_mll's rule (eval_result) on its own info word and
-// smallest pivot; the value is the LOO sum instead.
-int bobe_gp::loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* grad, int* status) {
+// smallest pivot; the value is the LOO sum instead.  noise_grad: d + 2 gradient entries per member, the last d L_LOO / d log nu.
+int bobe_gp::loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* grad, int* status, bool noise_grad) {
+  const int ng = d + 1 + (noise_grad ? 1 : 0);
   UseWs use_ws(*this, ws);
   for (int b = 0; b < B; ++b) {
     ws.tag[b].clear();
     ws.h_hyp[b] = hs[b];
     ws.floor[b] = pivot_floor(hs[b]);
   }
-  loo_enqueue(ws, B, hs, grad != nullptr, ws.width > 1 ? static_cast<const Hyper*>(ws.hyp.p) : nullptr);
+  loo_enqueue(ws, B, hs, grad != nullptr, ws.width > 1 ? static_cast<const Hyper*>(ws.hyp.p) : nullptr,
+              noise_grad && grad != nullptr);
   sync();
   int worst = BOBE_OK;
   for (int b = 0; b < B; ++b) {
     const double* hr = ws.h_res + (size_t)b * 128;
-    const int st = eval_result(hr, ws.floor[b], loo + b, grad ? grad + (size_t)b * (d + 1) : nullptr);
+    const int st = eval_result(hr, ws.floor[b], loo + b, grad ? grad + (size_t)b * ng : nullptr, noise_grad);
     if (st == BOBE_OK) loo[b] = hr[102];
     if (status) status[b] = st;
     if (st != BOBE_OK) worst = st;
@@ -132,16 +167,19 @@ int bobe_gp::loo_eval(EvalWs& ws, int B, const Hyper* hs, double* loo, double* g
   return worst;
 }
 
-// bobe_gp_loo_objective: the width-1, stride-0 case on the handle's own evaluation workspace
-int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad) {
+// bobe_gp_loo_objective (_noise): the width-1, stride-0 case on the handle's own evaluation workspace
+int bobe_gp::loo_objective(const Hyper& h, double* loo, double* grad, bool noise_grad) {
   use();
-  return loo_eval(own, 1, &h, loo, grad, nullptr);
+  return loo_eval(own, 1, &h, loo, grad, nullptr, noise_grad);
 }
 
 // bobe_gp_loo_objective_batch: BOBE_MAX_MLL_SLOTS members at a time in lock step on the batch workspace, as bobe_gp_mll_batch;
 // a lone member, and every member below BOBE_LOCKSTEP_MIN_N points, takes the single path (there is no slot form).
-int bobe_gp::loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status) {
+// noise (bobe_gp_loo_objective_noise_batch; NULL: the installed one): the members' own noise levels, and d + 2 gradient entries.
+int bobe_gp::loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status,
+                       const double* noise) {
   use();
+  const int ng = d + 1 + (noise ? 1 : 0);
   const bool lockstep = N >= tuning().lockstep_min_n;
   int worst = BOBE_OK;
   for (int64_t b0 = 0; b0 < B; b0 += BOBE_MAX_MLL_SLOTS) {
@@ -151,17 +189,19 @@ int bobe_gp::loo_batch(int64_t B, const double* ls, const double* kvar, double* 
       hs[i] = hyp;
       for (int j = 0; j < d; ++j) hs[i].ls[j] = ls[(b0 + i) * d + j];
       hs[i].kvar = kvar[b0 + i];
+      if (noise) hs[i].noise = noise[b0 + i];
     }
-    double* gr = grad ? grad + b0 * (d + 1) : nullptr;
+    double* gr = grad ? grad + b0 * ng : nullptr;
     int* sts = status ? status + b0 : nullptr;
     if (lockstep && nbat >= 2) {
       ensure_batch(nbat);
-      const int st = loo_eval(batch, nbat, hs, loo + b0, gr, sts);
+      const int st = loo_eval(batch, nbat, hs, loo + b0, gr, sts, noise != nullptr);
       if (st != BOBE_OK) worst = st;
       continue;
     }
     for (int i = 0; i < nbat; ++i) {
-      const int st = loo_eval(own, 1, hs + i, loo + b0 + i, gr ? gr + (size_t)i * (d + 1) : nullptr, sts ? sts + i : nullptr);
+      const int st = loo_eval(own, 1, hs + i, loo + b0 + i, gr ? gr + (size_t)i * ng : nullptr, sts ? sts + i : nullptr,
+                              noise != nullptr);
       if (st != BOBE_OK) worst = st;
     }
   }

@@ -231,4 +231,103 @@ __global__ __launch_bounds__(256, 2) void k_loo_grad(const double* __restrict__ 
   }
 }
 
+// ---- the noise component of the two gradients (bobe_gp_mll_noise, bobe_gp_loo_objective_noise) ----------------------------
+// theta_{d+1} = log nu with K~ = K + nu I, dK~ / dlog nu = nu I: the component is nu times the trace of the matrix the other
+// components contract with dK,
+//   dMLL / dlog nu   = 1/2 nu (sum_i alpha_i^2 - sum_i a_i)                  (tr K~^-1 = sum_i a_i = |L^-1|_F^2)
+//   dL_LOO / dlog nu = nu tr M = -nu (|B|_F^2 + w^T alpha)                   (|B|_F^2 = sum_k c_k (A^2)_kk)
+// over the true n x n block only: the identity padding of the factor would add np - n to tr K~^-1.  Bandwidth-bound
+// reductions, launched AFTER everything the evaluation queues without them; a thread owns a column, every order is fixed.
+// nu: hp[member].noise (the lock-step batch's device copy), else `noise` by value.
+
+// *out = 1/2 nu (sum_{i < n} alpha[i]^2 - sum_{i < n} a[i]): one workgroup per batch member (grid.y), k_loo_sum's order for
+// both sums.  a strides by bsV, alpha by bsA, out by bsO.
+static __global__ __launch_bounds__(256) void k_noise_mll_grad(const double* __restrict__ a, const double* __restrict__ alpha,
+                                                                int64_t n, double noise, const Hyper* __restrict__ hp,
+                                                                double* __restrict__ out, int64_t bsV = 0, int64_t bsA = 0,
+                                                                int64_t bsO = 0) {
+  a += blockIdx.y * bsV;
+  alpha += blockIdx.y * bsA;
+  out += blockIdx.y * bsO;
+  if (hp) noise = hp[blockIdx.y].noise;
+  __shared__ double r[2][4];
+  double s2 = 0.0, sa = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) {
+    const double al = alpha[i];
+    s2 = __builtin_fma(al, al, s2);
+    sa += a[i];
+  }
+  s2 = wave_sum(s2);
+  sa = wave_sum(sa);
+  if ((threadIdx.x & 63) == 0) {
+    r[0][threadIdx.x >> 6] = s2;
+    r[1][threadIdx.x >> 6] = sa;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double t2 = ((r[0][0] + r[0][1]) + r[0][2]) + r[0][3], ta = ((r[1][0] + r[1][1]) + r[1][2]) + r[1][3];
+    *out = 0.5 * noise * (t2 - ta);
+  }
+}
+
+// part[rb * ldp + c] = sum over the rows k < n of row block rb (128 rows) of B[k][c]^2 for the columns c < n, 0 for the
+// padding columns: k_loo_colsq_part's launch shape and order on a DENSE matrix (every row block).  grid.x = column strips of
+// 64, grid.y = row blocks, grid.z = batch members.
+static __global__ __launch_bounds__(256) void k_loo_bsq_part(const double* __restrict__ B, int64_t ld, int64_t n,
+                                                              double* __restrict__ part, int64_t ldp, int64_t bsB = 0,
+                                                              int64_t bsP = 0) {
+  B += blockIdx.z * bsB;
+  part += blockIdx.z * bsP;
+  __shared__ double red[4][64];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int64_t c = (int64_t)blockIdx.x * 64 + cx;
+  const int rb = blockIdx.y;
+  double s = 0.0;
+  if (c < n) {
+    const int64_t k0 = (int64_t)rb * TILE + ry * 32;
+#pragma unroll 8
+    for (int k = 0; k < 32; ++k) {
+      const double v = (k0 + k < n) ? B[(k0 + k) * ld + c] : 0.0;
+      s = __builtin_fma(v, v, s);
+    }
+  }
+  red[ry][cx] = s;
+  __syncthreads();
+  if (ry == 0) part[(int64_t)rb * ldp + c] = ((red[0][cx] + red[1][cx]) + red[2][cx]) + red[3][cx];
+}
+
+// *out = -nu (sum_{c < n} sum_rb part[rb * ldp + c] + sum_{c < n} w[c] alpha[c]): one workgroup per batch member (grid.y);
+// a thread sums its columns' row blocks in ascending order (k_colsum_parts), then k_loo_sum's order across the threads.
+// part strides by bsP, w by bsW, alpha by bsA, out by bsO.
+static __global__ __launch_bounds__(256) void k_noise_loo_grad(const double* __restrict__ part, int64_t ldp, int nrb,
+                                                                const double* __restrict__ wv, const double* __restrict__ alpha,
+                                                                int64_t n, double noise, const Hyper* __restrict__ hp,
+                                                                double* __restrict__ out, int64_t bsP = 0, int64_t bsW = 0,
+                                                                int64_t bsA = 0, int64_t bsO = 0) {
+  part += blockIdx.y * bsP;
+  wv += blockIdx.y * bsW;
+  alpha += blockIdx.y * bsA;
+  out += blockIdx.y * bsO;
+  if (hp) noise = hp[blockIdx.y].noise;
+  __shared__ double r[2][4];
+  double sb = 0.0, sw = 0.0;
+  for (int64_t c = threadIdx.x; c < n; c += 256) {
+    double col = 0.0;
+    for (int rb = 0; rb < nrb; ++rb) col += part[(int64_t)rb * ldp + c];
+    sb += col;
+    sw = __builtin_fma(wv[c], alpha[c], sw);
+  }
+  sb = wave_sum(sb);
+  sw = wave_sum(sw);
+  if ((threadIdx.x & 63) == 0) {
+    r[0][threadIdx.x >> 6] = sb;
+    r[1][threadIdx.x >> 6] = sw;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double tb = ((r[0][0] + r[0][1]) + r[0][2]) + r[0][3], tw = ((r[1][0] + r[1][1]) + r[1][2]) + r[1][3];
+    *out = -noise * (tb + tw);
+  }
+}
+
 }  // namespace bobe

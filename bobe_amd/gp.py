@@ -163,12 +163,16 @@ class GP:
                  kernel_variance_bounds=[1e-4, 1e8], lengthscale_bounds=[0.01, 5], lengthscales=None,
                  kernel_variance=None, kernel_variance_prior=None, lengthscale_prior=None, tausq=None,
                  tausq_bounds=[1e-4, 1e4], param_names: Optional[List[str]] = None, device: int = 0,
-                 pivot_floor_ulp: Optional[float] = None, _factor: bool = True, fit_objective: str = "mll"):
+                 pivot_floor_ulp: Optional[float] = None, _factor: bool = True, fit_objective: str = "mll",
+                 fit_noise: bool = False, noise_bounds=[1e-10, 1e-1], noise_prior=None):
         """Same keywords as BOBE/gp.py:201-203 plus ``device`` (HIP device index) and ``pivot_floor_ulp`` (None: the
         library's default, 0 = the reference's rule - a factorisation fails only on a pivot <= 0, gp.py:175, 549; 64 is
         what ``BOBE(...)`` passes, see the property).  ``_factor=False`` (internal) leaves the factorisation to the caller,
         which is about to install a known one (``from_state_dict``, ``copy``).  ``fit_objective``: what ``fit`` minimises,
-        'mll' (the reference's -(MLL + log prior)) or 'loo' (see the ``fit_objective`` property)."""
+        'mll' (the reference's -(MLL + log prior)) or 'loo' (see the ``fit_objective`` property).  ``fit_noise=True`` (a build
+        addition; off, nothing changes) makes the noise level the last hyper-parameter of ``fit``: ``noise`` is then its
+        start value, ``noise_bounds`` its box and ``noise_prior`` a ``make_distribution`` spec (None: Uniform over the
+        bounds, a constant)."""
         self._lib = _lib.load()
         self._h = C.c_void_p(0)
         self.device = int(device)
@@ -200,6 +204,11 @@ class GP:
         self.kernel_variance_bounds = kernel_variance_bounds
         self.tausq = float(tausq) if tausq is not None else 1.0
         self.tausq_bounds = tausq_bounds
+        self.fit_noise = bool(fit_noise)
+        self.noise_bounds = [float(b) for b in np.asarray(noise_bounds, dtype=np.float64).reshape(-1).tolist()]
+        self.noise_prior_spec = noise_prior
+        self.noise_prior_dist = (P.make_distribution(noise_prior) if noise_prior is not None
+                                 else P.Uniform(self.noise_bounds[0], self.noise_bounds[1]))
 
         self._setup_kernel_variance_prior(kernel_variance_prior)
         self._setup_lengthscale_prior(lengthscale_prior)
@@ -294,6 +303,9 @@ class GP:
         if self.lengthscale_prior_spec == "SAAS":
             self.hyperparam_names.append("tausq")
             bounds.append(self.tausq_bounds)
+        if self.fit_noise:                     # always the last entry
+            self.hyperparam_names.append("noise")
+            bounds.append(self.noise_bounds)
         self.hyperparam_bounds = np.log(np.array(bounds, dtype=np.float64).T)
         self.num_hyperparams = self.hyperparam_bounds.shape[1]
 
@@ -325,6 +337,8 @@ class GP:
     def _parse_hyperparams(self, log_params):
         """BOBE/gp.py:368-383."""
         hp = np.exp(np.asarray(log_params, dtype=np.float64))
+        if self.fit_noise and len(hp) == self.num_hyperparams:
+            hp = hp[:-1]                       # (the noise is the last entry: _parse_noise)
         ls = hp[:self.ndim]
         if self.fixed_kernel_variance:
             kvar = self.kernel_variance
@@ -336,6 +350,12 @@ class GP:
             kvar = hp[self.ndim]
             tausq = hp[self.ndim + 1] if len(hp) > self.ndim + 1 else self.tausq
         return ls, float(kvar), float(tausq)
+
+    def _parse_noise(self, log_params) -> float:
+        """The noise level of a hyper-parameter vector: its last entry with ``fit_noise``, else the GP's own."""
+        if self.fit_noise and len(log_params) == self.num_hyperparams:
+            return float(np.exp(np.asarray(log_params, dtype=np.float64)[-1]))
+        return float(self.noise)
 
     # ------------------------------------------------------------------ objective
     def mll_data(self, lengthscales, kernel_variance, want_grad=True, slot=None):
@@ -368,28 +388,90 @@ class GP:
         _lib.check(st, "bobe_gp_mll_batch")
         return mll, grad
 
+    def _noise_call(self, name, lengthscales, kernel_variance, noise, want_grad):
+        ls = _lib.as_f64(lengthscales).reshape(-1)
+        val = C.c_double(0.0)
+        grad = np.empty(self.ndim + 2) if want_grad else None
+        _lib.check(getattr(self._lib, name)(self._h, _lib.ptr(ls), float(kernel_variance), float(noise), C.byref(val),
+                                            _lib.ptr(grad)), name)
+        return val.value, grad
+
+    def _noise_call_batch(self, name, lengthscales, kernel_variances, noises, want_grad):
+        ls = _lib.as_f64(lengthscales).reshape(-1, self.ndim)
+        B = ls.shape[0]
+        kv = _lib.as_f64(kernel_variances).reshape(B)
+        nz = _lib.as_f64(noises).reshape(B)
+        val = np.empty(B)
+        grad = np.empty((B, self.ndim + 2)) if want_grad else None
+        status = np.zeros(B, dtype=np.int32)
+        _lib.check(getattr(self._lib, name)(self._h, B, _lib.ptr(ls), _lib.ptr(kv), _lib.ptr(nz), _lib.ptr(val),
+                                            _lib.ptr(grad), C.c_void_p(status.ctypes.data)), name)
+        return val, grad
+
+    def mll_data_noise(self, lengthscales, kernel_variance, noise, want_grad=True):
+        """``mll_data`` at an explicit noise level, with the gradient wrt (log ls, log kvar, log noise) - ndim + 2 entries
+        (``bobe_gp_mll_noise``).  The value and the first ndim + 1 entries have ``mll_data``'s bits at the same noise."""
+        return self._noise_call("bobe_gp_mll_noise", lengthscales, kernel_variance, noise, want_grad)
+
+    def mll_data_noise_batch(self, lengthscales, kernel_variances, noises, want_grad=True):
+        """``mll_data_noise`` for B vectors in lock step (``bobe_gp_mll_noise_batch``); a member has its single call's bits."""
+        return self._noise_call_batch("bobe_gp_mll_noise_batch", lengthscales, kernel_variances, noises, want_grad)
+
+    def loo_data_noise(self, lengthscales, kernel_variance, noise, want_grad=True):
+        """``loo_data`` at an explicit noise level, with ndim + 2 gradient entries (``bobe_gp_loo_objective_noise``)."""
+        return self._noise_call("bobe_gp_loo_objective_noise", lengthscales, kernel_variance, noise, want_grad)
+
+    def loo_data_noise_batch(self, lengthscales, kernel_variances, noises, want_grad=True):
+        """``loo_data_noise`` for B vectors in lock step (``bobe_gp_loo_objective_noise_batch``)."""
+        return self._noise_call_batch("bobe_gp_loo_objective_noise_batch", lengthscales, kernel_variances, noises, want_grad)
+
+    def _value_and_grad(self, objective, log_params, want_grad, slot=None):
+        """One theta through the data term of ``objective`` ('mll' / 'loo') - the noise forms with ``fit_noise``."""
+        log_params = np.asarray(log_params, dtype=np.float64)
+        ls, kvar, tausq = self._parse_hyperparams(log_params)
+        noise = None
+        if self.fit_noise:
+            noise = self._parse_noise(log_params)
+            val, g_data = (self.mll_data_noise if objective == "mll" else self.loo_data_noise)(ls, kvar, noise, want_grad)
+        elif objective == "mll":
+            val, g_data = self.mll_data(ls, kvar, want_grad, slot=slot)
+        else:
+            val, g_data = self.loo_data(ls, kvar, want_grad)
+        return self._assemble_objective(log_params, ls, kvar, tausq, val, g_data, want_grad, noise=noise)
+
+    def _value_and_grad_batch(self, objective, log_params_list, want_grad):
+        thetas = [np.asarray(t, dtype=np.float64) for t in log_params_list]
+        parsed = [self._parse_hyperparams(t) for t in thetas]
+        lss, kvs = np.array([p[0] for p in parsed]), np.array([p[1] for p in parsed])
+        noises = [None] * len(thetas)
+        if self.fit_noise:
+            noises = [self._parse_noise(t) for t in thetas]
+            fn = self.mll_data_noise_batch if objective == "mll" else self.loo_data_noise_batch
+            val, g_data = fn(lss, kvs, np.array(noises), want_grad)
+        else:
+            val, g_data = (self.mll_data_batch if objective == "mll" else self.loo_data_batch)(lss, kvs, want_grad)
+        return [self._assemble_objective(t, p[0], p[1], p[2], float(val[i]), None if g_data is None else g_data[i],
+                                         want_grad, noise=noises[i]) for i, (t, p) in enumerate(zip(thetas, parsed))]
+
     def neg_mll(self, log_params):
         """BOBE/gp.py:385-398."""
         return self.neg_mll_value_and_grad(log_params, want_grad=False)[0]
 
     def neg_mll_value_and_grad(self, log_params, want_grad=True, slot=None):
         """(f, df/dtheta) with f = -(MLL + log prior), theta = log hp — the closure optim.py:306-309 builds."""
-        log_params = np.asarray(log_params, dtype=np.float64)
-        ls, kvar, tausq = self._parse_hyperparams(log_params)
-        mll, g_data = self.mll_data(ls, kvar, want_grad, slot=slot)
-        return self._assemble_objective(log_params, ls, kvar, tausq, mll, g_data, want_grad)
+        return self._value_and_grad("mll", log_params, want_grad, slot=slot)
 
     def neg_mll_value_and_grad_batch(self, log_params_list, want_grad=True):
         """``neg_mll_value_and_grad`` for several theta at once (the concurrently running restarts of ``fit``);
         returns a list of (f, grad) pairs with exactly the values of the one-at-a-time call."""
-        thetas = [np.asarray(t, dtype=np.float64) for t in log_params_list]
-        parsed = [self._parse_hyperparams(t) for t in thetas]
-        mll, g_data = self.mll_data_batch(np.array([p[0] for p in parsed]), np.array([p[1] for p in parsed]), want_grad)
-        return [self._assemble_objective(t, p[0], p[1], p[2], float(mll[i]), None if g_data is None else g_data[i],
-                                         want_grad) for i, (t, p) in enumerate(zip(thetas, parsed))]
+        return self._value_and_grad_batch("mll", log_params_list, want_grad)
 
-    def _assemble_objective(self, log_params, ls, kvar, tausq, mll, g_data, want_grad):
+    def _assemble_objective(self, log_params, ls, kvar, tausq, mll, g_data, want_grad, noise=None):
+        """``noise`` (with ``fit_noise``): the vector's noise level - its prior joins the value, and the last gradient
+        entry is the data term's d / d log noise plus the prior's by the chain rule."""
         lp, g_ls, g_kvar, g_tau = self._prior_and_grad(ls, kvar, tausq)
+        if noise is not None:
+            lp = lp + float(np.sum(self.noise_prior_dist.log_prob(noise)))
         val = -(mll + lp)
         if not want_grad:
             return val, None
@@ -401,6 +483,8 @@ class GP:
             idx += 1
         if "tausq" in self.hyperparam_names and len(log_params) > idx:
             grad[idx] = g_tau * tausq
+        if noise is not None:
+            grad[-1] = g_data[self.ndim + 1] + float(np.sum(self.noise_prior_dist.dlog_prob(noise))) * noise
         return val, -grad
 
     # ------------------------------------------------------------------ leave-one-out cross-validation
@@ -476,19 +560,12 @@ class GP:
         """(f, df/dtheta) with f = -(L_LOO + log prior), theta = log hp: ``neg_mll_value_and_grad`` with the LOO log
         pseudo-likelihood in the place of the marginal likelihood (priors, a fixed kernel variance and tausq handled by the
         same ``_assemble_objective``)."""
-        log_params = np.asarray(log_params, dtype=np.float64)
-        ls, kvar, tausq = self._parse_hyperparams(log_params)
-        val, g_data = self.loo_data(ls, kvar, want_grad)
-        return self._assemble_objective(log_params, ls, kvar, tausq, val, g_data, want_grad)
+        return self._value_and_grad("loo", log_params, want_grad)
 
     def neg_loo_value_and_grad_batch(self, log_params_list, want_grad=True):
         """``neg_loo_value_and_grad`` for several theta at once (the restarts of a ``fit_objective='loo'`` fit advancing in
         lock step); returns a list of (f, grad) pairs with exactly the values of the one-at-a-time call."""
-        thetas = [np.asarray(t, dtype=np.float64) for t in log_params_list]
-        parsed = [self._parse_hyperparams(t) for t in thetas]
-        val, g_data = self.loo_data_batch(np.array([p[0] for p in parsed]), np.array([p[1] for p in parsed]), want_grad)
-        return [self._assemble_objective(t, p[0], p[1], p[2], float(val[i]), None if g_data is None else g_data[i],
-                                         want_grad) for i, (t, p) in enumerate(zip(thetas, parsed))]
+        return self._value_and_grad_batch("loo", log_params_list, want_grad)
 
     def fit(self, x0: np.ndarray = None, maxiter: int = 500) -> dict:
         """BOBE/gp.py:400-437.  With ``fit_objective='loo'`` the returned ``'mll'`` is L_LOO + log prior at the optimum."""
@@ -513,6 +590,8 @@ class GP:
         if self.concurrent_restarts and x0.shape[0] > 1 and self.mll_optimize is optimize_scipy:
             if lockstep:
                 extra = {"batch_value_and_grad": self.neg_mll_value_and_grad_batch}
+            elif self.fit_noise:
+                extra = {}                     # (no slot form of the noise entry points: one restart after another)
             else:
                 extra = {"slot_value_and_grad": lambda x, slot: self.neg_mll_value_and_grad(x, slot=slot),
                          "n_slots": self.restart_slots}
@@ -528,6 +607,8 @@ class GP:
         if not self.fixed_kernel_variance:
             self.kernel_variance = kvar
         self.tausq = tausq
+        if self.fit_noise:
+            self.noise = float(np.clip(self._parse_noise(hyperparams), self.noise_bounds[0], self.noise_bounds[1]))
         self.recompute_cholesky()
 
     def recompute_cholesky(self):
@@ -932,7 +1013,7 @@ class GP:
     def state_dict(self, with_factor: bool = True):
         """Same keys as BOBE/gp.py:597-634 (npz-interchangeable).  ``with_factor=False`` (internal, ``copy``) leaves
         the N x N factor on the GPU."""
-        return {
+        state = {
             "train_x": np.array(self.train_x),
             "train_y": np.array(self.train_y * self.y_std + self.y_mean),
             "lengthscales": np.array(self.lengthscales),
@@ -955,6 +1036,12 @@ class GP:
             "ndim": self.ndim,
             "gp_class": "GP",
         }
+        if self.fit_noise:                     # (off: key for key the reference's dictionary)
+            state.update(self._noise_state())
+        return state
+
+    def _noise_state(self) -> dict:
+        return {"fit_noise": True, "noise_bounds": list(self.noise_bounds), "noise_prior": self.noise_prior_spec}
 
     @classmethod
     def from_state_dict(cls, state, device: int = 0, _clone_of=None):
@@ -972,7 +1059,9 @@ class GP:
                  lengthscale_prior=plain(state.get("lengthscale_prior_spec")),
                  tausq=plain(state.get("tausq", 1.0)),
                  tausq_bounds=list(np.asarray(state.get("tausq_bounds", [1e-4, 1e4])).tolist()), device=device,
-                 _factor=False)
+                 _factor=False, fit_noise=bool(plain(state.get("fit_noise", False))),
+                 noise_bounds=list(np.asarray(state.get("noise_bounds", [1e-10, 1e-1])).tolist()),
+                 noise_prior=plain(state.get("noise_prior")))
         L, a = state.get("cholesky"), state.get("alphas")
         if _clone_of is not None:
             _lib.check(gp._lib.bobe_gp_clone_state(gp._h, _clone_of._h), "bobe_gp_clone_state")
@@ -1031,6 +1120,8 @@ class GP:
             hp = np.hstack([hp, self.kernel_variance])
         if self.lengthscale_prior_spec == "SAAS":
             hp = np.hstack([hp, self.tausq])
+        if self.fit_noise:
+            hp = np.hstack([hp, self.noise])
         return hp
 
     def hyperparams_dict(self):
@@ -1039,4 +1130,6 @@ class GP:
         out = {"lengthscales": ls_str, "kernel_variance": f"{float(self.kernel_variance):.4f}"}
         if "tausq" in self.hyperparam_names:
             out["tausq"] = f"{float(self.tausq):.4f}"
+        if self.fit_noise:
+            out["noise"] = f"{float(self.noise):.4e}"
         return out

@@ -133,6 +133,31 @@ int bobe_gp_loo_objective(bobe_gp_t* gp, const double* lengthscales, double kern
 int bobe_gp_loo_objective_batch(bobe_gp_t* gp, int64_t B, const double* lengthscales, const double* kernel_variance,
                                 double* loo, double* grad, int* status);
 
+/* The noise level as a hyper-parameter (a build addition: the reference keeps the noise a constructor constant).  The four
+ * calls below are their namesakes with the noise nu given explicitly instead of taken from set_hyper, and with a gradient of
+ * d+2 entries: d / d log ls_j (j < d), d / d log kernel_variance, d / d log nu.  With K~ = K + nu I, A = K~^-1, alpha = A y,
+ * a_i = A_ii = sum_{k >= i} (L^-1)_ki^2 and the c, b, w, B = diag(sqrt c) A of bobe_gp_loo_objective:
+ *   d MLL   / d log nu = 1/2 nu (sum_i alpha_i^2 - sum_i a_i)              (tr K~^-1 = |L^-1|_F^2: no product, no K^-1)
+ *   d L_LOO / d log nu = nu tr M = -nu (|B|_F^2 + w^T alpha)               (|B|_F^2 = sum_k c_k (A^2)_kk)
+ * every sum over the true N x N block, in a fixed order.  The value and the first d+1 gradient entries are, bit for bit, what
+ * bobe_gp_mll / bobe_gp_loo_objective return on a handle whose set_hyper noise is the same nu: the extra component comes from
+ * launches appended after theirs (one pass over L^-1's lower triangle resp. over B, bandwidth-bound).  grad == NULL: the value
+ * alone, no extra launch.  nu must be finite and > 0 (BOBE_ERR_ARG otherwise).  The installed hyper-parameters and the
+ * factorised state are not touched.  BOBE_NOT_PD (rank test included, its floor from the member's own kernel_variance + nu)
+ * -> the value and all d+2 entries are NaN.  The batch forms take noise[B] and grad B x (d+2); up to BOBE_MAX_MLL_SLOTS
+ * members advance in lock step, a lone member and every member below BOBE_LOCKSTEP_MIN_N points runs singly, and a member
+ * returns the bits of its single call.  There is NO slot form (bobe_gp_mll_submit) and no graph replay of these calls.
+ * An MLL member evaluated this way still holds its factor, recorded with its own nu: bobe_gp_set_hyper(.., nu) +
+ * bobe_gp_factor adopts it (bobe_debug_factor_source != 0); the LOO forms leave nothing to adopt. */
+int bobe_gp_mll_noise(bobe_gp_t* gp, const double* lengthscales, double kernel_variance, double noise, double* mll,
+                      double* grad);
+int bobe_gp_mll_noise_batch(bobe_gp_t* gp, int64_t B, const double* lengthscales, const double* kernel_variance,
+                            const double* noise, double* mll, double* grad, int* status);
+int bobe_gp_loo_objective_noise(bobe_gp_t* gp, const double* lengthscales, double kernel_variance, double noise, double* loo,
+                                double* grad);
+int bobe_gp_loo_objective_noise_batch(bobe_gp_t* gp, int64_t B, const double* lengthscales, const double* kernel_variance,
+                                      const double* noise, double* loo, double* grad, int* status);
+
 /* GP.predict_mean_batched / predict_var_batched / predict_batched (gp.py:450-493) for C query points
  * Xq (C x d).  mean[c] = k_c^T alpha; var[c] = kvar + noise - |L^-1 k_c|^2 with
  *   nan_policy 0: clip(var, 1e-12) keeps NaN (predict_var_single, gp.py:465)
