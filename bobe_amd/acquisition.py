@@ -158,18 +158,29 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
     """BOBE/acquisition.py:333-412."""
 
     _key = "wipv"
+    _pool_only_logged = False
 
-    def fun(self, x, gp, mc_points=None, k_train_mc=None):
-        r = gp.wip_sweep(np.atleast_2d(x), mc_points)
+    def _weighted(self, log_weights) -> bool:
+        """True where the scores come from ``bobe_gp_wip_sweep_w``: IMIQR / EIV, or integration points with log-weights."""
+        return self._key in ("imiqr", "eiv") or log_weights is not None
+
+    def fun(self, x, gp, mc_points=None, k_train_mc=None, *, log_weights=None):
+        if self._weighted(log_weights):
+            r = gp.wip_sweep(np.atleast_2d(x), mc_points, log_weights=log_weights, criteria=(self._key,))
+        else:
+            r = gp.wip_sweep(np.atleast_2d(x), mc_points)
         return r[self._key][0] if np.ndim(x) == 1 else r[self._key]
 
-    def sweep(self, gp, candidates, mc_points):
+    def sweep(self, gp, candidates, mc_points, *, log_weights=None):
         """Scores of all candidates and the argmin (acquisition.py:394-398)."""
+        if self._weighted(log_weights):
+            r = gp.wip_sweep(candidates, mc_points, log_weights=log_weights, criteria=(self._key,))
+            return r[self._key], r["argmin_" + self._key]
         r = gp.wip_sweep(candidates, mc_points)
         idx = r["argmin_v"] if self._key == "wipv" else r["argmin_s"]
         return r[self._key], idx
 
-    def sweep_best(self, gp, candidates, mc_points, group=None):
+    def sweep_best(self, gp, candidates, mc_points, group=None, *, log_weights=None):
         """(best score, index of the best candidate).  With an initialised ``torch.distributed`` group of G > 1
         ranks every rank scores its contiguous shard of the candidates on its own GPU (same factor everywhere) and
         one all-gather of (min score, global index) picks the winner, ties to the lowest index like
@@ -177,11 +188,23 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
         from .dist_sweep import dist_info, sharded_wip_sweep
         world, _, coll_dev = dist_info(group, gp.device)
         if world > 1 and candidates.shape[0] >= world:
-            _, gmin, gidx = sharded_wip_sweep(lambda c: self.sweep(gp, c, mc_points), candidates, group=group,
-                                              device=coll_dev)
+            _, gmin, gidx = sharded_wip_sweep(lambda c: self.sweep(gp, c, mc_points, log_weights=log_weights), candidates,
+                                              group=group, device=coll_dev)
             return float(gmin), int(gidx)
-        vals, idx = self.sweep(gp, candidates, mc_points)
+        vals, idx = self.sweep(gp, candidates, mc_points, log_weights=log_weights)
         return float(vals[idx]), int(idx)
+
+    @staticmethod
+    def _integration_points(acq_kwargs, rng):
+        """(mc_points, log_weights).  ``acq_kwargs['mc_log_weights']`` belongs to explicit ``acq_kwargs['mc_points']`` (what
+        ``get_mc_points(weighted=True)`` returns); without it the points are drawn as ever (``acq_kwargs['mc_points']`` is not
+        looked at) and carry no weights."""
+        lw = acq_kwargs.get("mc_log_weights")
+        if lw is not None:
+            if acq_kwargs.get("mc_points") is None:
+                raise ValueError("acq_kwargs['mc_log_weights'] needs the points it belongs to in acq_kwargs['mc_points']")
+            return np.asarray(acq_kwargs["mc_points"]), lw
+        return get_mc_points(acq_kwargs.get("mc_samples"), mc_points_size=acq_kwargs.get("mc_points_size", 128), rng=rng), None
 
     def get_next_batch(self, gp: GP, n_batch: int = 1, acq_kwargs=None, maxiter: int = 500, n_restarts: int = 8,
                        verbose: bool = True, early_stop_patience: int = 25, rng=None, *, batch_mode: str = "believer"):
@@ -201,21 +224,28 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
             raise ValueError(f"batch_mode must be 'believer' or 'sweep', not {batch_mode!r}")
         acq_kwargs = acq_kwargs if acq_kwargs is not None else {}
         mc_samples = acq_kwargs.get("mc_samples")
-        mc_points = get_mc_points(mc_samples, mc_points_size=acq_kwargs.get("mc_points_size", 128), rng=rng)
+        mc_points, log_weights = self._integration_points(acq_kwargs, rng)
         candidates = acq_kwargs.get("candidates")
         if candidates is None:
             candidates = mc_samples["x"]
-        r = gp.wip_select_batch(candidates, mc_points, n_batch, criterion=self._key)
+        if log_weights is None:
+            r = gp.wip_select_batch(candidates, mc_points, n_batch, criterion=self._key)
+        else:
+            r = gp.wip_select_batch_w(candidates, mc_points, n_batch, criterion=self._key, log_weights=log_weights)
         return np.array(r["points"]), np.array(r["scores"])
 
     def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 100, n_restarts: int = 1, verbose: bool = True,
                        early_stop_patience: int = 25, rng=None):
         acq_kwargs = acq_kwargs if acq_kwargs is not None else {}
-        mc_samples = acq_kwargs.get("mc_samples")
-        mc_points_size = acq_kwargs.get("mc_points_size", 128)
-        mc_points = get_mc_points(mc_samples, mc_points_size=mc_points_size, rng=rng)
-        best_val, idx = self.sweep_best(gp, mc_points, mc_points)            # candidates == integration points
+        mc_points, log_weights = self._integration_points(acq_kwargs, rng)
+        best_val, idx = self.sweep_best(gp, mc_points, mc_points, log_weights=log_weights)   # candidates == integration points
         best_x = np.array(mc_points[idx])
+        if self._weighted(log_weights):
+            # (the score gradients - bobe_gp_wip_grad - exist for equal-weight WIPV / WIPStd only)
+            if not self._pool_only_logged:                 # (once per acquisition object: BOBE.run makes one per stage)
+                log.info(f"{self.name}: weighted scores pick from the candidate pool, without the L-BFGS polish")
+                self._pool_only_logged = True
+            return best_x, best_val
         if gp.train_x.shape[0] > 500:                                          # acquisition.py:400-401
             return best_x, best_val
 
@@ -239,17 +269,36 @@ class WIPStd(WeightedIntegratedPosteriorBase):
     _key = "wipstd"
 
 
+class IMIQR(WeightedIntegratedPosteriorBase):
+    """The integrated median interquartile range of the lognormal likelihood estimate exp(f) (Jarvenpaa, Gutmann, Vehtari,
+    Marttinen, Bayesian Analysis 2021; no counterpart in the reference): ``log sum_z e^{a_z} 2 sinh(u sqrt(v+))``, of which
+    WIPStd is the small-sigma linearisation.  Picks from the candidate pool."""
+    name: str = "IMIQR"
+    _key = "imiqr"
+
+
+class EIV(WeightedIntegratedPosteriorBase):
+    """The expected integrated variance of exp(f) (same paper), as the negative log of the candidate's gain R(c): EIV = S -
+    R(c) with log S = ``wip_sweep(...)['log_eiv_total']``.  Picks from the candidate pool."""
+    name: str = "EIV"
+    _key = "eiv"
+
+
 def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, method="NUTS", num_chains=4,
-                   np_rng=None, rng_key=None, *, sampler="hmc"):
+                   np_rng=None, rng_key=None, *, sampler="hmc", weighted=False):
     """BOBE/acquisition.py:468-482: 'NUTS' (Hamiltonian Monte Carlo on the surrogate, batched on the GPU), 'NS'
     (nested sampling on the surrogate) or 'uniform' (scrambled Sobol).  ``sampler`` picks the chains of 'NUTS':
-    'hmc' (the default) or 'nuts' (No-U-Turn transitions on the device, ``sample_GP_NUTS``)."""
+    'hmc' (the default) or 'nuts' (No-U-Turn transitions on the device, ``sample_GP_NUTS``).  ``weighted`` ('NS' only): keep
+    the nested samples with their weights instead of resampling them to equal weights (``get_mc_points(weighted=True)``)."""
     if method == "uniform":
         return {"x": qmc.Sobol(gp.ndim, scramble=True, seed=np_rng).random(num_samples)}
     if method == "NS":                                   # acquisition.py:473-475, batched on the GPU GP
         from .samplers import nested_sampling
         rng = np_rng if isinstance(np_rng, np.random.Generator) else np.random.default_rng(np_rng)
-        samples, _, _ = nested_sampling(gp, ndim=gp.ndim, mode="acq", rng=rng)
+        if weighted:
+            samples, _, _ = nested_sampling(gp, ndim=gp.ndim, mode="acq", rng=rng, keep_weights=True)
+        else:
+            samples, _, _ = nested_sampling(gp, ndim=gp.ndim, mode="acq", rng=rng)
         return samples
     if method == "NUTS":                                 # acquisition.py:470-472, batched HMC on the GPU GP
         from .samplers import sample_GP_NUTS
@@ -259,8 +308,19 @@ def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, metho
     raise ValueError(f"Unknown method {method} for sampling GP")          # acquisition.py:481
 
 
-def get_mc_points(mc_samples, mc_points_size=128, rng=None):
-    """BOBE/acquisition.py:485-489."""
+def get_mc_points(mc_samples, mc_points_size=128, rng=None, *, weighted=False):
+    """BOBE/acquisition.py:485-489.  ``weighted=True``: the ``mc_points_size`` heaviest samples by ``mc_samples['weights']``
+    (ties by index; nothing is drawn from the generator) and their log-weights under the flat prior measure, ``log(weights) -
+    logl`` - returns ``(points, log_weights)``, what ``GP.wip_sweep(log_weights=)`` takes."""
+    if weighted:
+        if mc_samples.get("weights") is None or mc_samples.get("logl") is None:
+            raise ValueError("weighted integration points need mc_samples['weights'] and mc_samples['logl']")
+        w = np.asarray(mc_samples["weights"], dtype=np.float64).reshape(-1)
+        idxs = np.argsort(-w, kind="stable")[:mc_points_size]
+        idxs = idxs[w[idxs] > 0.0]
+        with np.errstate(divide="ignore"):
+            lw = np.log(w[idxs]) - np.asarray(mc_samples["logl"], dtype=np.float64).reshape(-1)[idxs]
+        return np.asarray(mc_samples["x"])[idxs], lw
     mc_size = max(mc_samples["x"].shape[0], mc_points_size)
     rng = rng if rng is not None else get_numpy_rng()
     idxs = rng.choice(mc_size, size=mc_points_size, replace=False)

@@ -28,7 +28,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 from scipy.stats import qmc
 
-from .acquisition import EI, LogEI, WeightedIntegratedPosteriorBase, WIPStd, WIPV, get_mc_samples
+from .acquisition import (EI, EIV, IMIQR, LogEI, WeightedIntegratedPosteriorBase, WIPStd, WIPV, get_mc_points,
+                          get_mc_samples)
 from .dist_sweep import dist_info, merge_best_fit, shard_bounds
 from .gp import GP
 from .likelihood import Likelihood
@@ -37,7 +38,7 @@ from .utils import (get_logger, get_numpy_rng, scale_from_unit, scale_to_unit, s
 
 log = get_logger("bo")
 
-_ACQ = {"wipv": WIPV, "wipstd": WIPStd, "ei": EI, "logei": LogEI}
+_ACQ = {"wipv": WIPV, "wipstd": WIPStd, "ei": EI, "logei": LogEI, "imiqr": IMIQR, "eiv": EIV}
 
 
 def _factorisable_start(gp: GP, init: np.ndarray) -> np.ndarray:
@@ -208,6 +209,7 @@ class BOBE:
         self.hmc_thinning, self.hmc_num_chains, self.mc_points_method, self.zeta_ei = 4, 4, "NUTS", 0.01
         self.num_mc_samples, self.acq_threshold, self.verbose, self.mc_sampler = 1024, None, False, "hmc"
         self.wip_batch_mode = "believer"
+        self.mc_weighted = False
         self.min_delta_seen = np.inf
         self.current_iteration = 0
         self.start_iteration = 0
@@ -577,7 +579,8 @@ class BOBE:
             num_hmc_warmup: int = 512, num_hmc_samples: int = 512, mc_points_size: int = 64, thinning: int = 4,
             num_chains: int = 4, mc_points_method: str = "NUTS", zeta_ei: float = 0.01, *,
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
-            mc_sampler: str = "hmc", loo_diagnostics: bool = False, wip_batch_mode: str = "believer") -> dict:
+            mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
+            wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
@@ -588,7 +591,11 @@ class BOBE:
         ``wip_batch_mode`` - how a WIPV / WIPStd batch is made: 'believer' (default: the reference's loop, one sweep of the
         integration points per member) or 'sweep' (``get_next_batch(batch_mode="sweep")``: one sweep of ALL integration
         samples as the candidate pool and rank-one downdates on the device, ``GP.wip_select_batch``; the default mode leaves
-        the run's generator and the checkpoint files as they were).  ``acq`` may be a tuple of stages, run one after the other on the
+        the run's generator and the checkpoint files as they were), and ``mc_weighted`` - meant for ``mc_points_method='NS'``:
+        True (refused with any other method) keeps the nested samples' weights and integrates over the heaviest ``mc_points_size`` of them with their
+        log-weights (``get_mc_points(weighted=True)``, ``acq_kwargs['mc_log_weights']``) instead of equal-weight draws; the
+        default changes nothing.  ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
+        those criteria.  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -617,6 +624,9 @@ class BOBE:
         if wip_batch_mode not in ("believer", "sweep"):
             raise ValueError(f"wip_batch_mode must be 'believer' or 'sweep', not {wip_batch_mode!r}")
         self.wip_batch_mode = wip_batch_mode
+        if mc_weighted and mc_points_method != "NS":
+            raise ValueError(f"mc_weighted=True needs mc_points_method='NS' (weighted nested samples), not {mc_points_method!r}")
+        self.mc_weighted = bool(mc_weighted)
         self.loo_diagnostics, self.loo_history = bool(loo_diagnostics), []
         self.converged, self.convergence_counter = False, 0
         self.min_delta_seen = np.inf
@@ -679,6 +689,8 @@ class BOBE:
                 self.run_WIPV(ii=self.current_iteration)
             elif a.lower() == "wipstd":
                 self.run_WIPStd(ii=self.current_iteration)
+            elif a.lower() in ("imiqr", "eiv"):
+                self.run_weighted_integrated_posterior(_ACQ[a.lower()], ii=self.current_iteration)
             else:
                 self.run_EI(ii=self.current_iteration)
         log.info(f"Final best point {self.best} with value = {self.best_f:.6f}, found at iteration {self.best_pt_iteration}")
@@ -732,8 +744,9 @@ class BOBE:
                                 thinning=self.hmc_thinning, method="NUTS", num_chains=self.hmc_num_chains,
                                 np_rng=self.np_rng, sampler=self.mc_sampler)
         else:
+            extra = {"weighted": True} if self.mc_weighted and self.mc_points_method == "NS" else {}
             mc = get_mc_samples(self.gp, num_samples=self.num_mc_samples, method=self.mc_points_method,
-                                np_rng=self.np_rng)
+                                np_rng=self.np_rng, **extra)
         self.timing["MCMC Sampling"] += time.time() - t0
         return mc
 
@@ -756,6 +769,9 @@ class BOBE:
             if self.verbose:
                 log.info(f"Iteration {ii} of {acq_name}, objective evals {current_evals}/{self.max_evals}")
             acq_kwargs = {"mc_samples": self.mc_samples, "mc_points_size": self.mc_points_size}
+            if self.mc_weighted and self.mc_samples.get("weights") is not None:
+                acq_kwargs["mc_points"], acq_kwargs["mc_log_weights"] = get_mc_points(
+                    self.mc_samples, mc_points_size=self.mc_points_size, weighted=True)
             new_pts_u, acq_vals = self.get_next_batch(acq_kwargs, n_batch=self.batch_size, n_restarts=1, maxiter=100,
                                                       early_stop_patience=10, step=ii, verbose=self.verbose)  # bo.py:1274
             new_pts_u = np.atleast_2d(new_pts_u)
@@ -779,6 +795,9 @@ class BOBE:
                     self.mc_samples = {"x": equal_samples, "logl": equal_logl,
                                        "weights": np.ones(equal_samples.shape[0]), "method": "NS",
                                        "best": ns_samples["best"]}
+                    if self.mc_weighted:                     # (the weighted samples themselves are the integration samples)
+                        self.mc_samples = {"x": ns_samples["x"], "logl": ns_samples["logl"], "weights": ns_samples["weights"],
+                                           "method": "NS", "best": ns_samples["best"]}
                     self.results_dict["logz"] = logz_dict
                     self.converged = self.check_convergence_logz(ii, logz_dict, equal_samples, equal_logl,
                                                                  verbose=self.verbose)

@@ -348,6 +348,25 @@ int bobe_gp_wip_select_batch(bobe_gp_t* g, const double* cand, int64_t C, const 
   API_END
 }
 
+int bobe_gp_wip_sweep_w(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                        const double* logw, double* wipv, double* wipstd, double* imiqr, double* eiv, double* log_s,
+                        int64_t* argmin, double* min) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  double* const outs[4] = {wipv, wipstd, imiqr, eiv};
+  return g->wip_sweep_w(cand, C, Z, M, y_std, logw, outs, log_s, argmin, min);
+  API_END
+}
+
+int bobe_gp_wip_select_batch_w(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                               const double* logw, int n_batch, int criterion, int64_t* picks, double* pick_scores,
+                               double* stage_scores) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  return g->wip_select_batch_w(cand, C, Z, M, y_std, logw, n_batch, criterion, picks, pick_scores, stage_scores);
+  API_END
+}
+
 int bobe_gp_fantasy_var(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                         double* out) {
   API_BEGIN

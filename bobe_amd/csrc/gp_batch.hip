@@ -21,9 +21,18 @@ constexpr size_t BATCH_KEEP_BYTES = size_t(16) << 30;
 
 int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch,
                               int criterion, int64_t* picks, double* pick_scores, double* stage_scores) {
+  if (criterion != 0 && criterion != 1) throw Err(BOBE_ERR_ARG, "criterion must be 0 (WIPV) or 1 (WIPStd)");
+  return select_batch(cand, C, Z, M, y_std, n_batch, criterion, picks, pick_scores, stage_scores, nullptr);
+}
+
+// w (bobe_gp_wip_select_batch_w, gp_criteria.hip): the weighted scorer in place of wip_score - stage 0's row comes from the
+// sweep's own weighted pass and its argmin from k_argmin_masked with nothing masked (k_argmin's rule), a later stage refreshes
+// the table's base_z terms from the call's downdated copy and scores with k_wip_score_w.  Everything else is shared.
+int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch,
+                          int criterion, int64_t* picks, double* pick_scores, double* stage_scores, SweepW* w) {
   if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
   if (n_batch < 1 || n_batch > BATCH_MAX || n_batch > C) throw Err(BOBE_ERR_ARG, "n_batch must be in [1, min(C, 64)]");
-  if (criterion != 0 && criterion != 1) throw Err(BOBE_ERR_ARG, "criterion must be 0 (WIPV) or 1 (WIPStd)");
+  if (criterion < 0 || criterion > (w ? 3 : 1)) throw Err(BOBE_ERR_ARG, "criterion out of range");
   if (!picks) throw Err(BOBE_ERR_ARG, "picks is NULL");
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   const int64_t Cp = round_up(C, TILE), Mp = round_up(M, TILE);
@@ -63,13 +72,23 @@ int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, in
   double val0 = 0.0;
   SweepReq rq;
   rq.cand = cand; rq.C = C; rq.Z = Z; rq.M = M; rq.y_std = y_std;
-  (wipv ? rq.wipv : rq.wipstd) = stage_row(0);
-  (wipv ? rq.argmin_v : rq.argmin_s) = &pick0;
-  (wipv ? rq.min_v : rq.min_s) = &val0;
   rq.keep = &keep;
-  sweep(rq);                                             // (synchronises: pick0 / val0 are on the host)
-  HIPCHK(hipMemcpyAsync(d_picks, &pick0, sizeof(int64_t), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(dval.p, &val0, sizeof(double), hipMemcpyHostToDevice, stream));
+  if (w) {
+    for (double*& o : w->out) o = nullptr;
+    w->out[criterion] = stage_row(0);
+    rq.w = w;
+    sweep(rq);
+    hipLaunchKernelGGL(k_argmin_masked, dim3(1), dim3(1024), 0, stream, (const double*)stage_row(0), C, d_picks, 0,
+                       static_cast<double*>(dval.p));
+    LAUNCH_CHECK();
+  } else {
+    (wipv ? rq.wipv : rq.wipstd) = stage_row(0);
+    (wipv ? rq.argmin_v : rq.argmin_s) = &pick0;
+    (wipv ? rq.min_v : rq.min_s) = &val0;
+    sweep(rq);                                           // (synchronises: pick0 / val0 are on the host)
+    HIPCHK(hipMemcpyAsync(d_picks, &pick0, sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dval.p, &val0, sizeof(double), hipMemcpyHostToDevice, stream));
+  }
 
   // ---- stages 1 .. n_batch - 1: rank-one downdates of crossT, base_z, s_c and a rescoring, queued without a host round trip
   if (nu > 0) {
@@ -103,7 +122,13 @@ int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, in
     hipLaunchKernelGGL(k_batch_rank1, dim3((unsigned)((Cp + 255) / 256), (unsigned)(Mp / 16)), dim3(256), 0, stream, xT.d(), Cp, Cp,
                        (const double*)uzj, (const double*)ucj);
     double* row = stage_row(j);
-    wip_score(xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, wipv ? row : nullptr, wipv ? nullptr : row, nullptr);
+    if (w) {
+      if (criterion == 3) wip_zterms(*w, M, Mp, y_std, bz.d(), false);
+      w->out[criterion] = row;
+      wip_score_w(*w, xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, 0);
+    } else {
+      wip_score(xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, wipv ? row : nullptr, wipv ? nullptr : row, nullptr);
+    }
     hipLaunchKernelGGL(k_argmin_masked, dim3(1), dim3(1024), 0, stream, (const double*)row, C, d_picks, j,
                        static_cast<double*>(dval.p) + j);
     LAUNCH_CHECK();

@@ -7,6 +7,7 @@
 //   gp_posterior.hip  joint posterior covariance at query points and correlated draws from it
 //   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
 //   gp_batch.hip      one-sweep batch selection for WIPV / WIPStd (the sweep's intermediates kept, rank-one downdates)
+//   gp_criteria.hip   importance-weighted integration points, IMIQR / EIV: the weighted scoring pass of the sweep and the batch
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
 // without a HIP device every entry point fails with BOBE_ERR_HIP.
@@ -230,6 +231,18 @@ struct SweepKeep {
   int64_t ldv_used = 0;
 };
 
+// Importance-weighted scoring of a sweep (SweepReq::w; bobe_gp_wip_sweep_w / bobe_gp_wip_select_batch_w, gp_criteria.hip).
+// After prepare_z the sweep has the per-z table built (bobe_gp::wip_zterms) and scores every super-chunk with k_wip_score_w
+// into out[criterion] (device memory, C each; NULL = not wanted) - next to, not instead of, what SweepReq::wipv / wipstd ask
+// of the equal-weight scorer.  The buffers belong to the call.
+struct SweepW {
+  const double* logw = nullptr;     // M log-weights, host or device; NULL: the points are draws of the surrogate posterior
+  double* out[4] = {nullptr, nullptr, nullptr, nullptr};   // wipv, wipstd, imiqr, eiv
+  CallBuf zt, zpart, lstage;        // the table [ZTERM_ROWS x Mp] + log S, the partial sums of K(X,Z)^T alpha, logw staged
+  int64_t ldt = 0;
+  double* log_s() const { return zt.d() + (int64_t)ZTERM_ROWS * ldt; }   // (zt holds 8 doubles behind the table)
+};
+
 // What bobe_gp::sweep is asked for: C candidates, optionally scored against M integration points Z (Z = NULL: prediction
 // only).  Every output may be NULL (host or device memory otherwise; the argmin / min ones are host scalars).
 struct SweepReq {
@@ -250,6 +263,7 @@ struct SweepReq {
   double* fantasy_out = nullptr;    // C x M fantasy variances, dense
   bool gated = false;               // apply the classifier gate (when one is set) to mean / var (the predict family)
   SweepKeep* keep = nullptr;
+  SweepW* w = nullptr;              // the weighted scoring pass in addition (NULL: today's launches, nothing else)
 };
 
 // What a member of an evaluation workspace (bobe_gp::EvalWs: the lock-step batch, an evaluation slot, the handle's own)
@@ -641,6 +655,20 @@ struct bobe_gp {
   // ---- gp_batch.hip (call-local buffers only; the handle's Z-side state is read, never written)
   int wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,
                        int64_t* picks, double* pick_scores, double* stage_scores);
+  // the batch selection itself; w: score with the weighted scorer (criterion 0 .. 3) instead of wip_score (0 / 1)
+  int select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,
+                   int64_t* picks, double* pick_scores, double* stage_scores, bobe::SweepW* w);
+
+  // ---- gp_criteria.hip: the importance-weighted scoring pass (criteria_kernels.hpp)
+  // the per-z table of w for the base_z in bz (first: mu, a, omega as well; else only the terms that follow base_z)
+  void wip_zterms(bobe::SweepW& w, int64_t M, int64_t Mp, double y_std, const double* bz, bool first);
+  // k_wip_score_w on ns candidates (wip_score's arguments); writes w.out[k] + off
+  void wip_score_w(const bobe::SweepW& w, const double* crossT, int64_t ldx, const double* cst, const double* scs,
+                   const double* bz, int64_t ns, int64_t M, int64_t Mp, double y_std, int64_t off);
+  int wip_sweep_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                  double* const outs[4], double* log_s, int64_t* argmin, double* mins);
+  int wip_select_batch_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                         int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

@@ -156,6 +156,8 @@ void bobe_gp::sweep(const SweepReq& r) {
   const bool need_s = wipstd || argmin_s || min_s;
   const double* cin = fetch(cand, (size_t)C * d, in_stage);
   if (do_wip) prepare_z(Z, M, Mp, false);
+  SweepW* const sw = do_wip ? r.w : nullptr;
+  if (sw) wip_zterms(*sw, M, Mp, y_std, basez.d(), true);
   // (the substitution path takes wider chunks - BOBE_SOLVE_CHUNK, speed only - unless the caller has set the chunk)
   const int64_t CH = (refine_v && solve_chunk > 0 && !chunk_set) ? solve_chunk : chunk;
   // The reference sweeps the integration points themselves (acquisition.py:394: candidates = mc_points).  Then K(X, C) and
@@ -279,8 +281,10 @@ void bobe_gp::sweep(const SweepReq& r) {
     if (do_wip) {
       double* vo = d_fant ? d_fant + s0 * M : nullptr;
       prof_begin(BOBE_PROF_CROSS);
-      wip_score(xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, d_wipv ? d_wipv + s0 : nullptr,
-                d_wipstd ? d_wipstd + s0 : nullptr, vo);
+      if (!sw || d_wipv || d_wipstd || vo)
+        wip_score(xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, d_wipv ? d_wipv + s0 : nullptr,
+                  d_wipstd ? d_wipstd + s0 : nullptr, vo);
+      if (sw) wip_score_w(*sw, xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, s0);
       prof_end(BOBE_PROF_CROSS);
       LAUNCH_CHECK();
     }

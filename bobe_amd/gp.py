@@ -834,14 +834,68 @@ class GP:
                                                  float(self.y_std), _lib.ptr(out)), "bobe_gp_fantasy_var")
         return out[0] if out.shape[0] == 1 else out
 
-    def wip_sweep(self, candidates, mc_points, want_mean_var=False):
+    CRITERIA = ("wipv", "wipstd", "imiqr", "eiv")
+
+    @staticmethod
+    def _log_weights(log_weights, m):
+        """``log_weights`` as what the library takes: None, a contiguous float64 torch CUDA tensor of M entries, or a finite
+        float64 array.  A device tensor is not read here: that its entries are finite is the caller's responsibility."""
+        if log_weights is None:
+            return None
+        if hasattr(log_weights, "data_ptr"):
+            import torch
+            if int(log_weights.numel()) != m:
+                raise ValueError(f"log_weights must have one entry per integration point ({m})")
+            if log_weights.dtype != torch.float64 or not log_weights.is_cuda or not log_weights.is_contiguous():
+                raise ValueError("a log_weights tensor must be a contiguous float64 CUDA tensor")
+            return log_weights
+        lw = _lib.as_f64(np.asarray(log_weights, dtype=np.float64).reshape(-1))
+        if lw.shape[0] != m or not np.all(np.isfinite(lw)):
+            raise ValueError(f"log_weights must be {m} finite values")
+        return lw
+
+    def _wip_sweep_w(self, cand, z, log_weights, criteria):
+        """``bobe_gp_wip_sweep_w``: the requested scores in physical units, their argmins / minima and log S."""
+        keys = self.CRITERIA if criteria is None else tuple(criteria)
+        for k in keys:
+            if k not in self.CRITERIA:
+                raise ValueError(f"criteria must be among {self.CRITERIA}, not {k!r}")
+        c, m = int(cand.shape[0]), int(z.shape[0])
+        lw = self._log_weights(log_weights, m)
+        arrs = [np.empty(c) if k in keys else None for k in self.CRITERIA]
+        log_s = C.c_double(0.0)
+        am, mn = np.full(4, -1, dtype=np.int64), np.empty(4)
+        _lib.check(self._lib.bobe_gp_wip_sweep_w(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), _lib.ptr(lw),
+                                                 *[_lib.ptr(a) for a in arrs], C.byref(log_s), _lib.ptr(am), _lib.ptr(mn)),
+                   "bobe_gp_wip_sweep_w")
+        # exp(f) lives on the physical scale: the y_mean the library leaves out shifts the log scores by a constant
+        shift = {"wipv": 0.0, "wipstd": 0.0, "imiqr": float(self.y_mean), "eiv": -2.0 * float(self.y_mean)}
+        out = {}
+        for i, k in enumerate(self.CRITERIA):
+            if k in keys:
+                out[k] = arrs[i] + shift[k] if shift[k] else arrs[i]
+                out["argmin_" + k], out["min_" + k] = int(am[i]), float(mn[i]) + shift[k]
+        out["log_eiv_total"] = log_s.value + 2.0 * float(self.y_mean)
+        return out
+
+    def wip_sweep(self, candidates, mc_points, want_mean_var=False, *, log_weights=None, criteria=None):
         """All-candidate WIPV / WIPStd scores (acquisition.py:385-398 + 438-465) in one GPU call.
 
         ``candidates`` / ``mc_points`` may be NumPy arrays or torch CUDA tensors (no copy then).
-        Returns dict(wipv, wipstd, argmin_v, min_v, argmin_s, min_s[, mean, var])."""
+        Returns dict(wipv, wipstd, argmin_v, min_v, argmin_s, min_s[, mean, var]).
+
+        ``log_weights`` (M finite log quadrature weights of the integration points under the flat prior on the unit cube, up to
+        a constant; None: the points are draws of the surrogate posterior) and / or ``criteria`` (a subset of ``wipv, wipstd,
+        imiqr, eiv``; None with weights: all four) select ``bobe_gp_wip_sweep_w`` instead: the result then holds the requested
+        scores (to minimise, physical units), ``argmin_<key>`` / ``min_<key>`` for each, and ``log_eiv_total`` = log S (the
+        expected integrated variance of a candidate is ``exp(log_eiv_total) - exp(-eiv)``)."""
         dev = hasattr(candidates, "data_ptr")
         cand = candidates if dev else _lib.as_f64(np.atleast_2d(candidates))
         z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
+        if log_weights is not None or criteria is not None:
+            if want_mean_var:
+                raise ValueError("want_mean_var goes with the equal-weight sweep only")
+            return self._wip_sweep_w(cand, z, log_weights, criteria)
         c, m = int(cand.shape[0]), int(z.shape[0])
         wipv, wipstd = np.empty(c), np.empty(c)
         mean = np.empty(c) if want_mean_var else None
@@ -867,9 +921,18 @@ class GP:
 
         ``candidates`` / ``mc_points``: NumPy arrays or torch CUDA tensors.  Returns dict(indices (n_batch,), points
         (n_batch, d), scores (n_batch,) - the winning score of every stage[, stage_scores (n_batch, C) - every stage's scores
-        of all candidates])."""
-        if criterion not in ("wipv", "wipstd"):
-            raise ValueError(f"criterion must be 'wipv' or 'wipstd', not {criterion!r}")
+        of all candidates]).
+
+        ``criterion`` 'imiqr' / 'eiv' (see ``wip_sweep``) are ``wip_select_batch_w`` without weights."""
+        return self.wip_select_batch_w(candidates, mc_points, n_batch, criterion, return_stage_scores)
+
+    def wip_select_batch_w(self, candidates, mc_points, n_batch, criterion="wipstd", return_stage_scores=False, *,
+                           log_weights=None):
+        """``wip_select_batch`` with importance-weighted integration points (``log_weights``, see ``wip_sweep``) and the four
+        criteria 'wipv', 'wipstd', 'imiqr', 'eiv' (``bobe_gp_wip_select_batch_w``): stage 0 is the weighted ``wip_sweep``
+        (same bits), the scores are physical ones as there.  Without weights 'wipv' / 'wipstd' take the equal-weight entry."""
+        if criterion not in self.CRITERIA:
+            raise ValueError(f"criterion must be one of {self.CRITERIA}, not {criterion!r}")
         dev = hasattr(candidates, "data_ptr")
         cand = candidates if dev else _lib.as_f64(np.atleast_2d(candidates))
         z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
@@ -877,9 +940,20 @@ class GP:
         picks = np.full(max(nb, 1), -1, dtype=np.int64)
         scores = np.empty(max(nb, 1))
         stage = np.empty((max(nb, 1), c)) if return_stage_scores else None
-        _lib.check(self._lib.bobe_gp_wip_select_batch(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), nb,
-                                                      0 if criterion == "wipv" else 1, _lib.ptr(picks), _lib.ptr(scores),
-                                                      _lib.ptr(stage)), "bobe_gp_wip_select_batch")
+        if log_weights is None and criterion in ("wipv", "wipstd"):
+            _lib.check(self._lib.bobe_gp_wip_select_batch(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), nb,
+                                                          0 if criterion == "wipv" else 1, _lib.ptr(picks), _lib.ptr(scores),
+                                                          _lib.ptr(stage)), "bobe_gp_wip_select_batch")
+        else:
+            lw = self._log_weights(log_weights, m)
+            _lib.check(self._lib.bobe_gp_wip_select_batch_w(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std),
+                                                            _lib.ptr(lw), nb, self.CRITERIA.index(criterion), _lib.ptr(picks),
+                                                            _lib.ptr(scores), _lib.ptr(stage)), "bobe_gp_wip_select_batch_w")
+            shift = {"imiqr": float(self.y_mean), "eiv": -2.0 * float(self.y_mean)}.get(criterion, 0.0)
+            if shift:
+                scores += shift
+                if stage is not None:
+                    stage += shift
         pts = cand[picks.tolist()].detach().cpu().numpy() if dev else np.array(cand[picks])
         out = {"indices": picks, "points": pts, "scores": scores}
         if return_stage_scores:

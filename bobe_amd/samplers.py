@@ -182,7 +182,7 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
                     maxcall: int = int(5e6), equal_weights: bool = False, rng=None, batch: int = 8192,
                     enlarge: float = 1.25, nlive: Optional[int] = None, sample_method: str = "auto",
                     walks: Optional[int] = None, device_walks: bool = True, logz_draws: int = 0,
-                    logz_draws_seed: int = 0) -> Tuple[Dict, Dict, bool]:
+                    logz_draws_seed: int = 0, *, keep_weights: bool = False) -> Tuple[Dict, Dict, bool]:
     """Static nested sampling of exp(GP mean) over the unit cube -> (samples_dict, logz_dict, success).
 
     Settings follow ``nested_sampling_Dy`` (samplers.py:119-126): mode 'acq' uses nlive = max(100, min(500, 20 d))
@@ -192,12 +192,13 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     for), 'auto' = ellipsoid up to 4 dimensions, rwalk above.  ``device_walks``: whole walks in one launch where the
     surrogate offers ``rwalk`` (``bobe_gp_rwalk``); False steps them from the host, one batched prediction per step.
     ``logz_draws`` > 0: the logZ dictionary also holds the evidence of that many joint posterior draws of the surrogate
-    (``logz_from_samples``, seeded by ``logz_draws_seed``); reported only, nothing else depends on them."""
+    (``logz_from_samples``, seeded by ``logz_draws_seed``); reported only, nothing else depends on them.
+    ``keep_weights``: mode 'acq' returns the weighted samples as they are instead of resampling them to equal weights."""
     rng = rng if rng is not None else get_numpy_rng()
     ndim = ndim if ndim is not None else gp.ndim
     if mode == "acq":
         nlive = nlive or max(100, min(500, 20 * ndim))
-        dlogz, equal_weights = 0.1, True
+        dlogz, equal_weights = 0.1, not keep_weights
     else:
         nlive = nlive or max(500, 40 * ndim)
 

@@ -205,6 +205,44 @@ int bobe_gp_wip_sweep(bobe_gp_t* gp, const double* cand, int64_t C, const double
 int bobe_gp_wip_select_batch(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                              int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores);
 
+/* bobe_gp_wip_sweep with importance-weighted integration points and two criteria on the scale of the likelihood (a build
+ * addition; the criteria are IMIQR and EIV of Jarvenpaa, Gutmann, Vehtari, Marttinen, Bayesian Analysis 2021).  For candidate
+ * c and integration point z, with v+(z|c) the scorer's fantasy variance in physical units (base_z - cross^2 / s_c, the rules
+ * of gp.py:574-576, times y_std^2):
+ *   b_z  = y_std^2 base_z (non-finite or < 1e-12 -> 1e-12),   mu_z = y_std (K(X,Z)^T alpha)_z  (no y_mean),
+ *   l_z  = logw[z]: the log of z's quadrature weight under the flat prior on the unit cube, up to a constant
+ *          (logw NULL: the points are draws of the surrogate posterior, l_z = -mu_z),
+ *   a_z  = l_z + mu_z,   omega = softmax(a),   u = Phi^-1(3/4) = 0.6744897501960817
+ *   wipv[c]   = sum_z omega_z v+                        wipstd[c] = sum_z omega_z sqrt(v+)
+ *   imiqr[c]  = log sum_z exp(a_z) 2 sinh(u sqrt(v+))   (the integrated median interquartile range of the lognormal estimate)
+ *   eiv[c]    = -log sum_z exp(l_z + 2 mu_z + 2 b_z - v+) = -log R(c)
+ *   *log_s    = log sum_z exp(l_z + 2 mu_z + 2 b_z)     = log S:  the expected integrated variance is S - R(c)
+ * All four are scores to MINIMISE.  eiv is the negative log of the candidate's gain R(c) rather than S - R(c): 1 - exp(-v+)
+ * is 1 in fp64 once v+ exceeds ~37, and every candidate ties; -log R(c) has the same argmin and does not saturate.  The two
+ * log scores are log-sum-exps with a running maximum per candidate: finite for any finite inputs with y_std > 0 (the domain:
+ * y_std = 0 or non-finite logw / state give NaN scores).
+ * With logw NULL, wipv / wipstd are bobe_gp_wip_sweep's bits (the equal-weight scorer itself).  The launch sequence is
+ * bobe_gp_wip_sweep's (plain product or blocked substitution, chunking, fused cross tiles, cand == Z) plus one scoring pass;
+ * all sums run in a fixed order: the same state gives the same bits whatever the chunk width, host or device pointers.
+ * wipv, wipstd, imiqr, eiv (C each), log_s (one double): host or device, any may be NULL and is then not computed.
+ * argmin[4] / min[4] (host, may be NULL): first-occurrence argmin (NaN counts as minimal) and minimum per criterion in the
+ * order above; -1 / NaN for a criterion whose array is NULL.  NOT gated.  The handle's state is left as it was.
+ * BOBE_ERR_ARG: NULL cand / Z, C or M < 1; BOBE_ERR_STATE without a factorised state; a NaN state behaves as in
+ * bobe_gp_wip_sweep (BOBE_OK). */
+int bobe_gp_wip_sweep_w(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                        const double* logw, double* wipv, double* wipstd, double* imiqr, double* eiv, double* log_s,
+                        int64_t* argmin, double* min);
+
+/* bobe_gp_wip_select_batch with bobe_gp_wip_sweep_w's scorer: criterion 0 wipv, 1 wipstd, 2 imiqr, 3 eiv, weights logw (M,
+ * host or device, may be NULL).  Row 0 of stage_scores and picks[0] are bobe_gp_wip_sweep_w's bits and argmin.  Under the
+ * believer append mu_z does not change, so omega and a_z are the call's; b_z follows the downdated base_z, so the terms of
+ * criterion 3 (and log S) are formed again at every stage.  y_std (and with it every physical quantity) is the CALLER's at
+ * every stage.  With logw NULL and criterion 0 / 1 the call IS bobe_gp_wip_select_batch.  Same cap, argument rules and
+ * return codes as bobe_gp_wip_select_batch (criterion outside 0 .. 3: BOBE_ERR_ARG). */
+int bobe_gp_wip_select_batch_w(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                               const double* logw, int n_batch, int criterion, int64_t* picks, double* pick_scores,
+                               double* stage_scores);
+
 /* GP.fantasy_var (gp.py:552-576) for C candidates at once: out is C x M, out[c][z] = var+(z|c)*y_std^2. */
 int bobe_gp_fantasy_var(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                         double* out);
