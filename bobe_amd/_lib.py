@@ -68,6 +68,12 @@ SIGNATURES = [
     ("bobe_gp_predict_cov", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("bobe_gp_posterior_sample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p]),
+    ("bobe_gp_paths_create", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("bobe_gp_paths_get", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("bobe_gp_paths_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    ("bobe_gp_paths_argmax", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("bobe_gp_paths_destroy", None, [C.c_void_p]),
     ("bobe_gp_wip_grad", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     ("bobe_gp_acq_ei", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_void_p]),

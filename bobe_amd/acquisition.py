@@ -284,6 +284,59 @@ class EIV(WeightedIntegratedPosteriorBase):
     _key = "eiv"
 
 
+class PathwiseTS(AcquisitionFunction):
+    """Thompson sampling by pathwise posterior draws of the surrogate (``GP.sample_paths``; no counterpart in the reference):
+    member s of a batch is the pool row that maximises path s - one draw of the surrogate per member, evaluated over the
+    whole pool on the device (``PosteriorPaths.argmax``).  The pool is ``acq_kwargs['candidates']`` or, without that key, all
+    of ``mc_samples['x']`` (the choice of ``batch_mode='sweep'``).  ``acq_kwargs['ts_mode']``: 'max' (default), classic
+    Thompson sampling, or 'posterior': a Gumbel-max draw from the pool reweighted from exp(mean) to exp(f_s) - the bias
+    handed to the argmax is Gumbel noise minus the surrogate mean.  ``acq_kwargs['ts_features']``: random Fourier features
+    per path (2048).  The paths are seeded by one ``rng.integers`` draw.  Values: the paths at their picks."""
+
+    name: str = "PathwiseTS"
+
+    def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 100, n_restarts: int = 1, verbose: bool = True,
+                       early_stop_patience: int = 25, rng=None):
+        pts, vals = self.get_next_batch(gp, n_batch=1, acq_kwargs=acq_kwargs, rng=rng)
+        return pts[0], float(vals[0])
+
+    def get_next_batch(self, gp: GP, n_batch: int = 1, acq_kwargs=None, maxiter: int = 500, n_restarts: int = 8,
+                       verbose: bool = True, early_stop_patience: int = 25, rng=None):
+        rng = rng if rng is not None else get_numpy_rng()
+        acq_kwargs = acq_kwargs if acq_kwargs is not None else {}
+        mode = acq_kwargs.get("ts_mode", "max")
+        if mode not in ("max", "posterior"):
+            raise ValueError(f"ts_mode must be 'max' or 'posterior', not {mode!r}")
+        pool = acq_kwargs.get("candidates")
+        if pool is None:
+            pool = acq_kwargs["mc_samples"]["x"]
+        on_device = hasattr(pool, "data_ptr")
+        pool_host = pool.detach().cpu().numpy() if on_device else _lib.as_f64(np.atleast_2d(pool))
+        if not on_device:
+            pool = pool_host
+        n_pool, n_batch = int(pool_host.shape[0]), int(n_batch)
+        if n_pool < n_batch:
+            raise ValueError(f"a batch of {n_batch} needs a pool of at least that many rows, not {n_pool}")
+        seed = int(rng.integers(0, 2 ** 63))
+        bias = None
+        if mode == "posterior":          # argmax_c y_std (f_s - m)(c) + G_sc, in the standardised units of the paths
+            mean, _ = gp._predict(pool_host, True, False, 0)
+            bias = rng.gumbel(size=(n_batch, n_pool)) / gp.y_std - mean[None, :]
+        with gp.sample_paths(n_batch, int(acq_kwargs.get("ts_features", 2048)), seed=seed) as paths:
+            picks, vals = paths.argmax(pool, bias)
+            taken = set()
+            for s in range(n_batch):
+                if int(picks[s]) in taken:           # the path's best row among those no earlier member took
+                    row = (paths.evaluate(pool)[s] - paths.y_mean) / paths.y_std
+                    if bias is not None:
+                        row = row + bias[s]
+                    row[list(taken)] = -np.inf
+                    picks[s] = int(np.argmax(row))
+                    vals[s] = paths.y_mean + paths.y_std * row[picks[s]]
+                taken.add(int(picks[s]))
+        return np.array(pool_host[picks]), np.array(vals)
+
+
 def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, method="NUTS", num_chains=4,
                    np_rng=None, rng_key=None, *, sampler="hmc", weighted=False):
     """BOBE/acquisition.py:468-482: 'NUTS' (Hamiltonian Monte Carlo on the surrogate, batched on the GPU), 'NS'

@@ -28,7 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 from scipy.stats import qmc
 
-from .acquisition import (EI, EIV, IMIQR, LogEI, WeightedIntegratedPosteriorBase, WIPStd, WIPV, get_mc_points,
+from .acquisition import (EI, EIV, IMIQR, LogEI, PathwiseTS, WeightedIntegratedPosteriorBase, WIPStd, WIPV, get_mc_points,
                           get_mc_samples)
 from .dist_sweep import dist_info, merge_best_fit, shard_bounds
 from .gp import GP
@@ -38,7 +38,7 @@ from .utils import (get_logger, get_numpy_rng, scale_from_unit, scale_to_unit, s
 
 log = get_logger("bo")
 
-_ACQ = {"wipv": WIPV, "wipstd": WIPStd, "ei": EI, "logei": LogEI, "imiqr": IMIQR, "eiv": EIV}
+_ACQ = {"wipv": WIPV, "wipstd": WIPStd, "ei": EI, "logei": LogEI, "imiqr": IMIQR, "eiv": EIV, "ts": PathwiseTS}
 
 
 def _factorisable_start(gp: GP, init: np.ndarray) -> np.ndarray:
@@ -595,7 +595,8 @@ class BOBE:
         True (refused with any other method) keeps the nested samples' weights and integrates over the heaviest ``mc_points_size`` of them with their
         log-weights (``get_mc_points(weighted=True)``, ``acq_kwargs['mc_log_weights']``) instead of equal-weight draws; the
         default changes nothing.  ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
-        those criteria.  ``acq`` may be a tuple of stages, run one after the other on the
+        those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
+        samples.  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -689,7 +690,7 @@ class BOBE:
                 self.run_WIPV(ii=self.current_iteration)
             elif a.lower() == "wipstd":
                 self.run_WIPStd(ii=self.current_iteration)
-            elif a.lower() in ("imiqr", "eiv"):
+            elif a.lower() in ("imiqr", "eiv", "ts"):
                 self.run_weighted_integrated_posterior(_ACQ[a.lower()], ii=self.current_iteration)
             else:
                 self.run_EI(ii=self.current_iteration)

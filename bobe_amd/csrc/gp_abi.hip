@@ -397,6 +397,39 @@ int bobe_gp_posterior_sample(bobe_gp_t* g, const double* Xq, int64_t C, int64_t 
   API_END
 }
 
+int bobe_gp_paths_create(bobe_gp_t* g, int64_t S, int64_t F, uint64_t seed, const double* u, const double* phase,
+                         const double* w, const double* eps, bobe_paths_t** out) {
+  API_BEGIN
+  NEED(out, "out is NULL");
+  *out = nullptr;
+  NEED(g, "gp is NULL");
+  return paths_create(*g, S, F, seed, u, phase, w, eps, out);
+  API_END
+}
+
+int bobe_gp_paths_get(bobe_paths_t* p, double* u, double* phase, double* w, double* eps) {
+  API_BEGIN
+  NEED(p, "paths is NULL");
+  return paths_get(*p, u, phase, w, eps);
+  API_END
+}
+
+int bobe_gp_paths_eval(bobe_paths_t* p, const double* Xq, int64_t C, int centered, double* f) {
+  API_BEGIN
+  NEED(p && Xq && f, "NULL argument");
+  return paths_eval(*p, Xq, C, centered, f);
+  API_END
+}
+
+int bobe_gp_paths_argmax(bobe_paths_t* p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best) {
+  API_BEGIN
+  NEED(p && Xq && idx && best, "NULL argument");
+  return paths_argmax(*p, Xq, C, bias, idx, best);
+  API_END
+}
+
+void bobe_gp_paths_destroy(bobe_paths_t* p) { paths_destroy(p); }
+
 int bobe_gp_wip_grad(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                      double* wipv, double* wipstd, double* dwipv, double* dwipstd) {
   API_BEGIN

@@ -8,6 +8,8 @@
 //   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
 //   gp_batch.hip      one-sweep batch selection for WIPV / WIPStd (the sweep's intermediates kept, rank-one downdates)
 //   gp_criteria.hip   importance-weighted integration points, IMIQR / EIV: the weighted scoring pass of the sweep and the batch
+//   gp_paths.hip      pathwise posterior draws of the latent surrogate (random Fourier features + Matheron's rule): path
+//                     sets, their evaluation at query points and per-path argmax
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
 // without a HIP device every entry point fails with BOBE_ERR_HIP.
@@ -205,6 +207,7 @@ void configure_sweep_kernels();
 void configure_consumer_kernels();
 void configure_posterior_kernels();
 void configure_loo_kernels();
+void configure_paths_kernels();
 // their guard: true on the first call on the current device only (`done`: the translation unit's own flag per device)
 inline bool first_use_on_device(bool (&done)[64]) {
   int dev = 0;
@@ -339,6 +342,8 @@ struct bobe_gp {
   // substitution, which overwrites B [Np x ldb] and needs V (V may be NULL only for the plain product); qp: the column sums
   // of squares per row tile (k_trimul's epilogue)
   void solve_v(double* B, int64_t ldb, int64_t ncp, double* V, int64_t ldv, double* qp, int64_t ldq);
+  // the backward half, W = L^-T V for ncp (a multiple of 128) columns: the product with the inverse factor's transpose
+  void solve_wt(const double* V, int64_t ldv, int64_t ncp, double* W, int64_t ldw);
   // prepare_z() keeps its results (ZsT, W_Z, base_z) while the same host Z arrives again and nothing they depend on
   // changed: an L-BFGS refinement of one acquisition point calls bobe_gp_wip_grad dozens of times with one Z
   std::vector<double> z_seen;
@@ -541,6 +546,7 @@ struct bobe_gp {
     bobe::configure_consumer_kernels();
     bobe::configure_posterior_kernels();
     bobe::configure_loo_kernels();
+    bobe::configure_paths_kernels();
   }
   void sync() { HIPCHK(hipStreamSynchronize(stream)); }
 
@@ -688,3 +694,14 @@ struct bobe_gp {
   void clone_from(bobe_gp& src);
   void release_all();
 };
+
+// ---- gp_paths.hip: the path set behind bobe_gp_paths_* (a snapshot of its parent's state; it uses the parent's stream, chunk
+// and launch helpers, so it is destroyed first).  The functions throw Err like the members above.
+namespace bobe {
+int paths_create(bobe_gp& g, int64_t S, int64_t F, uint64_t seed, const double* u, const double* phase, const double* w,
+                 const double* eps, bobe_paths** out);
+int paths_get(bobe_paths& p, double* u, double* phase, double* w, double* eps);
+int paths_eval(bobe_paths& p, const double* Xq, int64_t C, int centered, double* f);
+int paths_argmax(bobe_paths& p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best);
+void paths_destroy(bobe_paths* p);
+}  // namespace bobe

@@ -70,6 +70,12 @@ void bobe_gp::solve_v(double* B, int64_t ldb, int64_t ncp, double* V, int64_t ld
   }
 }
 
+void bobe_gp::solve_wt(const double* V, int64_t ldv, int64_t ncp, double* W, int64_t ldw) {
+  hipLaunchKernelGGL(k_trimul_t, dim3((unsigned)(ncp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
+                     (const double*)Linv.d(), Np, nb, V, ldv, W, ldw);
+  LAUNCH_CHECK();
+}
+
 // Z-side quantities of the sweep: ZsT, kXZ, V_Z = Linv kXZ, base_z = kself - |V_Z[:,z]|^2 and - for the score gradients
 // only (need_w) - W_Z = Linv^T V_Z
 void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {

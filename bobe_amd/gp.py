@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import threading
+import weakref
 from typing import List, Optional
 
 import numpy as np
@@ -175,6 +176,7 @@ class GP:
         bounds, a constant)."""
         self._lib = _lib.load()
         self._h = C.c_void_p(0)
+        self._paths = weakref.WeakSet()        # live path sets (sample_paths): closed before the handle they work on
         self.device = int(device)
         self._setup_training_data(train_x, train_y)
         self.param_names = param_names if param_names is not None else ["x_" + str(i) for i in range(self.ndim)]
@@ -227,6 +229,8 @@ class GP:
 
     def __del__(self):
         try:
+            for ps in list(getattr(self, "_paths", ())):
+                ps.close()
             if getattr(self, "_h", None) is not None and self._h.value:
                 self._lib.bobe_gp_destroy(self._h)
                 self._h = C.c_void_p(0)
@@ -772,6 +776,18 @@ class GP:
                    "bobe_gp_posterior_sample")
         out = self.y_std * out if centered else self.y_mean + self.y_std * out
         return (out, jit.value) if return_jitter else out
+
+    def sample_paths(self, n_paths, n_features=2048, seed=0, *, u=None, phase=None, w=None, eps=None):
+        """``n_paths`` pathwise draws of the posterior of the LATENT surrogate (no observation noise added, unlike
+        ``predict_cov`` / ``sample_posterior``) as a ``PosteriorPaths`` set: functions f_s(x) = phi(x)^T w_s + k(x, X) K^-1 (y -
+        Phi(X) w_s - eps_s) with ``n_features`` random Fourier features (Matheron's rule; include/bobe_gp.h,
+        bobe_gp_paths_create).  Creating the set costs a few passes through the factor; evaluating it is linear in the number
+        of points and has no cap.  ``u`` (F, d), ``phase`` (F,), ``w`` (S, F), ``eps`` (S, N): the caller's arrays (NumPy or
+        torch CUDA tensors) instead of the device's draws from ``seed`` (the same seed gives the same paths).  The set is a
+        snapshot: later ``update`` / ``fit`` calls do not change it.  Not gated: on a ``GPwithClassifier`` these are the plain
+        GP's paths.  Raises ``BobeLibraryError`` on a state that is not positive definite."""
+        from .paths import PosteriorPaths
+        return PosteriorPaths(self, n_paths, n_features, seed, u=u, phase=phase, w=w, eps=eps)
 
     # ------------------------------------------------------------------ update
     def update(self, new_x, new_y):

@@ -76,7 +76,8 @@ def _draw_in_ellipsoid(mu, A, n, rng):
 
 
 def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float, *, n_draws: int = 0,
-                      draws_seed: int = 0, draws_max_points: int = 16384) -> Dict:
+                      draws_seed: int = 0, draws_max_points: int = 16384, draws_method: str = "joint",
+                      draws_features: int = 2048, draws_arrays: Optional[Dict] = None) -> Dict:
     """The logZ dictionary of a finished run (samplers.py:172-183): the GP's predictive variance at every sample —
     ONE batched ``bobe_gp_predict`` call instead of the reference's ``lax.map`` over points — turns into
     logl +- std for the upper / lower evidence integrals and into the variance estimate of logZ.
@@ -84,7 +85,15 @@ def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float,
     ``upper`` / ``lower`` treat the GP's errors at the samples as perfectly correlated, ``var`` / ``std`` as independent.
     ``n_draws > 0`` adds the distribution the GP itself implies (``_logz_draws``): ``draws`` (logZ of ``n_draws`` joint
     posterior draws of the surrogate at the samples), ``draws_mean``, ``draws_std``, ``draws_points``, ``draws_jitter``.
-    The other keys do not depend on it, and the run's generator is not used."""
+    The other keys do not depend on it, and the run's generator is not used.
+
+    ``draws_method``: 'joint' (default) perturbs the ``draws_max_points`` heaviest samples by a draw from their dense joint
+    covariance (``GP.sample_posterior``, at most 16384 points); 'paths' perturbs EVERY sample with a finite, ungated logl by a
+    centred pathwise draw of the surrogate (``GP.sample_paths`` with ``draws_features`` random Fourier features, cost linear
+    in the number of samples, no cap) and reports ``draws_features`` in the place of ``draws_jitter``.  ``draws_arrays``
+    ('paths' only): the caller's ``u`` / ``phase`` / ``w`` / ``eps`` for ``GP.sample_paths`` instead of the seeded ones."""
+    if draws_method not in ("joint", "paths"):
+        raise ValueError(f"draws_method must be 'joint' or 'paths', not {draws_method!r}")
     logl = np.asarray(logl, dtype=np.float64)
     var = np.asarray(gp.predict_var_batched(samples_x), dtype=np.float64)
     std = np.sqrt(var)
@@ -95,7 +104,10 @@ def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float,
     var_logz = math.exp(float(np.clip(log_var_delta - 2 * mean, -100, 100)))
     out = {"mean": float(mean), "dlogz_sampler": float(logz_err), "upper": float(upper[-1]), "lower": float(lower[-1]),
            "var": var_logz, "std": 2 * math.sqrt(var_logz)}
-    if n_draws > 0:
+    if n_draws > 0 and draws_method == "paths":
+        out.update(_logz_draws_paths(gp, samples_x, logl, logvol, int(n_draws), int(draws_seed), int(draws_features),
+                                     draws_arrays))
+    elif n_draws > 0:
         out.update(_logz_draws(gp, samples_x, logl, logvol, int(n_draws), int(draws_seed), int(draws_max_points)))
     return out
 
@@ -142,6 +154,24 @@ def _logz_draws(gp, samples_x, logl, logvol, n_draws: int, seed: int, max_points
             "draws_points": int(len(idx)), "draws_jitter": float(jitter)}
 
 
+def _logz_draws_paths(gp, samples_x, logl, logvol, n_draws: int, seed: int, n_features: int, arrays: Optional[Dict]) -> Dict:
+    """``_logz_draws`` without the cap: delta_s is path s of ``gp.sample_paths`` minus the posterior mean
+    (``evaluate(..., centered=True)``) at EVERY sample ``draws_points`` leaves free; gated and non-finite samples stay fixed."""
+    logl = np.asarray(logl, dtype=np.float64)
+    idx = draws_points(gp, logl, logvol, max_points=len(logl))
+    delta = np.zeros((n_draws, 0))
+    if len(idx):
+        with gp.sample_paths(n_draws, n_features, seed=seed, **(arrays or {})) as paths:
+            delta = paths.evaluate(np.asarray(samples_x)[idx], centered=True)
+    draws = np.empty(n_draws)
+    for s in range(n_draws):
+        ls = logl.copy()
+        ls[idx] += delta[s]
+        draws[s] = compute_integrals(logl=ls, logvol=logvol)[-1]
+    return {"draws": draws, "draws_mean": float(np.mean(draws)), "draws_std": float(np.std(draws)),
+            "draws_points": int(len(idx)), "draws_features": int(n_features)}
+
+
 def _rwalk_pool(loglike, live, live_logl, worst, lstar, rng, n_walkers, walks, scale, gp=None):
     """Replacement candidates by constrained random walks, the proposal dynesty's 'rwalk' uses (the reference's choice,
     samplers.py:64, 152) — run as ONE batch: ``n_walkers`` walkers start from random live points and take ``walks``
@@ -182,7 +212,8 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
                     maxcall: int = int(5e6), equal_weights: bool = False, rng=None, batch: int = 8192,
                     enlarge: float = 1.25, nlive: Optional[int] = None, sample_method: str = "auto",
                     walks: Optional[int] = None, device_walks: bool = True, logz_draws: int = 0,
-                    logz_draws_seed: int = 0, *, keep_weights: bool = False) -> Tuple[Dict, Dict, bool]:
+                    logz_draws_seed: int = 0, *, keep_weights: bool = False,
+                    logz_draws_method: str = "joint") -> Tuple[Dict, Dict, bool]:
     """Static nested sampling of exp(GP mean) over the unit cube -> (samples_dict, logz_dict, success).
 
     Settings follow ``nested_sampling_Dy`` (samplers.py:119-126): mode 'acq' uses nlive = max(100, min(500, 20 d))
@@ -193,7 +224,10 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     surrogate offers ``rwalk`` (``bobe_gp_rwalk``); False steps them from the host, one batched prediction per step.
     ``logz_draws`` > 0: the logZ dictionary also holds the evidence of that many joint posterior draws of the surrogate
     (``logz_from_samples``, seeded by ``logz_draws_seed``); reported only, nothing else depends on them.
-    ``keep_weights``: mode 'acq' returns the weighted samples as they are instead of resampling them to equal weights."""
+    ``keep_weights``: mode 'acq' returns the weighted samples as they are instead of resampling them to equal weights.
+    ``logz_draws_method``: 'joint' (default) or 'paths' - how those draws are made (``logz_from_samples``, ``draws_method``)."""
+    if logz_draws_method not in ("joint", "paths"):
+        raise ValueError(f"logz_draws_method must be 'joint' or 'paths', not {logz_draws_method!r}")
     rng = rng if rng is not None else get_numpy_rng()
     ndim = ndim if ndim is not None else gp.ndim
     if mode == "acq":
@@ -212,8 +246,8 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
         nan = float("nan")
         logz_nan = {"mean": nan, "dlogz_sampler": nan, "upper": nan, "lower": nan, "var": nan, "std": nan}
         if logz_draws > 0:
-            logz_nan.update(draws=np.full(int(logz_draws), nan), draws_mean=nan, draws_std=nan, draws_points=0,
-                            draws_jitter=nan)
+            logz_nan.update(draws=np.full(int(logz_draws), nan), draws_mean=nan, draws_std=nan, draws_points=0)
+            logz_nan.update({"draws_features": 0} if logz_draws_method == "paths" else {"draws_jitter": nan})
         return ({"x": live, "weights": np.ones(nlive), "logl": live_logl, "best": live[0], "method": "nested"},
                 logz_nan, False)
     use_rwalk = sample_method == "rwalk" or (sample_method == "auto" and ndim > 4)
@@ -332,7 +366,7 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     success = bool(~np.all(logl == logl[0])) and not gave_up
 
     logz_dict = logz_from_samples(gp, samples_x, logl, logvol, mean, logz_err, n_draws=logz_draws,
-                                  draws_seed=logz_draws_seed)
+                                  draws_seed=logz_draws_seed, draws_method=logz_draws_method)
     logz_dict.update(ncall=int(ncall), niter=int(niter), truncated=bool(truncated))
     best_pt = samples_x[int(np.argmax(logl))]
     weights = renormalise_log_weights(logwt)
@@ -354,15 +388,15 @@ def prior_transform(x):
 def nested_sampling_Dy(gp, mode: str = "acq", ndim: int = 1, dlogz: float = 0.1, dynamic: bool = False,
                        maxcall: Optional[int] = int(5e6), print_progress: Optional[bool] = True,
                        equal_weights: bool = False, sample_method: str = "rwalk", rng=None, *, logz_draws: int = 0,
-                       logz_draws_seed: int = 0):
+                       logz_draws_seed: int = 0, logz_draws_method: str = "joint"):
     """The reference's entry point name and keywords (samplers.py:55-65) on ``nested_sampling`` above; ``dynamic``,
     ``print_progress`` are dynesty options without a counterpart here; ``sample_method='rwalk'`` (the reference's
     default) maps to 'auto': exact ellipsoid draws in up to 4 dimensions, batched random walks above.  ``logz_draws``,
-    ``logz_draws_seed``: see ``nested_sampling``."""
+    ``logz_draws_seed``, ``logz_draws_method``: see ``nested_sampling``."""
     return nested_sampling(gp, ndim=ndim if ndim and ndim > 1 else gp.ndim, mode=mode, dlogz=dlogz,
                            maxcall=maxcall if maxcall is not None else int(5e6), equal_weights=equal_weights, rng=rng,
                            sample_method="auto" if sample_method == "rwalk" else sample_method, logz_draws=logz_draws,
-                           logz_draws_seed=logz_draws_seed)
+                           logz_draws_seed=logz_draws_seed, logz_draws_method=logz_draws_method)
 
 
 def get_hmc_settings(ndim, warmup_steps=None, num_samples=None, thinning=None):

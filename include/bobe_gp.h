@@ -279,6 +279,34 @@ int bobe_gp_predict_cov(bobe_gp_t* gp, const double* Xq, int64_t C, double* cov)
 int bobe_gp_posterior_sample(bobe_gp_t* gp, const double* Xq, int64_t C, int64_t S, uint64_t seed, const double* z,
                              int centered, double* draws, double* jitter_out);
 
+/* PATHWISE posterior draws of the LATENT surrogate f (no observation noise added: bobe_gp_predict_cov / _posterior_sample above
+ * describe f + noise; here noise enters only through the conditioning).  A path is a function that can be evaluated anywhere,
+ * Matheron's rule with the prior drawn through F random Fourier features (the reference has no counterpart):
+ *   f_s(x) = phi(x)^T w_s + k(x, X) v_s,   v_s = K^-1 (y - Phi(X) w_s - eps_s),
+ *   phi_j(x) = sqrt(2 kvar / F) cos(u_j . (x / ls) + b_j),   w ~ N(0, 1),   eps ~ N(0, noise),   b_j ~ U[0, 2 pi),
+ *   u_j ~ N(0, I_d) (RBF) or g_j sqrt(5 / c_j), g_j ~ N(0, I_d), c_j ~ chi^2_5 (Matern-5/2: Student-t with 5 degrees of freedom).
+ * Standardised units.  Creating S paths costs a few multi-right-hand-side passes through the factor the handle holds;
+ * evaluating them at C points is linear in C and has no cap on C.
+ *   create: S >= 1 paths, 1 <= F <= 65536 features.  u (F x d), phase (F), w (S x F), eps (S x N): the caller's arrays (host
+ *     or device) or NULL = drawn on the device from `seed` with the counter hash of bobe_gp_posterior_sample, one sub-stream
+ *     per array (the exact layout is above k_paths_draw_normals in paths_kernels.hpp); the same seed gives the same bits.
+ *     The set is a SNAPSHOT of the factorised state: later set_data / set_hyper / factor / append calls on gp do not change
+ *     it.  It must be destroyed BEFORE gp (it works on gp's stream and honours bobe_gp_set_chunk).
+ *     BOBE_ERR_STATE without a factorised state, BOBE_ERR_ARG for bad sizes or a NULL out, BOBE_NOT_PD for a NaN state
+ *     (*out = NULL, nothing allocated).
+ *   get: copies of the four arrays as the set holds them (any pointer may be NULL).
+ *   eval: f[s][c] = f_s(Xq_c) (S x C, row-major); centered != 0: f_s - posterior mean (bobe_gp_predict's mean).
+ *   argmax: idx[s] = argmax_c f_s(Xq_c) + bias[s][c] and best[s] = that maximum, without forming the S x C matrix; bias (S x C)
+ *     may be NULL; ties go to the lower index.
+ * NOT gated (like bobe_gp_predict_cov).  eval / argmax: BOBE_ERR_ARG for C < 1 or a NULL pointer. */
+typedef struct bobe_paths bobe_paths_t;
+int bobe_gp_paths_create(bobe_gp_t* gp, int64_t S, int64_t F, uint64_t seed, const double* u, const double* phase,
+                         const double* w, const double* eps, bobe_paths_t** out);
+int bobe_gp_paths_get(bobe_paths_t* p, double* u, double* phase, double* w, double* eps);
+int bobe_gp_paths_eval(bobe_paths_t* p, const double* Xq, int64_t C, int centered, double* f);
+int bobe_gp_paths_argmax(bobe_paths_t* p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best);
+void bobe_gp_paths_destroy(bobe_paths_t* p);
+
 /* EI.fun / LogEI.fun (acquisition.py:226-253, 318-330) for C points: out[c] = +EI (mode 0) or
  * +log EI (mode 1); best_y, zeta in standardised units. */
 int bobe_gp_acq_ei(bobe_gp_t* gp, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);
