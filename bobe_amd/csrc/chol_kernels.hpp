@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void k_potf2(double* __restrict__ A, int64_t l
   potf2_body<FACTOR>(A + slot * bsA, lda, Linv + slot * bsL, ldl, blk, info + slot, nvalid);
 }
 
-// ---- inverse of every diagonal 128x128 block (grid = nb) --------------------------------------------
+// ---- inverse of the diagonal 128x128 blocks blk0 .. blk0 + grid - 1 (grid = nb: all of them) --------
 // in: L[blk][blk] (lower) and the 16x16 diagonal inverses left in Linv[blk][blk] by k_potf2.
 // out: Linv[blk][blk] = L[blk][blk]^-1 (lower, zeros above).
 // diag / first_aside: the factorisation left the L_kk of blocks >= first_aside in its scratch blocks (k_chol_panel); they
@@ -449,9 +449,9 @@ __device__ __forceinline__ void trti_block(double* S, double* __restrict__ Ib, i
 __global__ __launch_bounds__(256) void k_trti_diag(double* __restrict__ L, int64_t lda,
                                                    double* __restrict__ Linv, int64_t ldl, int64_t bsA = 0,
                                                    int64_t bsL = 0, const double* __restrict__ diag = nullptr,
-                                                   int64_t bsD = 0, int first_aside = 1 << 30) {
+                                                   int64_t bsD = 0, int first_aside = 1 << 30, int blk0 = 0) {
   extern __shared__ double S[];
-  const int blk = blockIdx.x;
+  const int blk = blk0 + blockIdx.x;
   L += blockIdx.y * bsA;
   Linv += blockIdx.y * bsL;
   double* Lb = L + ((int64_t)blk * TILE) * lda + (int64_t)blk * TILE;

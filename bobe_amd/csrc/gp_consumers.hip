@@ -472,5 +472,11 @@ void bobe_gp::release_all() {
     kv.second.d_colk0.release();
   }
   if (ev_batch) (void)hipEventDestroy(ev_batch);
+  if (side_stream) {
+    (void)hipStreamSynchronize(side_stream);
+    (void)hipStreamDestroy(side_stream);
+  }
+  if (ev_fork) (void)hipEventDestroy(ev_fork);
+  if (ev_join) (void)hipEventDestroy(ev_join);
   if (own_stream && stream) (void)hipStreamDestroy(stream);
 }

@@ -47,7 +47,7 @@ void configure_factor_kernels() {
 
 const Tuning& tuning() {
   static Tuning t = [] {
-    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, false, false, true, true, true};
+    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, 1, false, false, true, true, true};
     auto geti = [](const char* name, int& dst) {
       const char* e = std::getenv(name);
       if (e) dst = std::atoi(e);
@@ -61,6 +61,7 @@ const Tuning& tuning() {
     geti("BOBE_GRAPH_MAX_N", v.graph_max_n);
     geti("BOBE_XCD_SHARES", v.xcd_shares);
     geti("BOBE_FILL", v.fill);
+    geti("BOBE_INV_SIDE", v.inv_side);
     v.trace = std::getenv("BOBE_TRACE") != nullptr;
     int reuse = 1;
     geti("BOBE_FACTOR_REUSE", reuse);
@@ -124,35 +125,14 @@ double default_pivot_floor_ulp() {
 }  // namespace bobe
 
 void bobe_gp::build_probs() {
-  struct Item { int depth, lo, mid, hi; };
-  std::vector<Item> items;
-  struct Rec {
-    static void go(std::vector<Item>& it, int depth, int lo, int hi) {
-      if (hi - lo <= 1) return;
-      const int mid = lo + (hi - lo) / 2;
-      it.push_back({depth, lo, mid, hi});
-      go(it, depth + 1, lo, mid);
-      go(it, depth + 1, mid, hi);
-    }
-  };
-  Rec::go(items, 0, 0, nb);
-  int maxd = -1;
-  for (auto& i : items) maxd = i.depth > maxd ? i.depth : maxd;
-  std::vector<TriProb> flat;
-  depths.clear();
-  for (int dd = 0; dd <= maxd; ++dd) {
-    Depth D{(int)flat.size(), 0, 0};
-    for (auto& i : items)
-      if (i.depth == dd) {
-        flat.push_back({i.lo, i.mid, i.hi, D.nblocks});
-        D.nblocks += (i.hi - i.mid) * (i.mid - i.lo);
-        D.count++;
-      }
-    depths.push_back(D);
-  }
-  if (!flat.empty()) {
-    probs.ensure(flat.size() * sizeof(TriProb));
-    HIPCHK(hipMemcpy(probs.p, flat.data(), flat.size() * sizeof(TriProb), hipMemcpyHostToDevice));
+  const TriSplit sp = tri_split(nb);
+  depths = sp.depths;
+  lead_depths = sp.lead;
+  trail_depths = sp.trail;
+  tri_mid = sp.mid;
+  if (!sp.table.empty()) {
+    probs.ensure(sp.table.size() * sizeof(TriProb));
+    HIPCHK(hipMemcpy(probs.p, sp.table.data(), sp.table.size() * sizeof(TriProb), hipMemcpyHostToDevice));
   }
 }
 
@@ -465,7 +445,8 @@ void bobe_gp::build_plans() {
 // The panel launches leave most of the chip empty (one 150 KB workgroup per 48 / 64 rows): where that pays (fill_pays),
 // updates of block columns that are not needed soon are DEFERRED and ride in those launches as filler workgroups
 // (chol_plan, k_chol_panel<true, .>).  Every matrix element sees the same operation sequence in all forms (same bits).
-void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, int64_t bsL, double* dg, bool defer_diag) {
+void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, int64_t bsL, double* dg, bool defer_diag,
+                    const std::function<void(int)>* at_fork, int fork_panel) {
   if (!dg) dg = diag.d();                                     // scratch for the L_kk of the panel launches
   const int64_t bsD = (int64_t)nb * TILE * TILE;
   int first_aside = nb;                                       // first step whose L_kk was left in the scratch blocks
@@ -508,6 +489,7 @@ void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, 
           prof_end(BOBE_PROF_TRSM);
         }
       }
+      if (at_fork && kk == fork_panel) (*at_fork)(first_aside);
     } else {
       prof_begin(BOBE_PROF_SYRK);
       if (op.uniform) {
@@ -538,49 +520,76 @@ void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, 
   LAUNCH_CHECK();
 }
 
-// Linv = L^-1: diagonal 128-blocks in one batched launch, then recursive doubling (two GEMM launches per level)
-void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, int64_t bsL, int64_t bsT) {
+// One level of the recursive doubling (or the leading / trailing part of one): the problems of `part`, k_trtri_T and / or
+// k_trtri_R.  level_blocks: the 128-blocks of the WHOLE level, which pick the tile size - a part of a level takes the tiles
+// the level would (the bits do not depend on them; a timing comparison should not mix two changes).
+void bobe_gp::trtri_level(const TriArgs& t, const Depth& part, int level_blocks, bool do_t, bool do_r) {
   const Tuning& tu = tuning();
-  prof_begin(BOBE_PROF_TRTRI);
-  hipLaunchKernelGGL(k_trti_diag, dim3(nb, B), dim3(256), POTF2_SMEM_BYTES, stream, a, Np, linv, Np, bsA, bsL, cur->aside_dg,
-                     (int64_t)nb * TILE * TILE, cur->aside_first);
-  cur->aside_first = 1 << 30;
-  cur->aside_dg = nullptr;
-  prof_end(BOBE_PROF_TRTRI);
+  const TriProb* pr = static_cast<const TriProb*>(probs.p) + part.first;
+  // (64x64 tiles while a level of ONE matrix has too few 128x128 tiles to fill the chip; a tile's K order is the
+  // same either way.  Batches keep the per-matrix choice: four in lock step at N = 4096 take 7.0 ms per evaluation
+  // round with 64x64 tiles at every level against 7.4 with 128x128 tiles at the top level)
+  if (t.B * 2 * level_blocks <= std::max(num_cus, 1)) {
+    // A level with fewer 64 x 64 tile pairs than CUs (N <= 1024 in a batch of four, the deep levels of larger
+    // matrices): 32 x 32 tiles - four times the workgroups, a quarter of the work each.  Such a launch lasts as long as
+    // ONE workgroup's K loop, and a wave issues a 16 x 16 x 4 fp64 MFMA every 64 cycles at best: a quarter of the MFMAs
+    // per wave and K-step is a shorter launch.  Tile shape does not change an element's accumulation order (same bits).
+    const TileGrid tg = tile_grid(8 * part.nblocks);
+    if (do_t)
+      hipLaunchKernelGGL(k_trtri_T<32>, dim3(tg.grid, t.B), dim3(256), GEMM32_SMEM_BYTES, stream, t.a, Np,
+                         (const double*)t.linv, Np, t.tmp, Np, pr, part.count, t.bsA, t.bsL, t.bsT, tg.per);
+    if (do_r)
+      hipLaunchKernelGGL(k_trtri_R<32>, dim3(tg.grid, t.B), dim3(256), GEMM32_SMEM_BYTES, stream, t.linv, Np,
+                         (const double*)t.tmp, Np, pr, part.count, t.bsL, t.bsT, tg.per);
+  } else if (level_blocks < tu.trtri64_below) {
+    const TileGrid tg = tile_grid(2 * part.nblocks);             // (tile pairs of complementary K: equal work)
+    const auto kT = tu.gemm64_glds ? k_trtri_T<64, true> : k_trtri_T<64, false>;
+    const auto kR = tu.gemm64_glds ? k_trtri_R<64, true> : k_trtri_R<64, false>;
+    if (do_t)
+      hipLaunchKernelGGL(kT, dim3(tg.grid, t.B), dim3(256), GEMM64_SMEM_BYTES, stream, t.a, Np, (const double*)t.linv, Np,
+                         t.tmp, Np, pr, part.count, t.bsA, t.bsL, t.bsT, tg.per);
+    if (do_r)
+      hipLaunchKernelGGL(kR, dim3(tg.grid, t.B), dim3(256), GEMM64_SMEM_BYTES, stream, t.linv, Np, (const double*)t.tmp, Np,
+                         pr, part.count, t.bsL, t.bsT, tg.per);
+  } else {
+    if (do_t)
+      hipLaunchKernelGGL(k_trtri_T<128>, dim3(part.nblocks, t.B), dim3(256), GEMM_SMEM_BYTES, stream, t.a, Np,
+                         (const double*)t.linv, Np, t.tmp, Np, pr, part.count, t.bsA, t.bsL, t.bsT);
+    if (do_r)
+      hipLaunchKernelGGL(k_trtri_R<128>, dim3(part.nblocks, t.B), dim3(256), GEMM_SMEM_BYTES, stream, t.linv, Np,
+                         (const double*)t.tmp, Np, pr, part.count, t.bsL, t.bsT);
+  }
+}
+
+// Linv = L^-1, or one part of it, on `stream`: the diagonal 128-blocks of the part in one batched launch, then recursive
+// doubling (two GEMM launches per level).  TRI_LEAD ends with the top problem's T, TRI_TOP_R is its R alone.
+void bobe_gp::trtri_part(TriPart part, const TriArgs& t, const double* dg, int first_aside) {
+  const int b0 = part == TRI_TRAIL ? tri_mid : 0, b1 = part == TRI_LEAD ? tri_mid : nb;
+  if (part != TRI_TOP_R) {
+    prof_begin(BOBE_PROF_TRTRI);
+    hipLaunchKernelGGL(k_trti_diag, dim3(b1 - b0, t.B), dim3(256), POTF2_SMEM_BYTES, stream, t.a, Np, t.linv, Np, t.bsA, t.bsL,
+                       dg, (int64_t)nb * TILE * TILE, first_aside, b0);
+    prof_end(BOBE_PROF_TRTRI);
+  }
   for (int dd = (int)depths.size() - 1; dd >= 0; --dd) {
     const Depth& D = depths[dd];
-    const TriProb* pr = static_cast<const TriProb*>(probs.p) + D.first;
-    prof_begin(BOBE_PROF_TRTRI);
-    // (64x64 tiles while a level of ONE matrix has too few 128x128 tiles to fill the chip; a tile's K order is the
-    // same either way.  Batches keep the per-matrix choice: four in lock step at N = 4096 take 7.0 ms per evaluation
-    // round with 64x64 tiles at every level against 7.4 with 128x128 tiles at the top level)
-    if (B * 2 * D.nblocks <= std::max(num_cus, 1)) {
-      // A level with fewer 64 x 64 tile pairs than CUs (N <= 1024 in a batch of four, the deep levels of larger
-      // matrices): 32 x 32 tiles - four times the workgroups, a quarter of the work each.  Such a launch lasts as long as
-      // ONE workgroup's K loop, and a wave issues a 16 x 16 x 4 fp64 MFMA every 64 cycles at best: a quarter of the MFMAs
-      // per wave and K-step is a shorter launch.  Tile shape does not change an element's accumulation order (same bits).
-      const TileGrid tg = tile_grid(8 * D.nblocks);
-      hipLaunchKernelGGL(k_trtri_T<32>, dim3(tg.grid, B), dim3(256), GEMM32_SMEM_BYTES, stream, a, Np,
-                         (const double*)linv, Np, tmp, Np, pr, D.count, bsA, bsL, bsT, tg.per);
-      hipLaunchKernelGGL(k_trtri_R<32>, dim3(tg.grid, B), dim3(256), GEMM32_SMEM_BYTES, stream, linv, Np,
-                         (const double*)tmp, Np, pr, D.count, bsL, bsT, tg.per);
-    } else if (D.nblocks < tu.trtri64_below) {
-      const TileGrid tg = tile_grid(2 * D.nblocks);             // (tile pairs of complementary K: equal work)
-      const auto kT = tu.gemm64_glds ? k_trtri_T<64, true> : k_trtri_T<64, false>;
-      const auto kR = tu.gemm64_glds ? k_trtri_R<64, true> : k_trtri_R<64, false>;
-      hipLaunchKernelGGL(kT, dim3(tg.grid, B), dim3(256), GEMM64_SMEM_BYTES, stream, a, Np,
-                         (const double*)linv, Np, tmp, Np, pr, D.count, bsA, bsL, bsT, tg.per);
-      hipLaunchKernelGGL(kR, dim3(tg.grid, B), dim3(256), GEMM64_SMEM_BYTES, stream, linv, Np,
-                         (const double*)tmp, Np, pr, D.count, bsL, bsT, tg.per);
-    } else {
-      hipLaunchKernelGGL(k_trtri_T<128>, dim3(D.nblocks, B), dim3(256), GEMM_SMEM_BYTES, stream, a, Np,
-                         (const double*)linv, Np, tmp, Np, pr, D.count, bsA, bsL, bsT);
-      hipLaunchKernelGGL(k_trtri_R<128>, dim3(D.nblocks, B), dim3(256), GEMM_SMEM_BYTES, stream, linv, Np,
-                         (const double*)tmp, Np, pr, D.count, bsL, bsT);
+    if (part != TRI_ALL && dd > 0) {
+      const Depth& P = part == TRI_LEAD ? lead_depths[dd] : trail_depths[dd];
+      if (part != TRI_TOP_R && P.count > 0) trtri_level(t, P, D.nblocks, true, true);
+      continue;
     }
+    if (part == TRI_TRAIL) continue;
+    prof_begin(BOBE_PROF_TRTRI);
+    trtri_level(t, D, D.nblocks, part != TRI_TOP_R, part != TRI_LEAD);
     prof_end(BOBE_PROF_TRTRI);
   }
   LAUNCH_CHECK();
+}
+
+void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, int64_t bsL, int64_t bsT) {
+  trtri_part(TRI_ALL, {a, linv, tmp, B, bsA, bsL, bsT}, cur->aside_dg, cur->aside_first);
+  cur->aside_first = 1 << 30;
+  cur->aside_dg = nullptr;
 }
 
 // K^-1 tiles fused with the gradient partial sums (optionally stores K^-1's lower tiles); returns #partials.
@@ -625,9 +634,92 @@ void bobe_gp::solve_alpha(const double* linv, double* wv, double* al, double* pr
   LAUNCH_CHECK();
 }
 
+// Where the inverse's leading half goes to the side stream (chol_solve).  Measured on 256 CUs, one evaluation round
+// (value + gradient) forked / unforked (profiles/inverse_side_stream_ab.txt):
+//            B = 1    B = 4    B = 8
+//   N = 2048  0.993    0.964    0.973        (nb = 16)
+//       3072  0.935    0.939    0.957        (nb = 24)
+//       4096  0.980    0.947    0.989        (nb = 32)
+//       6144  0.926    0.962    0.986        (nb = 48)
+//       8192  0.950    1.004    1.020        (nb = 64)
+// The window it fills - panels mid .. nb-1 and their updates - grows with the chain (nb launches) and its updates; the work
+// it moves, the leading half's inverse and the top level's T, grows as B * nb^3 and runs on three quarters of the chip
+// (ensure_side).  Beyond B * nb^3 ~ 900 000 (between 8 x 48^3 and 4 x 64^3) the side stream outlasts the window and the
+// top level's R waits for it: unforked there.  Below 16 block columns nothing was measured: unforked (an evaluation of a
+// few hundred microseconds has no window worth a cross-stream hop of ~15 us).  Never on an evaluation slot's private stream
+// (the other slots' kernels want those CUs), never under graph capture (a captured pipeline keeps one stream), never while
+// the inverse's launches are timed as a class (prof_begin / prof_end bracket launches on one stream).  BOBE_INV_SIDE=2
+// forces the fork wherever there are two block columns, BOBE_INV_SIDE=0 turns it off.
+bool bobe_gp::inv_side_pays(int B) const {
+  const int f = tuning().inv_side;
+  if (f == 0 || nb < 2 || on_slot() || capturing || prof_tag == BOBE_PROF_TRTRI) return false;
+  if (f == 2) return true;
+  return nb >= 16 && (int64_t)B * nb * nb * nb <= 900000;
+}
+
+// The side stream and its two events, on first use.  Placement (profiles/inverse_side_stream_ab.txt): a plain or a
+// low-priority stream gains 1-2 % per round and never loses, but its 36 KB GEMM workgroups keep refilling every CU and the
+// 150 KB panel workgroups of the chain wait for a whole one; a stream confined to three quarters of the CUs
+// (hipExtStreamCreateWithCUMask, the first 3/4 of the mask's bits) leaves the chain CUs of its own and gains 2-7 %; half the
+// CUs is too few (the join waits), 7/8 gains less at N = 4096.  Without the entry point: a plain stream.
+void bobe_gp::ensure_side() {
+  if (side_stream) return;
+  if (!ev_fork) HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+  if (!ev_join) HIPCHK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+  const int words = (num_cus + 31) / 32;
+  std::vector<uint32_t> mask(words, 0u);
+  for (int c = 0; c < 3 * num_cus / 4; ++c) mask[c / 32] |= (1u << (c % 32));
+  hipStream_t st = nullptr;
+  if (num_cus < 4 || hipExtStreamCreateWithCUMask(&st, (uint32_t)words, mask.data()) != hipSuccess) {
+    (void)hipGetLastError();
+    st = nullptr;
+  }
+  if (!st) HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  side_stream = st;
+}
+
+// potrf, the inverse, w / alpha.  Where it pays (inv_side_pays) the inverse's leading half leaves the critical path: potrf
+// calls back after panel mid - 1, the hook forks the side stream off there and queues TRI_LEAD on it; the handle's stream
+// finishes the factorisation, inverts the trailing half, waits for the side stream and closes with the top level's R.  The
+// same launches on the same data in an order every element's dependencies allow: the same bits.
 void bobe_gp::chol_solve(const FactorBufs& f, int B, const double* rhs) {
-  potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag, true);
-  trtri(f.a, f.linv, f.tmp, B, f.mat, f.mat, f.mat);
+  const TriArgs t{f.a, f.linv, f.tmp, B, f.mat, f.mat, f.mat};
+  if (inv_side_pays(B)) {
+    ensure_side();
+    struct Join {                         // no exception leaves with the side stream still working on the caller's buffers
+      bobe_gp& g;
+      bool forked = false, joined = false;
+      ~Join() {
+        if (forked && !joined) (void)hipStreamSynchronize(g.side_stream);
+      }
+    } join{*this};
+    const std::function<void(int)> fork = [&](int first_aside) {
+      HIPCHK(hipEventRecord(ev_fork, stream));
+      HIPCHK(hipStreamWaitEvent(side_stream, ev_fork, 0));
+      join.forked = true;
+      {
+        struct OnSide {
+          bobe_gp& g;
+          const hipStream_t main;
+          ~OnSide() { g.stream = main; }
+        } on_side{*this, stream};
+        stream = side_stream;
+        trtri_part(TRI_LEAD, t, f.diag, first_aside);
+      }
+      HIPCHK(hipEventRecord(ev_join, side_stream));
+    };
+    potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag, true, &fork, tri_mid - 1);
+    if (!join.forked) throw Err(BOBE_ERR_STATE, "internal error: the factorisation has no panel to fork the inverse after");
+    trtri_part(TRI_TRAIL, t, cur->aside_dg, cur->aside_first);
+    cur->aside_first = 1 << 30;
+    cur->aside_dg = nullptr;
+    HIPCHK(hipStreamWaitEvent(stream, ev_join, 0));
+    join.joined = true;
+    trtri_part(TRI_TOP_R, t, nullptr, 0);
+  } else {
+    potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag, true);
+    trtri(f.a, f.linv, f.tmp, B, f.mat, f.mat, f.mat);
+  }
   solve_alpha(f.linv, f.w, f.alpha, f.part, B, f.mat, f.vec, f.prt, rhs, 0);
 }
 
@@ -740,13 +832,16 @@ void bobe_gp::eval_replay(EvalWs& ws, const Hyper* hs, bool want_grad) {
     }
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    capturing = true;
     try {
       eval_enqueue(ws, 1, hs, want_grad, static_cast<const Hyper*>(ws.hyp.p));
     } catch (...) {
+      capturing = false;
       (void)hipStreamEndCapture(stream, &graph);
       if (graph) (void)hipGraphDestroy(graph);
       throw;
     }
+    capturing = false;
     HIPCHK(hipStreamEndCapture(stream, &graph));
     const hipError_t ie = hipGraphInstantiate(&eg.exec[w], graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);

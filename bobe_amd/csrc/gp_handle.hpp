@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -128,6 +129,8 @@ void allow_big_lds(K kernel, int bytes) {
 //   BOBE_GRAPH_MAX_N    a slot replays its pipeline as a hipGraph up to this many points (2048)
 //   BOBE_XCD_SHARES     0: row-major tile order on every XCD (1)
 //   BOBE_FILL           deferred trailing updates in the panel launches: 0 off, 1 where they pay (potrf), 2 everywhere
+//   BOBE_INV_SIDE       the inverse's leading half on a side stream beside the late panel chain: 0 off, 1 where it pays
+//                       (inv_side_pays), 2 wherever there are two block columns or more
 //   BOBE_TRACE          print launch plans and batch timings to stderr
 //   BOBE_FACTOR_REUSE   0: bobe_gp_factor always factorises, never adopts an evaluation's factor (1; for A/B runs)
 //   BOBE_GEMM_GLDS      0: the sweep's 128-tile GEMMs (k_trimul, k_cross_vv<128>) take the register-staged tile core
@@ -135,7 +138,7 @@ void allow_big_lds(K kernel, int bytes) {
 //   BOBE_GEMM64_GLDS    0: the 64-tile GEMMs (k_syrk_trail<64, 16>, k_trtri_T/R<64>, k_lauum_grad<., ., 64>, k_cross_vv<64>,
 //                       k_trimul_v64, k_trimul_t64, k_loo_grad<., ., 64>) likewise (1; A/B)
 struct Tuning {
-  int syrk32_below, trtri64_below, pair_min, lockstep_min_n, mll_slots, graph_max_n, xcd_shares, fill;
+  int syrk32_below, trtri64_below, pair_min, lockstep_min_n, mll_slots, graph_max_n, xcd_shares, fill, inv_side;
   bool mll_slots_set, trace, factor_reuse, gemm_glds, gemm64_glds;
 };
 const Tuning& tuning();
@@ -215,8 +218,6 @@ inline bool first_use_on_device(bool (&done)[64]) {
   if (dev < 0 || dev >= 64 || done[dev]) return false;
   return done[dev] = true;
 }
-
-struct Depth { int first, count, nblocks; };
 
 // Retention buffers of a sweep (SweepReq::keep; bobe_gp_wip_select_batch, gp_batch.hip): the caller's
 // device buffers, all with leading dimension ld = C rounded up to 128, that receive what the sweep otherwise keeps per chunk
@@ -361,7 +362,9 @@ struct bobe_gp {
   DBuf wg_ws;     // workspace of bobe_gp_wip_grad's few-candidates path
   DBuf in_stage, z_stage, CsT, ZsT, kXC, kXZ, VZ, WZ, basez, sc, qpart, pv, ps, o_mean, o_var, o_wipv, o_wipstd,
       o_misc, kin_a, kin_b, kout, vxc, vxc2;
-  std::vector<bobe::Depth> depths;
+  // the inverse's problem table (probs) by depth: whole levels, and their leading / trailing parts (tri_split.hpp)
+  std::vector<bobe::Depth> depths, lead_depths, trail_depths;
+  int tri_mid = 0;
   double* h_res = nullptr;  // pinned, 128 doubles
   double* h_in = nullptr;   // pinned, 16 x MAX_D doubles: host coordinates of bobe_gp_wip_grad's few-candidate path
 
@@ -586,9 +589,33 @@ struct bobe_gp {
   void syrk(double* a, int k0, int k1, int first, int colmode, int B = 1, int64_t bsA = 0, const int* colk0 = nullptr,
             int far_col = 0, int ncols = 0);
   // defer_diag: leave the L_kk scratch blocks where they are; the trtri() that follows puts them in place (one launch less)
+  // at_fork / fork_panel: called right after the launch of panel fork_panel, with the first step whose L_kk is in the
+  // scratch blocks so far (nb: none yet) - from there on the factorisation leaves block columns <= fork_panel alone
   void potrf(double* a, double* linv, int* info_dev, int B = 1, int64_t bsA = 0, int64_t bsL = 0, double* dg = nullptr,
-             bool defer_diag = false);
+             bool defer_diag = false, const std::function<void(int)>* at_fork = nullptr, int fork_panel = -1);
+  // The matrices a factorisation / an inverse works on, and the parts of the inverse (tri_split.hpp): TRI_ALL is the whole
+  // of it, TRI_LEAD + TRI_TRAIL + TRI_TOP_R in this order (LEAD and TRAIL in either order, or side by side) the same launches
+  // on the same data.  dg / first_aside: the scratch blocks that still hold the L_kk of steps >= first_aside (potrf).
+  struct TriArgs {
+    double *a, *linv, *tmp;
+    int B;
+    int64_t bsA, bsL, bsT;
+  };
+  enum TriPart { TRI_ALL, TRI_LEAD, TRI_TRAIL, TRI_TOP_R };
+  void trtri_part(TriPart part, const TriArgs& t, const double* dg, int first_aside);
+  void trtri_level(const TriArgs& t, const bobe::Depth& part, int level_blocks, bool do_t, bool do_r);
   void trtri(double* a, double* linv, double* tmp, int B = 1, int64_t bsA = 0, int64_t bsL = 0, int64_t bsT = 0);
+  // ---- the side stream of the inverse's leading half (chol_solve).  With mid = nb / 2, once panel mid - 1 has run the
+  // factorisation only writes A[mid:, mid:], the scratch blocks and 16 x 16 inverses of steps >= mid and the info word:
+  // TRI_LEAD reads L[:, 0:mid) and writes Linv[0:mid, 0:mid) and Tmp[:, 0:mid), so it can run beside panels mid .. nb-1,
+  // which leave most CUs empty.  One fork (ev_fork, recorded by potrf's hook) and one join (ev_join, waited for before
+  // TRI_TOP_R) per factorisation; ordering by events only.  Only on the handle's own stream: never on an evaluation slot,
+  // never under graph capture (`capturing`), never while the inverse's launches are being timed as a class.
+  hipStream_t side_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool capturing = false;
+  bool inv_side_pays(int B) const;
+  void ensure_side();
   int lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
             const Hyper* hdev = nullptr, double* gp_out = nullptr, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
             int64_t bsX = 0, int64_t bsP = 0, double* scratch = nullptr, int64_t bsS = 0, int64_t bsK = 0);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tri_split.hpp"
+
 namespace bobe {
 
 constexpr int MAX_D = 32;
@@ -18,10 +20,7 @@ struct Hyper {
   int kern;  // 0 rbf, 1 matern-5/2
 };
 
-// problem {lo, mid, hi} of the recursive triangular inverse in 128-block units: with inv[lo:mid) and inv[mid:hi) known,
-//   Tm = L[mid:hi, lo:mid) * inv[lo:mid)  (k_trtri_T),   inv[mid:hi, lo:mid) = -inv[mid:hi) * Tm  (k_trtri_R).
-// `off` counts T x T tiles: a problem owns (hi-mid)(mid-lo)(128/T)^2 consecutive blocks.
-struct TriProb { int lo, mid, hi, off; };
+// (TriProb, the problem {lo, mid, hi} of the recursive triangular inverse: tri_split.hpp)
 
 // A filler job of a panel launch (k_chol_panel<true, .>): update tile A[ti][tj] -= sum_k A[ti][k] A[tj][k]^T over the
 // 64-column units [k0, k1) - k_syrk_trail's tile.  The two jobs of a workgroup run the same number of K-steps
