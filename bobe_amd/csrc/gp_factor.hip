@@ -231,13 +231,12 @@ void bobe_gp::kernel_matrix_cross(const double* AT, int64_t lda, int64_t na, int
   LAUNCH_CHECK();
 }
 
-void bobe_gp::assemble_kxx(const Hyper& h, const double* xst, double* a, const Hyper* hdev, int B, int64_t bsX,
-                           int64_t bsA) {
-  const dim3 grid((unsigned)(2 * nb * (nb + 1)), (unsigned)B);   // four workgroups per lower 128x128 tile
+void bobe_gp::assemble_kxx(const Hyper& h, const FactorBufs& f, const Hyper* hdev) {
+  const dim3 grid((unsigned)(2 * nb * (nb + 1)), (unsigned)f.B);   // four workgroups per lower 128x128 tile
   prof_begin(BOBE_PROF_KXX);
   with_kern_dcap(h.kern, h.d, [&](auto KE, auto DC) {
-    launch_kernel_matrix<true>(KE, DC, h.d, grid, stream, xst, Np, N, xst, Np, N, h, a, Np, hdev, bsX, bsA,
-                               (const double*)nullptr, (double*)nullptr, (int64_t)0);
+    launch_kernel_matrix<true>(KE, DC, h.d, grid, stream, (const double*)f.xst, Np, N, (const double*)f.xst, Np, N, h, f.a,
+                               Np, hdev, f.xs, f.mat, (const double*)nullptr, (double*)nullptr, (int64_t)0);
   });
   prof_end(BOBE_PROF_KXX);
   LAUNCH_CHECK();
@@ -250,9 +249,9 @@ void bobe_gp::assemble_kxx(const Hyper& h, const double* xst, double* a, const H
 // element accumulates its K range in the same order, four k per MFMA.)
 // colk0 (device table, one entry per block column): the columns of the launch start at different panels (deferred
 // columns, see potrf) - 64 x 64 tiles only.
-void bobe_gp::syrk(double* a, int k0, int k1, int first, int colmode, int B, int64_t bsA, const int* colk0, int far_col,
-                   int ncols) {
+void bobe_gp::syrk(const FactorBufs& f, int k0, int k1, int first, int colmode, const int* colk0, int far_col, int ncols) {
   const Tuning& tu = tuning();
+  const int B = f.B;
   const int rem = nb - first;                 // 128-blocks in the trailing matrix
   if (rem <= 0 || (!colk0 && k1 <= k0)) return;
   const int kb = k1 - k0;
@@ -265,15 +264,15 @@ void bobe_gp::syrk(double* a, int k0, int k1, int first, int colmode, int B, int
   // variants at every K (profiles/r02_a_ubench_update_variants.txt); when they would leave most of the chip idle, a single-panel
   // update takes 32x32 tiles, which stage the whole K = 128 panel in one LDS buffer
   if (kb == 1 && !colk0 && colmode != 2 && B * t64 < tu.syrk32_below) {
-    hipLaunchKernelGGL((k_syrk_trail<32, SYRK32_BK>), dim3(t32, B), dim3(256), SYRK32_SMEM, stream, a, Np, k0, k1, first,
-                       colmode, n32, bsA, 0, (const int*)nullptr, 0, 0);
+    hipLaunchKernelGGL((k_syrk_trail<32, SYRK32_BK>), dim3(t32, B), dim3(256), SYRK32_SMEM, stream, f.a, Np, k0, k1, first,
+                       colmode, n32, f.mat, 0, (const int*)nullptr, 0, 0);
     return;
   }
   const TileGrid tg = colmode ? TileGrid{t64, 0} : tile_grid(t64);
   // (the tile core BOBE_GEMM64_GLDS selects, through a function pointer: every argument is passed)
   const auto k64 = tu.gemm64_glds ? k_syrk_trail<64, SYRK64_BK, true> : k_syrk_trail<64, SYRK64_BK, false>;
-  hipLaunchKernelGGL(k64, dim3(tg.grid, B), dim3(256), SYRK64_SMEM, stream, a, Np, k0, k1, first, colmode, n64, bsA, tg.per,
-                     colk0, far_col, nc64);
+  hipLaunchKernelGGL(k64, dim3(tg.grid, B), dim3(256), SYRK64_SMEM, stream, f.a, Np, k0, k1, first, colmode, n64, f.mat,
+                     tg.per, colk0, far_col, nc64);
 }
 
 int bobe_gp::panel_strips(int B, int rr) const {
@@ -445,178 +444,166 @@ void bobe_gp::build_plans() {
 // The panel launches leave most of the chip empty (one 150 KB workgroup per 48 / 64 rows): where that pays (fill_pays),
 // updates of block columns that are not needed soon are DEFERRED and ride in those launches as filler workgroups
 // (chol_plan, k_chol_panel<true, .>).  Every matrix element sees the same operation sequence in all forms (same bits).
-void bobe_gp::potrf(double* a, double* linv, int* info_dev, int B, int64_t bsA, int64_t bsL, double* dg, bool defer_diag,
-                    const std::function<void(int)>* at_fork, int fork_panel) {
-  if (!dg) dg = diag.d();                                     // scratch for the L_kk of the panel launches
-  const int64_t bsD = (int64_t)nb * TILE * TILE;
-  int first_aside = nb;                                       // first step whose L_kk was left in the scratch blocks
-  const CholPlan& pl = chol_plan(B, fill_pays(B));
+// potrf_ops launches the ops [op_begin, op_end) of the plan - a linear list, which chol_solve cuts where it forks the
+// inverse - and potrf the whole of it.  The k_chol_panel steps leave their L_kk in the scratch blocks f.diag: `aside`.
+void bobe_gp::potrf_ops(const FactorBufs& f, const CholPlan& pl, size_t op_begin, size_t op_end, Aside& aside) {
+  const int B = f.B;
+  const int64_t bsD = (int64_t)nb * TILE * TILE;              // (f.diag: scratch for the L_kk of the panel launches)
   const FillJob* jobs = static_cast<const FillJob*>(pl.d_jobs.p);
   const int* coltab = static_cast<const int*>(pl.d_colk0.p);
-  for (const CholOp& op : pl.ops) {
+  for (size_t i = op_begin; i < op_end; ++i) {
+    const CholOp& op = pl.ops[i];
     if (op.kind == 0) {
       const int kk = op.k;
       const int rr = nb - 1 - kk;
       const int strips = panel_strips(B, rr);
       const int np_ = panel_workgroups(rr, strips);
-      const int rows_below = rr * TILE;
       const int nv = (int)std::min<int64_t>(TILE, N - (int64_t)kk * TILE);
       if (B * np_ <= std::max(num_cus, 1)) {
-        first_aside = std::min(first_aside, kk);
+        aside.first = std::min(aside.first, kk);              // (this step's L_kk stays in the scratch blocks)
+        auto panel = [&](auto FILLV, int gridx, const FillJob* jb, int njobs) {
+          const auto kern = strips == 3 ? k_chol_panel<decltype(FILLV)::value, 3> : k_chol_panel<decltype(FILLV)::value, 4>;
+          hipLaunchKernelGGL(kern, dim3(gridx, B), dim3(PANEL_THREADS), POTF2_SMEM_BYTES, stream, f.a, Np, f.mat, f.linv, Np,
+                             f.mat, kk, np_, f.info, nv, f.diag, bsD, jb, njobs, rr * TILE);
+        };
         prof_begin(BOBE_PROF_POTF2);
-#define PANEL_LAUNCH(FILLV, GRIDX, ...)                                                                                        \
-  do {                                                                                                                         \
-    if (strips == 3)                                                                                                           \
-      hipLaunchKernelGGL((k_chol_panel<FILLV, 3>), dim3(GRIDX, B), dim3(PANEL_THREADS), POTF2_SMEM_BYTES, stream, a, Np, bsA, \
-                         linv, Np, bsL, kk, np_, info_dev, nv, dg, bsD, __VA_ARGS__);                                          \
-    else                                                                                                                       \
-      hipLaunchKernelGGL((k_chol_panel<FILLV, 4>), dim3(GRIDX, B), dim3(PANEL_THREADS), POTF2_SMEM_BYTES, stream, a, Np, bsA, \
-                         linv, Np, bsL, kk, np_, info_dev, nv, dg, bsD, __VA_ARGS__);                                          \
-  } while (0)
-        if (op.tab_cnt > 0) PANEL_LAUNCH(true, np_ + op.tab_cnt / 2, jobs + op.tab_off, op.tab_cnt, rows_below);
-        else PANEL_LAUNCH(false, np_, (const FillJob*)nullptr, 0, rows_below);
-#undef PANEL_LAUNCH
+        if (op.tab_cnt > 0) panel(std::true_type{}, np_ + op.tab_cnt / 2, jobs + op.tab_off, op.tab_cnt);
+        else panel(std::false_type{}, np_, nullptr, 0);
         prof_end(BOBE_PROF_POTF2);
       } else {
         prof_begin(BOBE_PROF_POTF2);
-        hipLaunchKernelGGL(k_potf2<true>, dim3(B), dim3(256), POTF2_SMEM_BYTES, stream, a, Np, linv, Np, kk, info_dev, nv, bsA,
-                           bsL);
+        hipLaunchKernelGGL(k_potf2<true>, dim3(B), dim3(256), POTF2_SMEM_BYTES, stream, f.a, Np, f.linv, Np, kk, f.info, nv,
+                           f.mat, f.mat);
         prof_end(BOBE_PROF_POTF2);
         if (rr > 0) {
           prof_begin(BOBE_PROF_TRSM);
-          hipLaunchKernelGGL(k_trsm_panel, dim3(2 * rr, B), dim3(256), TRSM_SMEM_BYTES, stream, a, Np, (const double*)linv, Np,
-                             kk, bsA, bsL);
+          hipLaunchKernelGGL(k_trsm_panel, dim3(2 * rr, B), dim3(256), TRSM_SMEM_BYTES, stream, f.a, Np,
+                             (const double*)f.linv, Np, kk, f.mat, f.mat);
           prof_end(BOBE_PROF_TRSM);
         }
       }
-      if (at_fork && kk == fork_panel) (*at_fork)(first_aside);
     } else {
       prof_begin(BOBE_PROF_SYRK);
       if (op.uniform) {
-        syrk(a, op.k0_min, op.k, op.first, op.kind == 1 ? 1 : 0, B, bsA);
+        syrk(f, op.k0_min, op.k, op.first, op.kind == 1 ? 1 : 0);
       } else {
         // (columns before far_start share one first panel and take it as a scalar; deferred ones read the table.  A launch
         // whose active columns are few enumerates just those)
         const int ncols = op.last_active - op.first + 1;
         const bool few = ncols <= 8 && ncols < nb - op.first;
-        syrk(a, op.k0_plain, op.k, op.first, few ? 2 : 0, B, bsA, coltab + op.tab_off, pl.far_start, few ? ncols : 0);
+        syrk(f, op.k0_plain, op.k, op.first, few ? 2 : 0, coltab + op.tab_off, pl.far_start, few ? ncols : 0);
       }
       prof_end(BOBE_PROF_SYRK);
-    }
-  }
-  // (the scratch blocks of the k_chol_panel steps; k_potf2 steps wrote in place, and come first:
-  // B * npanel and rem only shrink with k)
-  cur->aside_first = 1 << 30;
-  cur->aside_dg = nullptr;
-  if (first_aside < nb) {
-    if (defer_diag) {
-      cur->aside_first = first_aside;
-      cur->aside_dg = dg;
-    } else {
-      hipLaunchKernelGGL(k_copy_diag, dim3(nb - first_aside, B), dim3(256), 0, stream, a, Np, bsA, (const double*)dg, bsD,
-                         first_aside);
     }
   }
   LAUNCH_CHECK();
 }
 
+bobe_gp::Aside bobe_gp::potrf(const FactorBufs& f, bool defer_diag) {
+  const CholPlan& pl = chol_plan(f.B, fill_pays(f.B));
+  Aside aside{nb, f.diag};
+  potrf_ops(f, pl, 0, pl.ops.size(), aside);
+  if (defer_diag) return aside;
+  // (the scratch blocks of the k_chol_panel steps; k_potf2 steps wrote in place, and come first:
+  // B * npanel and rem only shrink with k)
+  if (aside.first < nb) {
+    hipLaunchKernelGGL(k_copy_diag, dim3(nb - aside.first, f.B), dim3(256), 0, stream, f.a, Np, f.mat, aside.dg,
+                       (int64_t)nb * TILE * TILE, aside.first);
+    LAUNCH_CHECK();
+  }
+  return no_aside();
+}
+
 // One level of the recursive doubling (or the leading / trailing part of one): the problems of `part`, k_trtri_T and / or
 // k_trtri_R.  level_blocks: the 128-blocks of the WHOLE level, which pick the tile size - a part of a level takes the tiles
 // the level would (the bits do not depend on them; a timing comparison should not mix two changes).
-void bobe_gp::trtri_level(const TriArgs& t, const Depth& part, int level_blocks, bool do_t, bool do_r) {
+void bobe_gp::trtri_level(const FactorBufs& f, const Depth& part, int level_blocks, bool do_t, bool do_r, hipStream_t st) {
   const Tuning& tu = tuning();
   const TriProb* pr = static_cast<const TriProb*>(probs.p) + part.first;
   // (64x64 tiles while a level of ONE matrix has too few 128x128 tiles to fill the chip; a tile's K order is the
   // same either way.  Batches keep the per-matrix choice: four in lock step at N = 4096 take 7.0 ms per evaluation
   // round with 64x64 tiles at every level against 7.4 with 128x128 tiles at the top level)
-  if (t.B * 2 * level_blocks <= std::max(num_cus, 1)) {
+  if (f.B * 2 * level_blocks <= std::max(num_cus, 1)) {
     // A level with fewer 64 x 64 tile pairs than CUs (N <= 1024 in a batch of four, the deep levels of larger
     // matrices): 32 x 32 tiles - four times the workgroups, a quarter of the work each.  Such a launch lasts as long as
     // ONE workgroup's K loop, and a wave issues a 16 x 16 x 4 fp64 MFMA every 64 cycles at best: a quarter of the MFMAs
     // per wave and K-step is a shorter launch.  Tile shape does not change an element's accumulation order (same bits).
     const TileGrid tg = tile_grid(8 * part.nblocks);
     if (do_t)
-      hipLaunchKernelGGL(k_trtri_T<32>, dim3(tg.grid, t.B), dim3(256), GEMM32_SMEM_BYTES, stream, t.a, Np,
-                         (const double*)t.linv, Np, t.tmp, Np, pr, part.count, t.bsA, t.bsL, t.bsT, tg.per);
+      hipLaunchKernelGGL(k_trtri_T<32>, dim3(tg.grid, f.B), dim3(256), GEMM32_SMEM_BYTES, st, f.a, Np,
+                         (const double*)f.linv, Np, f.tmp, Np, pr, part.count, f.mat, f.mat, f.mat, tg.per);
     if (do_r)
-      hipLaunchKernelGGL(k_trtri_R<32>, dim3(tg.grid, t.B), dim3(256), GEMM32_SMEM_BYTES, stream, t.linv, Np,
-                         (const double*)t.tmp, Np, pr, part.count, t.bsL, t.bsT, tg.per);
+      hipLaunchKernelGGL(k_trtri_R<32>, dim3(tg.grid, f.B), dim3(256), GEMM32_SMEM_BYTES, st, f.linv, Np,
+                         (const double*)f.tmp, Np, pr, part.count, f.mat, f.mat, tg.per);
   } else if (level_blocks < tu.trtri64_below) {
     const TileGrid tg = tile_grid(2 * part.nblocks);             // (tile pairs of complementary K: equal work)
     const auto kT = tu.gemm64_glds ? k_trtri_T<64, true> : k_trtri_T<64, false>;
     const auto kR = tu.gemm64_glds ? k_trtri_R<64, true> : k_trtri_R<64, false>;
     if (do_t)
-      hipLaunchKernelGGL(kT, dim3(tg.grid, t.B), dim3(256), GEMM64_SMEM_BYTES, stream, t.a, Np, (const double*)t.linv, Np,
-                         t.tmp, Np, pr, part.count, t.bsA, t.bsL, t.bsT, tg.per);
+      hipLaunchKernelGGL(kT, dim3(tg.grid, f.B), dim3(256), GEMM64_SMEM_BYTES, st, f.a, Np, (const double*)f.linv, Np,
+                         f.tmp, Np, pr, part.count, f.mat, f.mat, f.mat, tg.per);
     if (do_r)
-      hipLaunchKernelGGL(kR, dim3(tg.grid, t.B), dim3(256), GEMM64_SMEM_BYTES, stream, t.linv, Np, (const double*)t.tmp, Np,
-                         pr, part.count, t.bsL, t.bsT, tg.per);
+      hipLaunchKernelGGL(kR, dim3(tg.grid, f.B), dim3(256), GEMM64_SMEM_BYTES, st, f.linv, Np, (const double*)f.tmp, Np,
+                         pr, part.count, f.mat, f.mat, tg.per);
   } else {
     if (do_t)
-      hipLaunchKernelGGL(k_trtri_T<128>, dim3(part.nblocks, t.B), dim3(256), GEMM_SMEM_BYTES, stream, t.a, Np,
-                         (const double*)t.linv, Np, t.tmp, Np, pr, part.count, t.bsA, t.bsL, t.bsT);
+      hipLaunchKernelGGL(k_trtri_T<128>, dim3(part.nblocks, f.B), dim3(256), GEMM_SMEM_BYTES, st, f.a, Np,
+                         (const double*)f.linv, Np, f.tmp, Np, pr, part.count, f.mat, f.mat, f.mat);
     if (do_r)
-      hipLaunchKernelGGL(k_trtri_R<128>, dim3(part.nblocks, t.B), dim3(256), GEMM_SMEM_BYTES, stream, t.linv, Np,
-                         (const double*)t.tmp, Np, pr, part.count, t.bsL, t.bsT);
+      hipLaunchKernelGGL(k_trtri_R<128>, dim3(part.nblocks, f.B), dim3(256), GEMM_SMEM_BYTES, st, f.linv, Np,
+                         (const double*)f.tmp, Np, pr, part.count, f.mat, f.mat);
   }
 }
 
-// Linv = L^-1, or one part of it, on `stream`: the diagonal 128-blocks of the part in one batched launch, then recursive
-// doubling (two GEMM launches per level).  TRI_LEAD ends with the top problem's T, TRI_TOP_R is its R alone.
-void bobe_gp::trtri_part(TriPart part, const TriArgs& t, const double* dg, int first_aside) {
+// Linv = L^-1, or one part of it, on the stream `st`: the diagonal 128-blocks of the part in one batched launch, then
+// recursive doubling (two GEMM launches per level).  TRI_LEAD ends with the top problem's T, TRI_TOP_R is its R alone.
+// (prof_begin / prof_end record on the handle's stream.  They fire only while the inverse is timed as a class, and then
+// inv_side_pays keeps the fork off: st is the handle's stream whenever they do.)
+void bobe_gp::trtri_part(TriPart part, const FactorBufs& f, Aside aside, hipStream_t st) {
   const int b0 = part == TRI_TRAIL ? tri_mid : 0, b1 = part == TRI_LEAD ? tri_mid : nb;
   if (part != TRI_TOP_R) {
     prof_begin(BOBE_PROF_TRTRI);
-    hipLaunchKernelGGL(k_trti_diag, dim3(b1 - b0, t.B), dim3(256), POTF2_SMEM_BYTES, stream, t.a, Np, t.linv, Np, t.bsA, t.bsL,
-                       dg, (int64_t)nb * TILE * TILE, first_aside, b0);
+    hipLaunchKernelGGL(k_trti_diag, dim3(b1 - b0, f.B), dim3(256), POTF2_SMEM_BYTES, st, f.a, Np, f.linv, Np, f.mat, f.mat,
+                       aside.dg, (int64_t)nb * TILE * TILE, aside.first, b0);
     prof_end(BOBE_PROF_TRTRI);
   }
   for (int dd = (int)depths.size() - 1; dd >= 0; --dd) {
     const Depth& D = depths[dd];
     if (part != TRI_ALL && dd > 0) {
       const Depth& P = part == TRI_LEAD ? lead_depths[dd] : trail_depths[dd];
-      if (part != TRI_TOP_R && P.count > 0) trtri_level(t, P, D.nblocks, true, true);
+      if (part != TRI_TOP_R && P.count > 0) trtri_level(f, P, D.nblocks, true, true, st);
       continue;
     }
     if (part == TRI_TRAIL) continue;
     prof_begin(BOBE_PROF_TRTRI);
-    trtri_level(t, D, D.nblocks, part != TRI_TOP_R, part != TRI_LEAD);
+    trtri_level(f, D, D.nblocks, part != TRI_TOP_R, part != TRI_LEAD, st);
     prof_end(BOBE_PROF_TRTRI);
   }
   LAUNCH_CHECK();
 }
 
-void bobe_gp::trtri(double* a, double* linv, double* tmp, int B, int64_t bsA, int64_t bsL, int64_t bsT) {
-  trtri_part(TRI_ALL, {a, linv, tmp, B, bsA, bsL, bsT}, cur->aside_dg, cur->aside_first);
-  cur->aside_first = 1 << 30;
-  cur->aside_dg = nullptr;
-}
-
-// K^-1 tiles fused with the gradient partial sums (optionally stores K^-1's lower tiles); returns #partials.
-// scratch (an Np x Np matrix per slot, stride bsS): small launches - fewer 64 x 64 tiles than four per CU - form K^-1 on
-// 32 x 32 tiles into it first (k_lauum_tiles) and run the gradient epilogue from there: N = 1024 in a batch of four,
-// 77 -> 36 us (the fused launch is as long as its longest tile, K = 1024 on one CU).  Same partial sums, same bits.
-// bsK: the member stride of kinv_out (the batched LOO objective keeps every member's K^-1).
-int bobe_gp::lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
-                   const Hyper* hdev, double* gp_out, int B, int64_t bsL, int64_t bsV, int64_t bsX, int64_t bsP,
-                   double* scratch, int64_t bsS, int64_t bsKout) {
+// K^-1 tiles fused with the gradient partial sums (into f.gpart); returns #partials.  store_kinv: K^-1's lower tiles are
+// stored to f.tmp (every member's: the LOO objective; kinv_debug).  Else f.tmp is scratch: small launches - fewer 64 x 64
+// tiles than four per CU - form K^-1 on 32 x 32 tiles into it first (k_lauum_tiles) and run the gradient epilogue from
+// there: N = 1024 in a batch of four, 77 -> 36 us (the fused launch is as long as its longest tile, K = 1024 on one CU).
+// Same partial sums, same bits.
+int bobe_gp::lauum(const Hyper& h, const FactorBufs& f, const Hyper* hdev, bool store_kinv) {
   // (the tile size fixes the order of the gradient's partial sums: it depends on N only, so that an evaluation
   // returns the same bits alone, on a slot and in a batch)
   const LauumTiling t = lauum_tiling(nb);
-  const int ntiles = t.ntiles;
-  double* gpo = gp_out ? gp_out : gpart.d();
-  const bool split = t.small && scratch && !kinv_out && B * ntiles < 4 * std::max(num_cus, 1);
-  double* kio = split ? scratch : kinv_out;
-  const int64_t bsK = split ? bsS : bsKout;
+  const int ntiles = t.ntiles, B = f.B;
+  const bool split = t.small && !store_kinv && B * ntiles < 4 * std::max(num_cus, 1);
+  double* kio = split || store_kinv ? f.tmp : nullptr;
   prof_begin(BOBE_PROF_LAUUM);
   if (split) {
-    hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, linv, Np, Np, scratch, Np,
-                       bsL, bsS, B);
+    hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, (const double*)f.linv, Np,
+                       Np, f.tmp, Np, f.mat, f.mat, B);
   }
   with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT, auto GL) {
     hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT, GL>), dim3(ntiles * B), dim3(256),
-                       (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, linv, Np, Np, N, al, xst, Np, h, gpo, kio,
-                       Np, hdev, bsL, bsV, bsX, bsP, B, split ? 1 : 0, bsK);
+                       (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)f.linv, Np, Np, N,
+                       (const double*)f.alpha, (const double*)f.xst, Np, h, f.gpart, kio, Np, hdev, f.mat, f.vec, f.xs, f.gps,
+                       B, split ? 1 : 0, kio ? f.mat : (int64_t)0);
   });
   prof_end(BOBE_PROF_LAUUM);
   LAUNCH_CHECK();
@@ -678,14 +665,20 @@ void bobe_gp::ensure_side() {
   side_stream = st;
 }
 
-// potrf, the inverse, w / alpha.  Where it pays (inv_side_pays) the inverse's leading half leaves the critical path: potrf
-// calls back after panel mid - 1, the hook forks the side stream off there and queues TRI_LEAD on it; the handle's stream
-// finishes the factorisation, inverts the trailing half, waits for the side stream and closes with the top level's R.  The
-// same launches on the same data in an order every element's dependencies allow: the same bits.
-void bobe_gp::chol_solve(const FactorBufs& f, int B, const double* rhs) {
-  const TriArgs t{f.a, f.linv, f.tmp, B, f.mat, f.mat, f.mat};
-  if (inv_side_pays(B)) {
+// potrf, the inverse, w / alpha.  Where it pays (inv_side_pays) the inverse's leading half leaves the critical path: the
+// plan's op list is cut one past panel mid - 1, the side stream is forked off between the two ranges and gets TRI_LEAD with
+// what is aside so far; the handle's stream finishes the factorisation, inverts the trailing half, waits for the side
+// stream and closes with the top level's R.  The same launches on the same data in an order every element's dependencies
+// allow: the same bits.
+void bobe_gp::chol_solve(const FactorBufs& f, const double* rhs) {
+  if (inv_side_pays(f.B)) {
     ensure_side();
+    const CholPlan& pl = chol_plan(f.B, fill_pays(f.B));
+    size_t cut = 0;                       // one past the panel op after which block columns < mid are final
+    while (cut < pl.ops.size() && !(pl.ops[cut].kind == 0 && pl.ops[cut].k == tri_mid - 1)) ++cut;
+    if (cut == pl.ops.size())
+      throw Err(BOBE_ERR_STATE, "internal error: the factorisation has no panel to fork the inverse after");
+    ++cut;
     struct Join {                         // no exception leaves with the side stream still working on the caller's buffers
       bobe_gp& g;
       bool forked = false, joined = false;
@@ -693,40 +686,28 @@ void bobe_gp::chol_solve(const FactorBufs& f, int B, const double* rhs) {
         if (forked && !joined) (void)hipStreamSynchronize(g.side_stream);
       }
     } join{*this};
-    const std::function<void(int)> fork = [&](int first_aside) {
-      HIPCHK(hipEventRecord(ev_fork, stream));
-      HIPCHK(hipStreamWaitEvent(side_stream, ev_fork, 0));
-      join.forked = true;
-      {
-        struct OnSide {
-          bobe_gp& g;
-          const hipStream_t main;
-          ~OnSide() { g.stream = main; }
-        } on_side{*this, stream};
-        stream = side_stream;
-        trtri_part(TRI_LEAD, t, f.diag, first_aside);
-      }
-      HIPCHK(hipEventRecord(ev_join, side_stream));
-    };
-    potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag, true, &fork, tri_mid - 1);
-    if (!join.forked) throw Err(BOBE_ERR_STATE, "internal error: the factorisation has no panel to fork the inverse after");
-    trtri_part(TRI_TRAIL, t, cur->aside_dg, cur->aside_first);
-    cur->aside_first = 1 << 30;
-    cur->aside_dg = nullptr;
+    Aside aside{nb, f.diag};
+    potrf_ops(f, pl, 0, cut, aside);
+    HIPCHK(hipEventRecord(ev_fork, stream));
+    HIPCHK(hipStreamWaitEvent(side_stream, ev_fork, 0));
+    join.forked = true;
+    trtri_part(TRI_LEAD, f, aside, side_stream);
+    HIPCHK(hipEventRecord(ev_join, side_stream));
+    potrf_ops(f, pl, cut, pl.ops.size(), aside);
+    trtri_part(TRI_TRAIL, f, aside, stream);
     HIPCHK(hipStreamWaitEvent(stream, ev_join, 0));
     join.joined = true;
-    trtri_part(TRI_TOP_R, t, nullptr, 0);
+    trtri_part(TRI_TOP_R, f, no_aside(), stream);
   } else {
-    potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag, true);
-    trtri(f.a, f.linv, f.tmp, B, f.mat, f.mat, f.mat);
+    trtri(f, potrf(f, true));
   }
-  solve_alpha(f.linv, f.w, f.alpha, f.part, B, f.mat, f.vec, f.prt, rhs, 0);
+  solve_alpha(f.linv, f.w, f.alpha, f.part, f.B, f.mat, f.vec, f.prt, rhs, 0);
 }
 
-void bobe_gp::factor_into(const Hyper& h, const FactorBufs& f, const Hyper* hdev, int B) {
-  scale(X.d(), N, Np, h, f.xst, Np, hdev, B, f.xs, f.info);      // (also arms the B info words)
-  assemble_kxx(h, f.xst, f.a, hdev, B, f.xs, f.mat);
-  chol_solve(f, B);
+void bobe_gp::factor_into(const Hyper& h, const FactorBufs& f, const Hyper* hdev) {
+  scale(X.d(), N, Np, h, f.xst, Np, hdev, f.B, f.xs, f.info);    // (also arms the B info words)
+  assemble_kxx(h, f, hdev);
+  chol_solve(f);
 }
 
 void bobe_gp::mll_terms(const double* wv, const double* a, double* res_dev, const int* info_dev) {
@@ -794,20 +775,18 @@ void bobe_gp::ensure_batch(int B) {
 // in the pinned ws.h_res[b * 128 + ...]; the info word of member b rides in res[b * 128 + 100], so one copy brings
 // everything to the host.  noise_grad: the launches of the gradient's noise component follow the others (gp_loo.hip).
 void bobe_gp::eval_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad) {
-  const FactorBufs f = ws.bufs();
-  const int64_t gps = ws.stride(ws.gps()), rs = ws.stride(128);
+  const FactorBufs f = ws.bufs(B);
   if (hdev) HIPCHK(hipMemcpyAsync(ws.hyp.p, ws.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
-  factor_into(hs[0], f, hdev, B);
+  factor_into(hs[0], f, hdev);
   if (want_grad) {
-    const int ntiles = lauum(hs[0], f.linv, f.alpha, f.xst, nullptr, hdev, ws.gpart.d(), B, f.mat, f.vec, f.xs, gps, f.tmp,
-                             f.mat);
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)ws.gpart.d(), ntiles,
-                       dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)f.w, (const double*)f.a, Np, Np,
-                       (const int*)f.info, gps, rs, f.vec, f.mat);
-    if (noise_grad) mll_noise_tail(ws, B, hs, hdev);
+    const int ntiles = lauum(hs[0], f, hdev, false);
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 2, B), dim3(256), 0, stream, (const double*)f.gpart, ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), f.res, (const double*)f.w, (const double*)f.a, Np, Np,
+                       (const int*)f.info, f.gps, f.rs, f.vec, f.mat);
+    if (noise_grad) mll_noise_tail(f, hs, hdev);
   } else {
-    hipLaunchKernelGGL(k_mll_terms, dim3(B), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, ws.res.d(),
-                       f.vec, f.mat, rs, (const int*)f.info);
+    hipLaunchKernelGGL(k_mll_terms, dim3(B), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, f.res,
+                       f.vec, f.mat, f.rs, (const int*)f.info);
   }
   LAUNCH_CHECK();
   // ([100] = info, [101] = min L_jj are the last a member writes; the batch brings its members' whole blocks)
@@ -1182,7 +1161,7 @@ void bobe_gp::set_chol(const double* L, const double* alpha_in) {
     hipLaunchKernelGGL(k_potf2<false>, dim3(1), dim3(256), POTF2_SMEM_BYTES, stream, A.d(), Np, Linv.d(), Np, k,
                        static_cast<int*>(info.p));
   LAUNCH_CHECK();
-  trtri(A.d(), Linv.d(), Tmp.d());
+  trtri(state_bufs(), no_aside());
   // the restored factor's smallest pivot decides how the products with Linv are formed, as after a factorisation
   const double min_diag = min_pivot_root();
   factored = true;
@@ -1219,7 +1198,7 @@ int bobe_gp::mll_from_k(const double* K, int64_t n, const double* yv, double* ml
   sync();
   size_workspace(n);
   forget_evals();                                  // (the handle's own workspace holds this matrix's factor from here on)
-  const FactorBufs f = own.bufs();
+  const FactorBufs f = own.bufs(1);
   const double* k_in = fetch(K, (size_t)n * n, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, k_in, n,
                      f.a, Np, Np, 1);
@@ -1227,7 +1206,7 @@ int bobe_gp::mll_from_k(const double* K, int64_t n, const double* yv, double* ml
   HIPCHK(hipMemcpyAsync(w.p, yv, (size_t)n * sizeof(double),
                         is_device_ptr(yv) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemsetAsync(f.info, 0x7f, sizeof(int), stream));
-  chol_solve(f, 1, w.d());
+  chol_solve(f, w.d());
   mll_terms(f.w, f.a, own.res.d(), f.info);
   res_to_host(own.res.d(), own.h_res, 102);
   // (this entry's own rule instead of a floor: min L_jj > 0; a NaN floor fails whatever the pivot)
@@ -1241,7 +1220,7 @@ void bobe_gp::chol_row_update(const double* L, int64_t n, const double* k, doubl
   sync();
   size_workspace(n);
   forget_evals();
-  const FactorBufs f = own.bufs();
+  const FactorBufs f = own.bufs(1);
   const double* l_in = fetch(L, (size_t)n * n, kout);
   hipLaunchKernelGGL(k_load_padded_lower, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, stream, l_in, n,
                      f.a, Np, Np, 0);
@@ -1251,7 +1230,7 @@ void bobe_gp::chol_row_update(const double* L, int64_t n, const double* k, doubl
   for (int kb = 0; kb < nb; ++kb)                      // the 16 x 16 diagonal inverses the block inverse starts from
     hipLaunchKernelGGL(k_potf2<false>, dim3(1), dim3(256), POTF2_SMEM_BYTES, stream, f.a, Np, f.linv, Np, kb, f.info);
   LAUNCH_CHECK();
-  trtri(f.a, f.linv, f.tmp);
+  trtri(f, no_aside());
   hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), 1u), dim3(256), 0, stream, (const double*)f.linv, Np, Np,
                      (const double*)w.d(), f.w, (int64_t)0, (int64_t)0, (int64_t)0);
   mll_terms(f.w, f.a, own.res.d(), nullptr);
@@ -1264,7 +1243,7 @@ void bobe_gp::chol_row_update(const double* L, int64_t n, const double* k, doubl
 void bobe_gp::kinv_debug(double* Kinv) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   use();
-  lauum(hyp, Linv.d(), alpha.d(), XsT.d(), Tmp.d());
+  lauum(hyp, state_bufs(), nullptr, true);
   // symmetrise on the host side of the copy
   std::vector<double> full((size_t)N * N);
   HIPCHK(hipMemcpy2DAsync(full.data(), (size_t)N * 8, Tmp.p, (size_t)Np * 8, (size_t)N * 8, (size_t)N, hipMemcpyDeviceToHost,
@@ -1323,7 +1302,7 @@ double bobe_gp::time_potrf_wide(EvalWs& ws, int B, int reps) {
   forget_evals();                                              // (the timers factorise into the evaluation workspaces)
   if (ws.width > 1) ensure_batch(B);
   UseWs use_ws(*this, ws);
-  const FactorBufs f = ws.bufs();
+  const FactorBufs f = ws.bufs(B);
   const Hyper* hdev = nullptr;
   if (ws.width > 1) {
     for (int b = 0; b < B; ++b) ws.h_hyp[b] = hyp;
@@ -1334,10 +1313,10 @@ double bobe_gp::time_potrf_wide(EvalWs& ws, int B, int reps) {
   return timed_passes(
       stream, reps,
       [&] {
-        assemble_kxx(hyp, f.xst, f.a, hdev, B, f.xs, f.mat);
+        assemble_kxx(hyp, f, hdev);
         HIPCHK(hipMemsetAsync(f.info, 0x7f, (size_t)B * sizeof(int), stream));
       },
-      [&](hipEvent_t) { potrf(f.a, f.linv, f.info, B, f.mat, f.mat, f.diag); });
+      [&](hipEvent_t) { potrf(f); });
 }
 
 double bobe_gp::time_potrf(int reps) { return time_potrf_wide(own, 1, reps); }
@@ -1356,20 +1335,20 @@ double bobe_gp::time_potrf_batch(int B, int reps) {
       stream, reps,
       [&] {
         for (int i = 0; i < B; ++i) {      // K(X,X) of every slot, on the handle's stream
-          const FactorBufs f = slots[i]->bufs();
+          const FactorBufs f = slots[i]->bufs(1);
           scale(X.d(), N, Np, hyp, f.xst, Np);
-          assemble_kxx(hyp, f.xst, f.a);
+          assemble_kxx(hyp, f);
           HIPCHK(hipMemsetAsync(f.info, 0x7f, sizeof(int), stream));
         }
       },
       [&](hipEvent_t e0) {
         for (int i = 0; i < B; ++i) {
           EvalWs& sl = *slots[i];
-          const FactorBufs f = sl.bufs();
+          const FactorBufs f = sl.bufs(1);
           HIPCHK(hipStreamWaitEvent(sl.stream, e0, 0));
           {
             UseWs use_ws(*this, sl);
-            potrf(f.a, f.linv, f.info, 1, 0, 0, f.diag);
+            potrf(f);
           }
           HIPCHK(hipEventRecord(done[i], sl.stream));
           HIPCHK(hipStreamWaitEvent(stream, done[i], 0));

@@ -25,7 +25,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -430,12 +429,15 @@ struct bobe_gp {
     hipGraphExec_t exec[2] = {nullptr, nullptr};    // [want_grad]
     std::array<const void*, 16> sig[2] = {};        // every address / size the captured kernels were given
   };
-  // what the factorisation front (factor_into / chol_solve) works on: a workspace's buffers with its member strides, or
-  // the installed factor's with stride 0
+  // How a stage of the factorisation front (assemble_kxx, potrf, trtri, lauum, loo_terms, factor_into / chol_solve) is told
+  // where to work and how wide: B members, member b at b * stride of every buffer.  A workspace's buffers with its member
+  // strides (EvalWs::bufs), or the installed factor's at width 1 (state_bufs); a width-1 view has stride 0 throughout.
+  // mat strides a, linv and tmp; vec w and alpha; xs xst; prt part; gps gpart; rs res (128 per member); lvs loo.
   struct FactorBufs {
-    double *xst, *a, *linv, *tmp, *w, *alpha, *part, *diag;
+    int B;
+    double *xst, *a, *linv, *tmp, *w, *alpha, *part, *diag, *gpart, *res, *loo;
     int* info;
-    int64_t mat, vec, xs, prt;
+    int64_t mat, vec, xs, prt, gps, rs, lvs;
   };
   struct EvalWs {
     explicit EvalWs(int width_) : width(width_), tag(width_), floor(width_, 0.0) {}
@@ -453,8 +455,6 @@ struct bobe_gp {
     EvalGraph eg;
     std::vector<bobe::EvalTag> tag;  // per member: what it holds
     std::vector<double> floor;       // per member: the rank test's floor of the evaluation in flight (read at collect)
-    int aside_first = 1 << 30;       // set by potrf(defer_diag = true) on this workspace, consumed by the next trtri()
-    const double* aside_dg = nullptr;
     // evaluation slots only: the private stream (the handle's, of slot_stream_set) and the state of submit / wait
     hipStream_t stream = nullptr;
     hipEvent_t ev = nullptr;
@@ -468,17 +468,19 @@ struct bobe_gp {
     int64_t lvs() const { return 7 * Np; }
     // the strides the launches are given: a width-1 workspace is the plain call (B = 1, stride 0)
     int64_t stride(int64_t per_member) const { return width > 1 ? per_member : 0; }
-    FactorBufs bufs() const {
-      return {XsT.d(), A.d(), Linv.d(), Tmp.d(), w.d(), alpha.d(), part.d(), diag.d(), static_cast<int*>(info.p),
-              stride(mat()), stride(vec()), stride(xs()), stride(prt())};
+    FactorBufs bufs(int B) const {               // the view the stages are given: members [0, B)
+      return {B, XsT.d(), A.d(), Linv.d(), Tmp.d(), w.d(), alpha.d(), part.d(), diag.d(), gpart.d(), res.d(), loo.d(),
+              static_cast<int*>(info.p), stride(mat()), stride(vec()), stride(xs()), stride(prt()), stride(gps()),
+              stride(128), stride(lvs())};
     }
     void ensure(const bobe_gp& g, int B);      // room for B members at the handle's Np / nb / d
     void release();
   };
   EvalWs own{1}, batch{BOBE_MAX_MLL_SLOTS};
   std::vector<EvalWs*> slots;                // (reserved once: bobe_gp_mll_wait reads it without the submit mutex)
-  // The workspace the stage functions run on: potrf / trtri keep their hand-over (aside_*) there, and on a slot the
-  // handle's `stream` is the slot's.  UseWs makes one current for a scope; nothing else of the handle changes.
+  // The workspace an evaluation runs on.  It holds buffers and records only - no stage leaves hand-over state on it (the
+  // stages get a FactorBufs view and pass what they hand over by value) - so `cur` is just what on_slot() reads, and on a
+  // slot the handle's `stream` is the slot's.  UseWs makes one current for a scope; nothing else of the handle changes.
   EvalWs* cur = &own;
   bool on_slot() const { return cur->stream != nullptr; }
   struct UseWs {
@@ -496,8 +498,9 @@ struct bobe_gp {
     UseWs(const UseWs&) = delete;
     UseWs& operator=(const UseWs&) = delete;
   };
-  FactorBufs state_bufs() const {
-    return {XsT.d(), A.d(), Linv.d(), Tmp.d(), w.d(), alpha.d(), part.d(), diag.d(), static_cast<int*>(info.p), 0, 0, 0, 0};
+  FactorBufs state_bufs() const {            // the installed factor (loo: loo_ws, once loo_state has sized it)
+    return {1, XsT.d(), A.d(), Linv.d(), Tmp.d(), w.d(), alpha.d(), part.d(), diag.d(), gpart.d(), res.d(), loo_ws.d(),
+            static_cast<int*>(info.p), 0, 0, 0, 0, 0, 0, 0};
   }
   std::vector<hipStream_t> slot_streams;     // one per evaluation slot, created on first use
   const std::vector<hipStream_t>& slot_stream_set();
@@ -584,47 +587,51 @@ struct bobe_gp {
   void kernel_matrix_cross(const double* AT, int64_t lda, int64_t na, int64_t napad, const double* BT, int64_t ldb,
                            int64_t nbv, int64_t nbpad, const Hyper& h, double* out, int64_t ldo,
                            const double* wv = nullptr, double* prt = nullptr, int64_t ldp = 0);
-  void assemble_kxx(const Hyper& h, const double* xst, double* a, const Hyper* hdev = nullptr, int B = 1,
-                    int64_t bsX = 0, int64_t bsA = 0);
-  void syrk(double* a, int k0, int k1, int first, int colmode, int B = 1, int64_t bsA = 0, const int* colk0 = nullptr,
-            int far_col = 0, int ncols = 0);
-  // defer_diag: leave the L_kk scratch blocks where they are; the trtri() that follows puts them in place (one launch less)
-  // at_fork / fork_panel: called right after the launch of panel fork_panel, with the first step whose L_kk is in the
-  // scratch blocks so far (nb: none yet) - from there on the factorisation leaves block columns <= fork_panel alone
-  void potrf(double* a, double* linv, int* info_dev, int B = 1, int64_t bsA = 0, int64_t bsL = 0, double* dg = nullptr,
-             bool defer_diag = false, const std::function<void(int)>* at_fork = nullptr, int fork_panel = -1);
-  // The matrices a factorisation / an inverse works on, and the parts of the inverse (tri_split.hpp): TRI_ALL is the whole
-  // of it, TRI_LEAD + TRI_TRAIL + TRI_TOP_R in this order (LEAD and TRAIL in either order, or side by side) the same launches
-  // on the same data.  dg / first_aside: the scratch blocks that still hold the L_kk of steps >= first_aside (potrf).
-  struct TriArgs {
-    double *a, *linv, *tmp;
-    int B;
-    int64_t bsA, bsL, bsT;
+  void assemble_kxx(const Hyper& h, const FactorBufs& f, const Hyper* hdev = nullptr);
+  void syrk(const FactorBufs& f, int k0, int k1, int first, int colmode, const int* colk0 = nullptr, int far_col = 0,
+            int ncols = 0);
+  // What a factorisation hands to the inverse that follows it: the L_kk of steps >= first are still in the scratch blocks
+  // dg (first = nb: none).  It travels by value - potrf returns it, the inverse takes it - and nothing of it stays behind.
+  struct Aside {
+    int first;
+    const double* dg;
   };
+  Aside no_aside() const { return {nb, nullptr}; }           // an inverse of a factor that no potrf of ours left behind
+  // The factorisation of f.a (L in place, the 16 x 16 diagonal inverses into f.linv): potrf_ops runs the ops
+  // [op_begin, op_end) of the launch plan and lowers `aside` to the first step it left in the scratch blocks; potrf is the
+  // whole plan.  defer_diag: return what is aside for the trtri() that follows to put in place (one launch less); else
+  // k_copy_diag puts the blocks back here and nothing is aside.
+  void potrf_ops(const FactorBufs& f, const CholPlan& pl, size_t op_begin, size_t op_end, Aside& aside);
+  Aside potrf(const FactorBufs& f, bool defer_diag = false);
+  // The parts of the inverse (tri_split.hpp): TRI_ALL is the whole of it, TRI_LEAD + TRI_TRAIL + TRI_TOP_R in this order
+  // (LEAD and TRAIL in either order, or side by side) the same launches on the same data.  trtri_part / trtri_level launch
+  // on the stream they are given; trtri is TRI_ALL on the handle's.
   enum TriPart { TRI_ALL, TRI_LEAD, TRI_TRAIL, TRI_TOP_R };
-  void trtri_part(TriPart part, const TriArgs& t, const double* dg, int first_aside);
-  void trtri_level(const TriArgs& t, const bobe::Depth& part, int level_blocks, bool do_t, bool do_r);
-  void trtri(double* a, double* linv, double* tmp, int B = 1, int64_t bsA = 0, int64_t bsL = 0, int64_t bsT = 0);
+  void trtri_part(TriPart part, const FactorBufs& f, Aside aside, hipStream_t st);
+  void trtri_level(const FactorBufs& f, const bobe::Depth& part, int level_blocks, bool do_t, bool do_r, hipStream_t st);
+  void trtri(const FactorBufs& f, Aside aside) { trtri_part(TRI_ALL, f, aside, stream); }
   // ---- the side stream of the inverse's leading half (chol_solve).  With mid = nb / 2, once panel mid - 1 has run the
   // factorisation only writes A[mid:, mid:], the scratch blocks and 16 x 16 inverses of steps >= mid and the info word:
   // TRI_LEAD reads L[:, 0:mid) and writes Linv[0:mid, 0:mid) and Tmp[:, 0:mid), so it can run beside panels mid .. nb-1,
-  // which leave most CUs empty.  One fork (ev_fork, recorded by potrf's hook) and one join (ev_join, waited for before
-  // TRI_TOP_R) per factorisation; ordering by events only.  Only on the handle's own stream: never on an evaluation slot,
-  // never under graph capture (`capturing`), never while the inverse's launches are being timed as a class.
+  // which leave most CUs empty.  chol_solve cuts the plan's op list after that panel: one fork (ev_fork, recorded between
+  // the two ranges) and one join (ev_join, waited for before TRI_TOP_R) per factorisation; ordering by events only, and the
+  // handle's `stream` is never swapped for it.  Only on the handle's own stream: never on an evaluation slot, never under
+  // graph capture (`capturing`), never while the inverse's launches are being timed as a class.
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool capturing = false;
   bool inv_side_pays(int B) const;
   void ensure_side();
-  int lauum(const Hyper& h, const double* linv, const double* al, const double* xst, double* kinv_out,
-            const Hyper* hdev = nullptr, double* gp_out = nullptr, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
-            int64_t bsX = 0, int64_t bsP = 0, double* scratch = nullptr, int64_t bsS = 0, int64_t bsK = 0);
-  // wv = Linv rhs, al = Linv^T wv (rhs: y unless given; bsY: its stride per batch member)
+  // K^-1 tiles with the gradient's partial sums into f.gpart; returns their count.  store_kinv: K^-1's lower tiles go to
+  // f.tmp (the LOO objective, kinv_debug); else f.tmp is the scratch of the 32-tile form (the MLL gradient)
+  int lauum(const Hyper& h, const FactorBufs& f, const Hyper* hdev, bool store_kinv);
+  // wv = Linv rhs, al = Linv^T wv (rhs: y unless given; bsY: its stride per batch member).  Pointer form: bobe_gp_wip_grad
+  // solves for many right-hand sides against ONE factor, a pattern no FactorBufs describes
   void solve_alpha(const double* linv, double* wv, double* al, double* prt, int B = 1, int64_t bsL = 0, int64_t bsV = 0,
                    int64_t bsP = 0, const double* rhs = nullptr, int64_t bsY = 0);
   // scale, K(X, X), chol_solve on f's buffers; chol_solve: potrf, trtri, w / alpha of the right-hand side (y unless given)
-  void factor_into(const Hyper& h, const FactorBufs& f, const Hyper* hdev = nullptr, int B = 1);
-  void chol_solve(const FactorBufs& f, int B = 1, const double* rhs = nullptr);
+  void factor_into(const Hyper& h, const FactorBufs& f, const Hyper* hdev = nullptr);
+  void chol_solve(const FactorBufs& f, const double* rhs = nullptr);
   // k_mll_terms of one factor (w may be NULL: the pivots only) into res; res_to_host: its first n doubles, synchronised
   void mll_terms(const double* wv, const double* a, double* res_dev, const int* info_dev);
   void res_to_host(const double* res_dev, double* h, int n);
@@ -670,10 +677,10 @@ struct bobe_gp {
   // ---- gp_loo.hip (loo_ws: seven vectors of Np - diag K^-1, mean, var, lpd, sqrt c, b / sqrt c, w - of the state form;
   // an evaluation works on its workspace's own)
   DBuf loo_ws;
-  // The LOO terms of B factors: their inverse factors (stride bsL), alphas (bsA), partial sums (bsP), seven-vector blocks
-  // lw (bsV); the sums land in sum_out + b * bsO
-  void loo_terms(const double* linv, const double* al, double* prt, double* lw, bool with_grad_terms, double* sum_out,
-                 int B = 1, int64_t bsL = 0, int64_t bsA = 0, int64_t bsP = 0, int64_t bsV = 0, int64_t bsO = 0);
+  // The LOO terms of f's factors, from their inverse factors and alphas through f.part into the seven-vector blocks f.loo; the
+  // sums land in f.res[102].  loo_kinv_diag is their front: diag K^-1 into the first vector of f.loo
+  void loo_kinv_diag(const FactorBufs& f);
+  void loo_terms(const FactorBufs& f, bool with_grad_terms);
   int loo_state(double* mean, double* var, double* lpd, double* sum_lpd);
   // the launches of B LOO evaluations on ws (eval_enqueue's counterpart), and their start-to-collect on ws
   void loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad = false);
@@ -682,8 +689,8 @@ struct bobe_gp {
   int loo_batch(int64_t B, const double* ls, const double* kvar, double* loo, double* grad, int* status,
                 const double* noise = nullptr);
   // the noise component of the gradient, d / d log nu: the launches appended to an MLL / a LOO evaluation with a gradient
-  void mll_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev);
-  void loo_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev);
+  void mll_noise_tail(const FactorBufs& f, const Hyper* hs, const Hyper* hdev);
+  void loo_noise_tail(const FactorBufs& f, const Hyper* hs, const Hyper* hdev);
 
   // ---- gp_batch.hip (call-local buffers only; the handle's Z-side state is read, never written)
   int wip_select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,

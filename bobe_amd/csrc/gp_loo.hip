@@ -23,19 +23,25 @@ void configure_loo_kernels() {
 
 }  // namespace bobe
 
-// a = diag(K^-1) from the inverse factors `linv`, then mean / var / lpd (and sqrt c, b / sqrt c when `with_grad_terms`) into
-// lw, and sum lpd into sum_out (device).  lw: seven vectors of Np per member - a, mean, var, lpd, sqrt c, b / sqrt c, w.
-void bobe_gp::loo_terms(const double* linv, const double* al, double* prt, double* lw, bool with_grad_terms, double* sum_out,
-                        int B, int64_t bsL, int64_t bsA, int64_t bsP, int64_t bsV, int64_t bsO) {
-  const unsigned nm = (unsigned)B;
-  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream, linv, Np, prt, Np, bsL,
-                     bsP);
-  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)prt, Np, nb, 1,
-                     Np, lw, bsP, bsV);
-  hipLaunchKernelGGL(k_loo_point, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)lw, al,
-                     (const double*)y.d(), N, Np, lw + Np, lw + 2 * Np, lw + 3 * Np, with_grad_terms ? lw + 4 * Np : nullptr,
-                     with_grad_terms ? lw + 5 * Np : nullptr, bsA, bsV);
-  hipLaunchKernelGGL(k_loo_sum, dim3(1, nm), dim3(256), 0, stream, (const double*)(lw + 3 * Np), N, sum_out, bsV, bsO);
+// a = diag(K^-1) of f's members, from their inverse factors through f.part into the first vector of their LOO blocks
+void bobe_gp::loo_kinv_diag(const FactorBufs& f) {
+  const unsigned nm = (unsigned)f.B;
+  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream,
+                     (const double*)f.linv, Np, f.part, Np, f.mat, f.prt);
+  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)f.part, Np,
+                     nb, 1, Np, f.loo, f.prt, f.lvs);
+}
+
+// a (loo_kinv_diag), then mean / var / lpd (and sqrt c, b / sqrt c when `with_grad_terms`) into the LOO blocks, and sum lpd
+// into res[102].  A LOO block: seven vectors of Np per member - a, mean, var, lpd, sqrt c, b / sqrt c, w.
+void bobe_gp::loo_terms(const FactorBufs& f, bool with_grad_terms) {
+  const unsigned nm = (unsigned)f.B;
+  double* lw = f.loo;
+  loo_kinv_diag(f);
+  hipLaunchKernelGGL(k_loo_point, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)lw,
+                     (const double*)f.alpha, (const double*)y.d(), N, Np, lw + Np, lw + 2 * Np, lw + 3 * Np,
+                     with_grad_terms ? lw + 4 * Np : nullptr, with_grad_terms ? lw + 5 * Np : nullptr, f.vec, f.lvs);
+  hipLaunchKernelGGL(k_loo_sum, dim3(1, nm), dim3(256), 0, stream, (const double*)(lw + 3 * Np), N, f.res + 102, f.lvs, f.rs);
   LAUNCH_CHECK();
 }
 
@@ -44,7 +50,7 @@ int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) 
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   use();
   loo_ws.ensure((size_t)7 * Np * sizeof(double));
-  loo_terms(Linv.d(), alpha.d(), part.d(), loo_ws.d(), false, res.d() + 102);
+  loo_terms(state_bufs(), false);
   const double* ws = loo_ws.d();
   double* outs[3] = {mean, var, lpd};
   for (int q = 0; q < 3; ++q)
@@ -65,31 +71,22 @@ int bobe_gp::loo_state(double* mean, double* var, double* lpd, double* sum_lpd) 
 // The launches bobe_gp_mll_noise appends to an evaluation with a gradient (eval_enqueue, after everything it queues
 // otherwise): a = diag(K~^-1) from the members' inverse factors into their LOO blocks, then 1/2 nu (sum alpha^2 - sum a) into
 // res[2 + d + 1].  Writes part, the LOO block and that one result: L, Linv, alpha, w stay what bobe_gp_factor adopts.
-void bobe_gp::mll_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev) {
-  const FactorBufs f = ws.bufs();
-  const int64_t rs = ws.stride(128), lvs = ws.stride(ws.lvs());
-  const unsigned nm = (unsigned)B;
-  double* lw = ws.loo.d();
-  hipLaunchKernelGGL(k_loo_colsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream,
-                     (const double*)f.linv, Np, f.part, Np, f.mat, f.prt);
-  hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)f.part, Np,
-                     nb, 1, Np, lw, f.prt, lvs);
-  hipLaunchKernelGGL(k_noise_mll_grad, dim3(1, nm), dim3(256), 0, stream, (const double*)lw, (const double*)f.alpha, N,
-                     hs[0].noise, hdev, ws.res.d() + 2 + d + 1, lvs, f.vec, rs);
+void bobe_gp::mll_noise_tail(const FactorBufs& f, const Hyper* hs, const Hyper* hdev) {
+  loo_kinv_diag(f);
+  hipLaunchKernelGGL(k_noise_mll_grad, dim3(1, (unsigned)f.B), dim3(256), 0, stream, (const double*)f.loo,
+                     (const double*)f.alpha, N, hs[0].noise, hdev, f.res + 2 + d + 1, f.lvs, f.vec, f.rs);
 }
 
 // The launches bobe_gp_loo_objective_noise appends (loo_enqueue, after k_mll_grad_reduce): A holds the dense B = diag(sqrt c)
 // K~^-1, the LOO block w; |B|_F^2 over the true N x N block in two stages through part, then -nu (|B|_F^2 + w^T alpha) into
 // res[2 + d + 1].
-void bobe_gp::loo_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hdev) {
-  const FactorBufs f = ws.bufs();
-  const int64_t rs = ws.stride(128), lvs = ws.stride(ws.lvs());
-  const unsigned nm = (unsigned)B;
+void bobe_gp::loo_noise_tail(const FactorBufs& f, const Hyper* hs, const Hyper* hdev) {
+  const unsigned nm = (unsigned)f.B;
   hipLaunchKernelGGL(k_loo_bsq_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream, (const double*)f.a, Np,
                      N, f.part, Np, f.mat, f.prt);
   hipLaunchKernelGGL(k_noise_loo_grad, dim3(1, nm), dim3(256), 0, stream, (const double*)f.part, Np, nb,
-                     (const double*)(ws.loo.d() + 6 * Np), (const double*)f.alpha, N, hs[0].noise, hdev,
-                     ws.res.d() + 2 + d + 1, f.prt, lvs, f.vec, rs);
+                     (const double*)(f.loo + 6 * Np), (const double*)f.alpha, N, hs[0].noise, hdev, f.res + 2 + d + 1, f.prt,
+                     f.lvs, f.vec, f.rs);
 }
 
 // The launches of B LOO evaluations on ws, on the current stream - eval_enqueue's counterpart: the single evaluation (B = 1,
@@ -103,38 +100,37 @@ void bobe_gp::loo_noise_tail(EvalWs& ws, int B, const Hyper* hs, const Hyper* hd
 // Without a gradient the list stops after the value.  noise_grad (with a gradient only): loo_noise_tail's launches follow.
 // Results land in the pinned ws.h_res[b * 128 + ...].
 void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, const Hyper* hdev, bool noise_grad) {
-  const FactorBufs f = ws.bufs();
-  const int64_t gps = ws.stride(ws.gps()), rs = ws.stride(128), lvs = ws.stride(ws.lvs());
-  double* lw = ws.loo.d();
+  const FactorBufs f = ws.bufs(B);
+  double* lw = f.loo;
   const unsigned nm = (unsigned)B;
   if (hdev) HIPCHK(hipMemcpyAsync(ws.hyp.p, ws.h_hyp, (size_t)B * sizeof(Hyper), hipMemcpyHostToDevice, stream));
-  factor_into(hs[0], f, hdev, B);
-  hipLaunchKernelGGL(k_mll_terms, dim3(nm), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, ws.res.d(),
-                     f.vec, f.mat, rs, (const int*)f.info);
-  loo_terms(f.linv, f.alpha, f.part, lw, want_grad, ws.res.d() + 102, B, f.mat, f.vec, f.prt, lvs, rs);
+  factor_into(hs[0], f, hdev);
+  hipLaunchKernelGGL(k_mll_terms, dim3(nm), dim3(256), 0, stream, (const double*)f.w, (const double*)f.a, Np, Np, f.res, f.vec,
+                     f.mat, f.rs, (const int*)f.info);
+  loo_terms(f, want_grad);
   if (want_grad) {
-    (void)lauum(hs[0], f.linv, f.alpha, f.xst, f.tmp, hdev, ws.gpart.d(), B, f.mat, f.vec, f.xs, gps, nullptr, 0, f.mat);
+    (void)lauum(hs[0], f, hdev, true);
     const int nt32 = (int)(Np / 32);
     hipLaunchKernelGGL(k_loo_make_b, dim3((unsigned)(nt32 * (nt32 + 1) / 2), nm), dim3(256), 0, stream, (const double*)f.tmp, Np,
-                       (const double*)(lw + 4 * Np), f.a, f.mat, lvs);
+                       (const double*)(lw + 4 * Np), f.a, f.mat, f.lvs);
     hipLaunchKernelGGL(k_gemv_t_part, dim3((unsigned)(Np / 64), (unsigned)nb, nm), dim3(256), 0, stream, (const double*)f.a, Np, 0,
-                       (const double*)(lw + 5 * Np), f.part, Np, f.mat, lvs, f.prt);
+                       (const double*)(lw + 5 * Np), f.part, Np, f.mat, f.lvs, f.prt);
     hipLaunchKernelGGL(k_colsum_parts, dim3((unsigned)((Np + 255) / 256), nm), dim3(256), 0, stream, (const double*)f.part, Np,
-                       nb, 0, Np, lw + 6 * Np, f.prt, lvs);
+                       nb, 0, Np, lw + 6 * Np, f.prt, f.lvs);
     const LauumTiling t = lauum_tiling(nb);       // (the dense B^T B on the tiles and the tile core K^-1 was formed on)
     prof_begin(BOBE_PROF_LAUUM);
     with_lauum_variant(hs[0].kern, hs[0].d, t, [&](auto KE, auto DC, auto TT, auto GL) {
       hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(t.ntiles * B), dim3(256),
                          (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)f.a, Np, Np, N,
-                         (const double*)f.alpha, (const double*)(lw + 6 * Np), (const double*)f.xst, Np, hs[0], ws.gpart.d(),
-                         hdev, f.mat, f.vec, lvs, f.xs, gps, B);
+                         (const double*)f.alpha, (const double*)(lw + 6 * Np), (const double*)f.xst, Np, hs[0], f.gpart,
+                         hdev, f.mat, f.vec, f.lvs, f.xs, f.gps, B);
     });
     prof_end(BOBE_PROF_LAUUM);
     // (d + 1 workgroups per member: the gradient components; the scalar terms were reduced above)
-    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1, nm), dim3(256), 0, stream, (const double*)ws.gpart.d(), t.ntiles,
-                       dcap_of(d) + 1, d, dcap_of(d), ws.res.d(), (const double*)nullptr, (const double*)nullptr, Np, Np,
-                       (const int*)nullptr, gps, rs, (int64_t)0, (int64_t)0);
-    if (noise_grad) loo_noise_tail(ws, B, hs, hdev);
+    hipLaunchKernelGGL(k_mll_grad_reduce, dim3(d + 1, nm), dim3(256), 0, stream, (const double*)f.gpart, t.ntiles,
+                       dcap_of(d) + 1, d, dcap_of(d), f.res, (const double*)nullptr, (const double*)nullptr, Np, Np,
+                       (const int*)nullptr, f.gps, f.rs, (int64_t)0, (int64_t)0);
+    if (noise_grad) loo_noise_tail(f, hs, hdev);
   }
   LAUNCH_CHECK();
   HIPCHK(hipMemcpyAsync(ws.h_res, ws.res.p, (size_t)(ws.width > 1 ? B * 128 : 103) * sizeof(double), hipMemcpyDeviceToHost,

@@ -210,7 +210,7 @@ int bobe_gp::posterior_sample(const double* Xq, int64_t C, int64_t S, uint64_t s
                            (const double*)sig.d(), C, C, jit, c.A.d(), Cp, Cp);
         HIPCHK(hipMemsetAsync(c.info.p, 0x7f, sizeof(int), stream));
         prof_begin(BOBE_PROF_POTF2);
-        c.potrf(c.A.d(), c.Linv.d(), static_cast<int*>(c.info.p));
+        c.potrf(c.state_bufs());
         prof_end(BOBE_PROF_POTF2);
         hipLaunchKernelGGL(k_mll_terms, dim3(1), dim3(256), 0, stream, (const double*)nullptr, (const double*)c.A.d(), Cp, Cp,
                            c.res.d(), (int64_t)0, (int64_t)0, (int64_t)0, (const int*)c.info.p);

@@ -4,6 +4,8 @@ prints one JSON line:
   bad_lead / bad_trail   a lock-step batch of three whose middle member is not positive definite, the failing pivot in the
                          leading / the trailing half of the factor
   repeat                 four batch evaluations at different theta, then the first again
+  interleave             the entry points that share a handle's own workspace and its installed factor, one after the other
+                         on one handle, against each of them alone on a fresh handle (N = 300, d = 3 and N = 641, d = 5)
   lifetime               twenty create / evaluate / destroy rounds and the device memory they leave behind"""
 import ctypes as C
 import gc
@@ -92,9 +94,76 @@ def lifetime_case():
     return int(free0 - torch.cuda.mem_get_info(0)[0])
 
 
+def interleave_case(n, d, kern):
+    """Nine calls in sequence on ONE handle - they share its own evaluation workspace and the installed factor - and each
+    of them again alone on a fresh handle (`single`); the two free functions also by the binding's own route, a data-less
+    handle per call (`free`).  A step is (name, call(gp) -> arrays); the saved factor and the matrices are made up front."""
+    from bobe_amd.gp import fast_update_cholesky, gp_mll
+    rng = np.random.default_rng(100 + n)
+    X = rng.uniform(size=(n, d))
+    y = np.sin(X.sum(1)) + 0.1 * rng.normal(size=n)
+    xq = rng.uniform(size=(200, d))
+    kvec = 0.5 * np.exp(-np.sum((X - 0.5) ** 2, axis=1))
+
+    def fresh():
+        return GP(X, y, noise=1e-5, kernel=kern, lengthscales=np.full(d, 0.5))
+
+    saved = fresh()
+    L, alpha = np.array(saved.cholesky), np.array(saved.alphas).reshape(-1)
+    K, ys = L @ L.T, np.array(saved.train_y).reshape(-1)
+    ls1, ls4 = np.full(d, 0.45), np.full((4, d), 0.4) + 0.03 * np.arange(4)[:, None]
+
+    # the free functions' entry points on g's handle (a handle with data takes matrices of its data's size)
+    def row_update(g):
+        v, diag = np.empty(n), C.c_double(0.0)
+        _lib.check(g._lib.bobe_gp_chol_row_update(g._h, _lib.ptr(L), n, _lib.ptr(kvec), 2.0, _lib.ptr(v), C.byref(diag)),
+                   "bobe_gp_chol_row_update")
+        return v, diag.value
+
+    def mll_of_k(g):
+        mll = C.c_double(0.0)
+        _lib.check(g._lib.bobe_gp_mll_from_k(g._h, _lib.ptr(K), n, _lib.ptr(ys), C.byref(mll)), "bobe_gp_mll_from_k")
+        return (mll.value,)
+
+    def restore(g):
+        _lib.check(g._lib.bobe_gp_set_chol(g._h, _lib.ptr(L), _lib.ptr(alpha)), "bobe_gp_set_chol")
+        g._chol_cache = g._alpha_cache = None
+        return (g.cholesky, g.alphas) + g.predict_batched(xq)
+
+    def refit(g):
+        g.recompute_cholesky()
+        return (g.cholesky, g.alphas) + g.predict_batched(xq)
+
+    def loo(g):
+        r = g.loo()
+        return r["mean"], r["var"], r["lpd"], r["elpd"]
+
+    steps = [("mll_data", lambda g: g.mll_data(ls1, 1.3)),
+             ("fast_update_cholesky", row_update),
+             ("gp_mll", mll_of_k),
+             ("set_chol", restore),
+             ("refit", refit),
+             ("loo", loo),
+             ("mll_data_batch", lambda g: g.mll_data_batch(ls4, np.ones(4))),
+             ("sample_posterior", lambda g: (g.sample_posterior(xq, n_samples=3, seed=20240),)),
+             ("mll_data again", lambda g: g.mll_data(ls1, 1.3))]
+
+    def digest(arrays):
+        flat = np.concatenate([np.ravel(np.asarray(a, dtype=np.float64)) for a in arrays])
+        return {"hex": hexes(flat), "finite": bool(np.all(np.isfinite(flat)))}
+
+    gp = fresh()
+    shared = [digest(call(gp)) for _, call in steps]
+    single = [digest(call(fresh())) for _, call in steps]
+    new_row = fast_update_cholesky(L, kvec, 2.0)[n]          # the binding's own route: a data-less handle per call
+    free = [digest((new_row[:n], new_row[n])), digest((gp_mll(K, ys, n),))]
+    return {"steps": [name for name, _ in steps], "shared": shared, "single": single, "free": free}
+
+
 if __name__ == "__main__":
     out = {"bad_lead": bad_member_case(np.arange(40, 100), np.arange(0, 60)),
            "bad_trail": bad_member_case(np.arange(200, 300), np.arange(0, 100)),
            "repeat": repeat_case(),
+           "interleave": [interleave_case(300, 3, "matern"), interleave_case(641, 5, "rbf")],
            "lifetime": lifetime_case()}
     print(json.dumps(out))

@@ -74,6 +74,20 @@ def test_consecutive_evaluations_keep_their_bits(forced):
     assert calls[4] == calls[0]                       # (a missing join shows as a changed Tmp / Linv)
 
 
+@pytest.mark.parametrize("which", [0, 1])
+def test_entry_points_sharing_a_handle_keep_their_bits(forced, which):
+    """What the factorisation hands to the inverse travels by value: no entry point finds what another one left on the
+    handle's own workspace.  N = 300, d = 3 (three block columns, ragged) and N = 641, d = 5, the fork forced."""
+    r = forced["interleave"][which]
+    assert r["steps"] == ["mll_data", "fast_update_cholesky", "gp_mll", "set_chol", "refit", "loo", "mll_data_batch",
+                          "sample_posterior", "mll_data again"]
+    assert all(s["finite"] for s in r["shared"] + r["single"] + r["free"]), r["steps"]
+    differing = [name for name, a, b in zip(r["steps"], r["shared"], r["single"]) if a["hex"] != b["hex"]]
+    assert not differing, differing                    # each call: the bits it has alone on a fresh handle
+    assert [s["hex"] for s in r["shared"][1:3]] == [s["hex"] for s in r["free"]]      # ... and on a data-less one
+    assert r["shared"][8]["hex"] == r["shared"][0]["hex"]                             # the last mll_data equals the first
+
+
 def test_handles_return_the_side_stream(forced):
     # one leaked N x N buffer per handle would be 20 x 1.2 MB; the allowance is the allocator's granularity
     assert forced["lifetime"] < 4 << 20, f"{forced['lifetime'] / 2 ** 20:.1f} MiB over twenty handles"
