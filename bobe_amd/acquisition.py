@@ -291,7 +291,11 @@ class PathwiseTS(AcquisitionFunction):
     of ``mc_samples['x']`` (the choice of ``batch_mode='sweep'``).  ``acq_kwargs['ts_mode']``: 'max' (default), classic
     Thompson sampling, or 'posterior': a Gumbel-max draw from the pool reweighted from exp(mean) to exp(f_s) - the bias
     handed to the argmax is Gumbel noise minus the surrogate mean.  ``acq_kwargs['ts_features']``: random Fourier features
-    per path (2048).  The paths are seeded by one ``rng.integers`` draw.  Values: the paths at their picks."""
+    per path (2048).  The paths are seeded by one ``rng.integers`` draw.  Values: the paths at their picks.
+    ``acq_kwargs['ts_polish'] = R`` (default 0: the pool picks above, bit for bit) carries the argmax to the continuum: member
+    s starts from the R best pool rows of path s and takes the maximum of its path over the unit cube
+    (``PosteriorPaths.maximize``, at most ``acq_kwargs['ts_polish_maxiter']`` = 100 L-BFGS-B iterations; ``_polished_batch``
+    has the replacement rule); it needs ``ts_mode='max'`` and draws the same numbers from ``rng``."""
 
     name: str = "PathwiseTS"
 
@@ -307,6 +311,7 @@ class PathwiseTS(AcquisitionFunction):
         mode = acq_kwargs.get("ts_mode", "max")
         if mode not in ("max", "posterior"):
             raise ValueError(f"ts_mode must be 'max' or 'posterior', not {mode!r}")
+        polish = _ts_polish(acq_kwargs, mode)
         pool = acq_kwargs.get("candidates")
         if pool is None:
             pool = acq_kwargs["mc_samples"]["x"]
@@ -323,6 +328,9 @@ class PathwiseTS(AcquisitionFunction):
             mean, _ = gp._predict(pool_host, True, False, 0)
             bias = rng.gumbel(size=(n_batch, n_pool)) / gp.y_std - mean[None, :]
         with gp.sample_paths(n_batch, int(acq_kwargs.get("ts_features", 2048)), seed=seed) as paths:
+            if polish > 0:
+                return self._polished_batch(gp, paths, pool, pool_host, n_batch, polish,
+                                            int(acq_kwargs.get("ts_polish_maxiter", 100)))
             picks, vals = paths.argmax(pool, bias)
             taken = set()
             for s in range(n_batch):
@@ -335,6 +343,59 @@ class PathwiseTS(AcquisitionFunction):
                     vals[s] = paths.y_mean + paths.y_std * row[picks[s]]
                 taken.add(int(picks[s]))
         return np.array(pool_host[picks]), np.array(vals)
+
+    @staticmethod
+    def _polished_batch(gp, paths, pool, pool_host, n_batch, n_starts, maxiter):
+        """``ts_polish`` = R > 0: member s starts from the R best pool rows of path s (ties: the lower index) and takes the
+        maximum of its path over the unit cube (``PosteriorPaths.maximize``).  A polished point within 1e-12 (max-norm) of an
+        earlier member's pick, or infeasible under the GP's gate, is replaced by the path's next-best admissible restart
+        result, then by its pool pick: the best pool row no earlier member took (feasible, where the gate leaves one)."""
+        fpool = paths.evaluate(pool)                                             # (S, C), physical units
+        order = np.argsort(-fpool, axis=1, kind="stable")                        # descending, ties by the lower index
+        r = min(int(n_starts), pool_host.shape[0])
+        res = paths.maximize(pool_host[order[:, :r]], bounds=(0.0, 1.0), maxiter=maxiter)
+        gated = bool(getattr(gp, "_gated", lambda: False)())
+
+        def feasible(x):
+            if not gated:
+                return np.ones(len(x), dtype=bool)
+            from .clf import gate_eval
+            return gate_eval(gp._lib, gp._h, x, gp.ndim)[1] > 0.0
+
+        pts, vals, taken = [], [], set()
+
+        def admissible(x):
+            return all(np.max(np.abs(x - q)) > _TS_DUPLICATE_TOL for q in pts) and bool(feasible(x[None, :])[0])
+
+        for s in range(n_batch):
+            ranked = [k for k in np.argsort(-res["restart_value"][s], kind="stable") if np.isfinite(res["restart_value"][s, k])]
+            cands = [(res["x"][s], res["value"][s])] + [(res["restart_x"][s, k], res["restart_value"][s, k]) for k in ranked]
+            pick = next(((x, v) for x, v in cands if admissible(x)), None)
+            if pick is None:
+                free = [int(c) for c in order[s] if int(c) not in taken]
+                ok = feasible(pool_host[free])
+                row = next((c for c, f in zip(free, ok) if f), free[0])
+                taken.add(row)
+                pick = (pool_host[row], fpool[s, row])
+            else:
+                hit = np.flatnonzero(np.all(pool_host == pick[0], axis=1))        # (a start that won is a pool row)
+                taken.update(int(c) for c in hit)
+            pts.append(np.array(pick[0]))
+            vals.append(float(pick[1]))
+        return np.array(pts), np.array(vals)
+
+
+_TS_DUPLICATE_TOL = 1e-12       # max-norm distance below which a polished Thompson pick counts as an earlier member's
+
+
+def _ts_polish(acq_kwargs, mode) -> int:
+    """``acq_kwargs['ts_polish']``: restarts of the L-BFGS-B polish per path, 0 (default) = none"""
+    r = acq_kwargs.get("ts_polish", 0)
+    if isinstance(r, bool) or int(r) != r or int(r) < 0:
+        raise ValueError(f"ts_polish must be a non-negative integer, not {r!r}")
+    if int(r) > 0 and mode == "posterior":
+        raise ValueError("ts_polish needs ts_mode='max': a Gumbel-max draw from a pool has no continuum form")
+    return int(r)
 
 
 def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, method="NUTS", num_chains=4,

@@ -210,6 +210,7 @@ class BOBE:
         self.num_mc_samples, self.acq_threshold, self.verbose, self.mc_sampler = 1024, None, False, "hmc"
         self.wip_batch_mode = "believer"
         self.mc_weighted = False
+        self.ts_polish = 0
         self.min_delta_seen = np.inf
         self.current_iteration = 0
         self.start_iteration = 0
@@ -580,7 +581,7 @@ class BOBE:
             num_chains: int = 4, mc_points_method: str = "NUTS", zeta_ei: float = 0.01, *,
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
             mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
-            wip_batch_mode: str = "believer") -> dict:
+            ts_polish: int = 0, wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
@@ -594,7 +595,10 @@ class BOBE:
         the run's generator and the checkpoint files as they were), and ``mc_weighted`` - meant for ``mc_points_method='NS'``:
         True (refused with any other method) keeps the nested samples' weights and integrates over the heaviest ``mc_points_size`` of them with their
         log-weights (``get_mc_points(weighted=True)``, ``acq_kwargs['mc_log_weights']``) instead of equal-weight draws; the
-        default changes nothing.  ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
+        default changes nothing, and ``ts_polish`` - for ``acq='ts'``: R > 0 hands ``acq_kwargs['ts_polish'] = R`` to
+        ``PathwiseTS``, which then maximises every path over the unit cube by L-BFGS-B from its R best pool rows
+        (``PosteriorPaths.maximize``); 0 (default): the pool picks, and an ``acq_kwargs`` without the key.
+        ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
         samples.  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
@@ -628,6 +632,9 @@ class BOBE:
         if mc_weighted and mc_points_method != "NS":
             raise ValueError(f"mc_weighted=True needs mc_points_method='NS' (weighted nested samples), not {mc_points_method!r}")
         self.mc_weighted = bool(mc_weighted)
+        if isinstance(ts_polish, bool) or int(ts_polish) != ts_polish or int(ts_polish) < 0:
+            raise ValueError(f"ts_polish must be a non-negative integer, not {ts_polish!r}")
+        self.ts_polish = int(ts_polish)
         self.loo_diagnostics, self.loo_history = bool(loo_diagnostics), []
         self.converged, self.convergence_counter = False, 0
         self.min_delta_seen = np.inf
@@ -770,6 +777,8 @@ class BOBE:
             if self.verbose:
                 log.info(f"Iteration {ii} of {acq_name}, objective evals {current_evals}/{self.max_evals}")
             acq_kwargs = {"mc_samples": self.mc_samples, "mc_points_size": self.mc_points_size}
+            if self.ts_polish > 0:
+                acq_kwargs["ts_polish"] = self.ts_polish
             if self.mc_weighted and self.mc_samples.get("weights") is not None:
                 acq_kwargs["mc_points"], acq_kwargs["mc_log_weights"] = get_mc_points(
                     self.mc_samples, mc_points_size=self.mc_points_size, weighted=True)

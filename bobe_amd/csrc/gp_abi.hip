@@ -428,6 +428,14 @@ int bobe_gp_paths_argmax(bobe_paths_t* p, const double* Xq, int64_t C, const dou
   API_END
 }
 
+int bobe_gp_paths_grad(bobe_paths_t* p, const double* Xq, int64_t T, const int64_t* path_idx, int centered, double* f,
+                       double* df) {
+  API_BEGIN
+  NEED(p && Xq && path_idx, "NULL argument");
+  return paths_grad(*p, Xq, T, path_idx, centered, f, df);
+  API_END
+}
+
 void bobe_gp_paths_destroy(bobe_paths_t* p) { paths_destroy(p); }
 
 int bobe_gp_wip_grad(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,

@@ -737,5 +737,6 @@ int paths_create(bobe_gp& g, int64_t S, int64_t F, uint64_t seed, const double* 
 int paths_get(bobe_paths& p, double* u, double* phase, double* w, double* eps);
 int paths_eval(bobe_paths& p, const double* Xq, int64_t C, int centered, double* f);
 int paths_argmax(bobe_paths& p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best);
+int paths_grad(bobe_paths& p, const double* Xq, int64_t T, const int64_t* path_idx, int centered, double* f, double* df);
 void paths_destroy(bobe_paths* p);
 }  // namespace bobe

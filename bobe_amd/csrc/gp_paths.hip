@@ -4,7 +4,8 @@
 // A path set is a SNAPSHOT of the handle's factorised state: it owns the scaled training coordinates, alpha, the
 // hyper-parameters, the frequencies / phases / weights and V_c = -K^-1 (Phi(X) W^T + E^T); the parent's factor is read while
 // the set is created and never again.  The parent's stream, chunk and launch helpers are used by every call, so the set is
-// destroyed before its parent.  Kernels: paths_kernels.hpp.  Every call-scoped buffer is a CallBuf.
+// destroyed before its parent.  Kernels: paths_kernels.hpp.  Every call-scoped buffer is a CallBuf.  paths_grad (value and
+// input gradient of one path per point, k_paths_grad) adds one lazily built member, the transposed coefficients VcT.
 #include "gp_handle.hpp"
 
 #include "paths_kernels.hpp"
@@ -21,8 +22,10 @@ struct bobe_paths {
   // XsT [d x Np], alpha [Np]: copies of the parent's; U [F x d], B [F], W [S x F], E [S x N]: the set's random arrays, dense;
   // VW [(Np + Fp) x Sp]: V_c over W^T, the B operand of the evaluation product
   DBuf XsT, alpha, U, B, W, E, VW;
+  // VcT [S x Np]: V_c transposed, a path's coefficients as a contiguous row; built by the first paths_grad call
+  DBuf VcT;
   void release() {
-    for (DBuf* b : {&XsT, &alpha, &U, &B, &W, &E, &VW}) b->release();
+    for (DBuf* b : {&XsT, &alpha, &U, &B, &W, &E, &VW, &VcT}) b->release();
   }
 };
 
@@ -294,6 +297,54 @@ int paths_argmax(bobe_paths& p, const double* Xq, int64_t C, const double* bias,
   HIPCHK(hipMemcpyAsync(idx, d_idx, (size_t)p.S * sizeof(int64_t),
                         is_device_ptr(idx) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g.stream));
   g.sync();
+  return BOBE_OK;
+}
+
+int paths_grad(bobe_paths& p, const double* Xq, int64_t T, const int64_t* path_idx, int centered, double* f, double* df) {
+  if (T < 1) throw Err(BOBE_ERR_ARG, "T must be positive");
+  if (!f && !df) throw Err(BOBE_ERR_ARG, "f and df are both NULL");
+  if (is_device_ptr(path_idx)) throw Err(BOBE_ERR_ARG, "path_idx must be host memory");
+  for (int64_t t = 0; t < T; ++t)
+    if (path_idx[t] < 0 || path_idx[t] >= p.S) throw Err(BOBE_ERR_ARG, "path_idx out of range");
+  bobe_gp& g = *p.g;
+  g.use();
+  const int d = p.d;
+  if (!p.VcT.p) {
+    p.VcT.ensure((size_t)p.S * p.Np * sizeof(double));
+    hipLaunchKernelGGL(k_paths_transpose_vc, dim3((unsigned)p.S, (unsigned)((p.Np + 255) / 256)), dim3(256), 0, g.stream,
+                       (const double*)p.VW.d(), p.Sp, p.Np, p.VcT.d(), p.Np);
+    LAUNCH_CHECK();
+  }
+  CallBuf xin, idx, fout, dout;
+  const double* xq = Xq;
+  if (!is_device_ptr(Xq)) {
+    xin.ensure((size_t)T * d * sizeof(double));
+    HIPCHK(hipMemcpyAsync(xin.p, Xq, (size_t)T * d * sizeof(double), hipMemcpyHostToDevice, g.stream));
+    xq = xin.d();
+  }
+  idx.ensure((size_t)T * sizeof(int64_t));
+  HIPCHK(hipMemcpyAsync(idx.p, path_idx, (size_t)T * sizeof(int64_t), hipMemcpyHostToDevice, g.stream));
+  double* fd = f;
+  double* dd = df;
+  if (f && !is_device_ptr(f)) {
+    fout.ensure((size_t)T * sizeof(double));
+    fd = fout.d();
+  }
+  if (df && !is_device_ptr(df)) {
+    dout.ensure((size_t)T * d * sizeof(double));
+    dd = dout.d();
+  }
+  const double amp = std::sqrt(2.0 * p.hyp.kvar / (double)p.F);
+  with_kern_dcap(p.hyp.kern, d, [&](auto KE, auto DC) {
+    hipLaunchKernelGGL((k_paths_grad<KE, DC>), dim3((unsigned)T), dim3(256), 0, g.stream, (const double*)p.XsT.d(), p.Np,
+                       p.N, p.hyp, (const double*)p.alpha.d(), (const double*)p.VcT.d(), p.Np, (const double*)p.U.d(),
+                       (const double*)p.B.d(), (const double*)p.W.d(), p.F, amp, xq, (const int64_t*)idx.p,
+                       centered != 0 ? 1 : 0, fd, dd);
+  });
+  LAUNCH_CHECK();
+  if (fd != f) HIPCHK(hipMemcpyAsync(f, fd, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (dd != df) HIPCHK(hipMemcpyAsync(df, dd, (size_t)T * d * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  g.sync();     // (the call's buffers are freed on return)
   return BOBE_OK;
 }
 

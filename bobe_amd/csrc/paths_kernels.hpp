@@ -254,4 +254,104 @@ __global__ void k_paths_argmax_arm(double* __restrict__ best, int64_t* __restric
   idx[s] = 0;
 }
 
+// ---- value and input gradient of one path per query point (bobe_gp_paths_grad) -------------------------------------------------
+// VcT[s * ldt + n] = VW[n * ldv + s] for s < S, n < Np: a path's coefficients as one contiguous row.  Built once per set, at
+// its first gradient call.  grid (S, ceil(Np / 256))
+__global__ void k_paths_transpose_vc(const double* __restrict__ VW, int64_t ldv, int64_t Np, double* __restrict__ VcT,
+                                     int64_t ldt) {
+  const int64_t n = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+  const int64_t s = blockIdx.x;
+  if (n >= Np) return;
+  VcT[s * ldt + n] = VW[n * ldv + s];
+}
+
+// With xs = x / ls, c_n = VcT[s][n] + alpha[n] (centred: VcT[s][n] alone), amp = sqrt(2 kvar / F), arg_j = u_j . xs + b_j:
+//   f[t]      = sum_n c_n k(r2_n) + amp sum_j w_sj cos(arg_j)
+//   df[t][k]  = (1 / ls_k) [ sum_n c_n G(r2_n) (xs_nk - xs_k) - amp sum_j w_sj sin(arg_j) u_jk ],   G = kern_grad_factor
+// for the point x = Xq[t] and the path s = pidx[t] (a wave-uniform load).  One 256-thread workgroup per point.  Thread tau
+// adds the kernel terms n = tau, tau + 256, ... < N and then the feature terms j = tau, tau + 256, ... < F, each in
+// ascending order, into ONE set of 1 + d accumulators (the feature terms enter as (amp w_sj) cos and -(amp w_sj) sin u_jk).
+// The training coordinates come from XsT (coalesced); the argument is reduced as in k_paths_features, t = arg / 2 pi -
+// rint(arg / 2 pi), and the pair taken as sincospi(2 t): no large-argument path, no scratch.  The 256 partials of every
+// component are added in one fixed tree: chain_wave_sum (f) and wave_sum_components (the DCAP gradient components) within a
+// wave, then the four waves through LDS as ((w0 + w1) + w2) + w3; the division by ls_k happens once, at the store.  No
+// atomics: the bits of (f, df) at a point depend on the set, the point, its path and the centred flag alone - not on T, the
+// other points of the call or the pointer kinds.  f or df may be NULL (nothing else changes).
+// The set is read again by every workgroup (L2-resident at the sizes of a polish: tens to thousands of points).
+// Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950), rbf / matern: DCAP 8: 94 / 117 VGPRs (5 / 4 waves per
+// SIMD), DCAP 16: 166 / 166 (3), DCAP 32: 241 / 246 (2); no AGPRs, scratch 0 in all six, LDS 4 * (DCAP + 1) doubles.
+template <int KERN, int DCAP>
+__global__ __launch_bounds__(256) void k_paths_grad(const double* __restrict__ XsT, int64_t ldx, int64_t N, Hyper h,
+                                                    const double* __restrict__ alpha, const double* __restrict__ VcT,
+                                                    int64_t ldt, const double* __restrict__ U,
+                                                    const double* __restrict__ phase, const double* __restrict__ W,
+                                                    int64_t F, double amp, const double* __restrict__ Xq,
+                                                    const int64_t* __restrict__ pidx, int centered,
+                                                    double* __restrict__ f, double* __restrict__ df) {
+  __shared__ double red[4][DCAP + 1];
+  const int tau = threadIdx.x, lane = tau & 63, wave = tau >> 6;
+  const int64_t t = blockIdx.x;
+  const int64_t s = pidx[t];
+  const int d = h.d;
+  double xs[DCAP], acc[DCAP], v[DCAP];
+  double af = 0.0;
+  // (constant indices into h.ls: a runtime index would send the by-value struct through scratch memory)
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    xs[k] = (k < d) ? Xq[t * d + k] / h.ls[k] : 0.0;
+    acc[k] = 0.0;
+  }
+  const double* vc = VcT + s * ldt;
+  for (int64_t n = tau; n < N; n += 256) {
+    double r2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) {
+      v[k] = (k < d) ? XsT[(int64_t)k * ldx + n] - xs[k] : 0.0;
+      r2 = __builtin_fma(v[k], v[k], r2);
+    }
+    const double c = centered ? vc[n] : vc[n] + alpha[n];
+    const double kv = kern_eval<KERN>(r2, h.kvar);
+    const double cg = c * kern_grad_factor<KERN>(r2, h.kvar, kv);
+    af = __builtin_fma(c, kv, af);
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) acc[k] = __builtin_fma(cg, v[k], acc[k]);
+  }
+  const double* ws = W + s * F;
+  for (int64_t j = tau; j < F; j += 256) {
+    const double* uj = U + j * d;
+    double arg = phase[j];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) {
+      v[k] = (k < d) ? uj[k] : 0.0;
+      arg = __builtin_fma(v[k], xs[k], arg);
+    }
+    double tt = arg * PATHS_INV_TWO_PI;
+    tt -= rint(tt);
+    double sn, cs;
+    sincospi(2.0 * tt, &sn, &cs);
+    const double wa = amp * ws[j];
+    af = __builtin_fma(wa, cs, af);
+    const double ms = -(wa * sn);
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) acc[k] = __builtin_fma(ms, v[k], acc[k]);
+  }
+  // the wave's sums: f in every lane, gradient component (lane >> SH) in the lanes of its group
+  constexpr int SH = DCAP == 8 ? 3 : (DCAP == 16 ? 2 : 1);
+  af = chain_wave_sum(af);
+  const double gk = wave_sum_components<DCAP>(acc, lane);
+  if ((lane & ((1 << SH) - 1)) == 0) red[wave][lane >> SH] = gk;
+  if (lane == 0) red[wave][DCAP] = af;
+  __syncthreads();
+  if (tau < d) {
+    if (df) {
+      double lk = h.ls[0];
+#pragma unroll
+      for (int k = 1; k < DCAP; ++k) lk = (tau == k) ? h.ls[k] : lk;
+      df[t * d + tau] = (((red[0][tau] + red[1][tau]) + red[2][tau]) + red[3][tau]) / lk;
+    }
+  } else if (tau == 64) {
+    if (f) f[t] = ((red[0][DCAP] + red[1][DCAP]) + red[2][DCAP]) + red[3][DCAP];
+  }
+}
+
 }  // namespace bobe

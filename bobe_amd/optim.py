@@ -63,8 +63,9 @@ class _LockStep:
     have seen alone; the rounds are deterministic, and ``batch_fun`` is only ever called from one thread at a time.
     """
 
-    def __init__(self, batch_fun: Callable, n_workers: int):
-        self.batch_fun = batch_fun
+    def __init__(self, batch_fun: Callable, n_workers: int, with_ids: bool = False):
+        # (with_ids: batch_fun(ids, xs) is told which minimisations the points belong to)
+        self.batch_fun = batch_fun if with_ids else (lambda ids, xs: batch_fun(xs))
         self.cv = threading.Condition()
         self.active = n_workers
         self.pending = {}          # worker -> x
@@ -75,13 +76,13 @@ class _LockStep:
         xs = [self.pending[i] for i in ids]
         self.pending = {}
         try:
-            out = self.batch_fun(xs)
+            out = self.batch_fun(ids, xs)
             for i, r in zip(ids, out):
                 self.results[i] = r
         except Exception:               # narrowed down point by point: only the minimisation whose point raises gets it
             for i, x in zip(ids, xs):
                 try:
-                    self.results[i] = self.batch_fun([x])[0]
+                    self.results[i] = self.batch_fun([i], [x])[0]
                 except Exception as e:
                     self.results[i] = e
         self.cv.notify_all()
@@ -105,16 +106,18 @@ class _LockStep:
                 self._flush_locked()
 
 
-def _minimize_concurrently(batch_fun: Callable, starts: np.ndarray, has_grad: bool, **kw) -> List:
+def _minimize_concurrently(batch_fun: Callable, starts: np.ndarray, has_grad: bool, *, with_ids: bool = False,
+                           **kw) -> List:
     """``scipy.optimize.minimize`` from every row of ``starts``; returns the results (or the exception) per row.
-    L-BFGS-B with gradients is stepped by one thread (``_rc_minimize_all``) where that is available."""
+    L-BFGS-B with gradients is stepped by one thread (``_rc_minimize_all``) where that is available.  ``with_ids``:
+    ``batch_fun(ids, xs)`` also receives the rows of ``starts`` the points belong to (objectives that differ per row)."""
     known = {"maxcor", "ftol", "gtol", "maxfun", "maxiter", "maxls"}
     if has_grad and kw.get("method", "L-BFGS-B") == "L-BFGS-B" and set(kw.get("options") or {}) <= known and _rc_available():
         try:
-            return _rc_minimize_all(batch_fun, starts, kw.get("bounds"), dict(kw.get("options") or {}))
+            return _rc_minimize_all(batch_fun, starts, kw.get("bounds"), dict(kw.get("options") or {}), with_ids=with_ids)
         except Exception as e:  # pragma: no cover
             log.warning(f"stepped L-BFGS-B driver failed with {e}; running the restarts in threads")
-    ls = _LockStep(batch_fun, len(starts))
+    ls = _LockStep(batch_fun, len(starts), with_ids)
     out: List = [None] * len(starts)
 
     def work(i):
@@ -233,11 +236,12 @@ class _RcRun:
                               message=msg, x=self.x, success=(warnflag == 0))
 
 
-def _rc_minimize_all(batch_fun: Callable, starts, bounds, options) -> List:
+def _rc_minimize_all(batch_fun: Callable, starts, bounds, options, *, with_ids: bool = False) -> List:
     """Every restart stepped by this thread; returns an OptimizeResult - or the exception that ended it - per restart.
     An exception out of ``batch_fun`` is narrowed down by evaluating that round's points one by one: only the restart
     whose point raises ends with it (what ``_LockStep`` / one ``minimize`` per thread would do), the others go on."""
     from scipy.optimize import _lbfgsb
+    call = batch_fun if with_ids else (lambda ids, xs: batch_fun(xs))      # (with_ids: the restarts the points belong to)
     runs = [_RcRun(_lbfgsb, x0, bounds, **options) for x0 in starts]
     failed: dict = {}
     waiting = [i for i, r in enumerate(runs) if r.advance()]
@@ -245,12 +249,12 @@ def _rc_minimize_all(batch_fun: Callable, starts, bounds, options) -> List:
         # (ScalarFunction hands the objective a copy of x and stores float(f): the values the routine sees are the same)
         pts = [np.array(runs[i].x) for i in waiting]
         try:
-            vals = batch_fun(pts)
+            vals = call(list(waiting), pts)
         except Exception:
             vals = []
-            for x in pts:
+            for i, x in zip(waiting, pts):
                 try:
-                    vals.append(batch_fun([x])[0])
+                    vals.append(call([i], [x])[0])
                 except Exception as e:
                     vals.append(e)
         nxt = []

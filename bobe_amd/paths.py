@@ -1,6 +1,6 @@
 """``PosteriorPaths`` - a set of pathwise posterior draws of a ``GP``'s latent surrogate (``bobe_gp_paths_*``,
 include/bobe_gp.h): functions that can be evaluated at any points, maximised over a pool or added to a sampler's log
-likelihoods.  Created by ``GP.sample_paths``."""
+likelihoods, differentiated with respect to the input and maximised over the cube.  Created by ``GP.sample_paths``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,6 +9,69 @@ import weakref
 import numpy as np
 
 from . import _lib
+
+
+def maximize_paths(batch_value_and_grad, starts, bounds=(0.0, 1.0), maxiter=100, options=None) -> dict:
+    """SciPy's L-BFGS-B on -f_s from every start, all S * R runs in lock step (the drivers of optim.py: the stepped one where it
+    is available, one ``minimize`` per thread otherwise).  ``starts``: (S, R, d), run (s, r) maximises path s.
+    ``batch_value_and_grad(x (T, d), path_index (T,)) -> (f (T,), df (T, d))`` serves one round: the points of the runs still
+    waiting, in run order - ONE call per round.  ``options``: L-BFGS-B options (SciPy's defaults; ``maxiter`` is set from the
+    argument).
+
+    Selection, per path: the largest value among the results of the restarts that finished and the (clipped) starts
+    themselves, the values of the starts being those of the first round; ties go to the lower restart, then to the lower
+    start; a restart that raised or ended on a non-finite value is skipped - so a path's result is never below its best
+    start.  Returns ``x`` (S, d), ``value`` (S,), ``start_value`` (S,), ``restart`` (S,) (-1: a start won), ``n_rounds``,
+    ``n_evaluations``, and the material of the selection: ``restart_x`` (S, R, d) / ``restart_value`` (S, R) (-inf: skipped)
+    and ``start_x`` (S, R, d) / ``start_values`` (S, R) (-inf: the start's evaluation raised or was not finite)."""
+    from .optim import _minimize_concurrently, _setup_bounds
+    starts = np.array(starts, dtype=np.float64)
+    if starts.ndim != 3:
+        raise ValueError(f"starts must have shape (S, R, d), not {starts.shape}")
+    S, R, d = starts.shape
+    b = _setup_bounds(bounds, d)
+    scipy_bounds = None if b is None else [(float(b[0, i]), float(b[1, i])) for i in range(d)]
+    opts = dict(options or {})
+    opts["maxiter"] = int(maxiter)
+    count = {"rounds": 0, "evals": 0}
+    start_x = np.array(starts.reshape(S * R, d) if b is None else np.clip(starts.reshape(S * R, d), b[0], b[1]))
+    start_values = np.full(S * R, -np.inf)
+    seen = np.zeros(S * R, dtype=bool)
+
+    def batch(ids, xs):
+        ids = np.asarray(ids, dtype=np.int64)
+        count["rounds"] += 1
+        count["evals"] += len(ids)
+        f, g = batch_value_and_grad(np.array(xs, dtype=np.float64).reshape(len(ids), d), ids // R)
+        f, g = np.asarray(f, dtype=np.float64).reshape(-1), np.asarray(g, dtype=np.float64).reshape(len(ids), d)
+        for i, fi in zip(ids, f):                  # a run's first evaluation is at its start
+            if not seen[i]:
+                seen[i] = True
+                if np.isfinite(fi):
+                    start_values[i] = fi
+        return [(-float(fi), -gi) for fi, gi in zip(f, g)]
+
+    results = _minimize_concurrently(batch, start_x, True, with_ids=True, method="L-BFGS-B", bounds=scipy_bounds,
+                                     options=opts)
+    restart_x = np.array(start_x).reshape(S, R, d)
+    restart_value = np.full((S, R), -np.inf)
+    for i, res in enumerate(results):
+        if isinstance(res, Exception) or res is None or not np.isfinite(res.fun):
+            continue
+        restart_x[i // R, i % R] = res.x
+        restart_value[i // R, i % R] = -float(res.fun)
+    start_x, start_values = start_x.reshape(S, R, d), start_values.reshape(S, R)
+    x, value, which = np.empty((S, d)), np.empty(S), np.empty(S, dtype=np.int64)
+    for s in range(S):
+        # (np.argmax keeps the first of equal values: restarts in order, then the starts in order)
+        both = np.concatenate([restart_value[s], start_values[s]])
+        k = int(np.argmax(both))
+        value[s] = both[k]
+        which[s] = k if k < R else -1
+        x[s] = restart_x[s, k] if k < R else start_x[s, k - R]
+    return {"x": x, "value": value, "start_value": start_values.max(axis=1), "restart": which,
+            "n_rounds": count["rounds"], "n_evaluations": count["evals"], "restart_x": restart_x,
+            "restart_value": restart_value, "start_x": start_x, "start_values": start_values}
 
 
 def _destroy(lib, handle: C.c_void_p) -> None:
@@ -83,6 +146,38 @@ class PosteriorPaths:
         _lib.check(self._lib.bobe_gp_paths_eval(self._handle(), _lib.ptr(x), c, 1 if centered else 0, _lib.ptr(out)),
                    "bobe_gp_paths_eval")
         return self.y_std * out if centered else self.y_mean + self.y_std * out
+
+    def _grad_std(self, x, path_index, centered=False):
+        """``bobe_gp_paths_grad``: (f (T,), df (T, d)) in the set's standardised units"""
+        x = self._points(x)
+        t = int(x.shape[0])
+        idx = np.ascontiguousarray(np.broadcast_to(np.asarray(path_index, dtype=np.int64).reshape(-1), (t,)))
+        f, df = np.empty(t), np.empty((t, self._d))
+        _lib.check(self._lib.bobe_gp_paths_grad(self._handle(), _lib.ptr(x), t, _lib.ptr(idx), 1 if centered else 0, _lib.ptr(f),
+                                                _lib.ptr(df)), "bobe_gp_paths_grad")
+        return f, df
+
+    def value_and_grad(self, x, path_index, centered=False):
+        """(values (T,), grads (T, d)): path ``path_index[t]`` and its gradient with respect to the input at row t of ``x``
+        (NumPy array or torch CUDA tensor; one index serves every row), in physical units: y_mean + y_std f_s(x) and
+        y_std grad f_s(x); ``centered=True``: the path minus the posterior mean, without y_mean.  Analytic, on the device
+        (``bobe_gp_paths_grad``); the bits at a point do not depend on the other points of the call."""
+        f, df = self._grad_std(x, path_index, centered)
+        return (self.y_std * f if centered else self.y_mean + self.y_std * f), self.y_std * df
+
+    def maximize(self, starts, bounds=(0.0, 1.0), maxiter=100, options=None) -> dict:
+        """The maximum of every path by L-BFGS-B from R starts each (``starts``: (S, R, d); ``maximize_paths`` has the
+        driver, the selection rule and the keys of the result).  Every round of the S * R runs is one ``bobe_gp_paths_grad``
+        call on the points still waiting, in standardised units; ``value`` / ``start_value`` / ``restart_value`` /
+        ``start_values`` come back in physical units, y_mean + y_std f.  A path's result is never below its best start."""
+        starts = np.asarray(starts, dtype=np.float64)
+        if starts.ndim != 3 or starts.shape[0] != self.n_paths or starts.shape[2] != self._d:
+            raise ValueError(f"starts must have shape ({self.n_paths}, R, {self._d}), not {starts.shape}")
+        self._handle()
+        out = maximize_paths(self._grad_std, starts, bounds=bounds, maxiter=maxiter, options=options)
+        for k in ("value", "start_value", "restart_value", "start_values"):
+            out[k] = self.y_mean + self.y_std * out[k]
+        return out
 
     def argmax(self, x, bias=None):
         """(indices (S,), values (S,)): for every path the row of ``x`` that maximises f_s(x) + bias[s] (``bias``: (S, C), in the

@@ -298,6 +298,19 @@ int bobe_gp_posterior_sample(bobe_gp_t* gp, const double* Xq, int64_t C, int64_t
  *   eval: f[s][c] = f_s(Xq_c) (S x C, row-major); centered != 0: f_s - posterior mean (bobe_gp_predict's mean).
  *   argmax: idx[s] = argmax_c f_s(Xq_c) + bias[s][c] and best[s] = that maximum, without forming the S x C matrix; bias (S x C)
  *     may be NULL; ties go to the lower index.
+ *   grad: value and INPUT gradient of one path per point: for t < T, with s = path_idx[t], x = Xq[t], xs = x / ls,
+ *     c_n = V_c[n][s] + alpha_n (centered != 0: V_c[n][s] alone), amp = sqrt(2 kvar / F), arg_j = u_j . xs + b_j, r2_n = |xs_n - xs|^2,
+ *       f[t]     = sum_n c_n k(r2_n) + amp sum_j w_sj cos(arg_j)
+ *       df[t][k] = (1 / ls_k) [ sum_n c_n G(r2_n) (xs_nk - xs_k) - amp sum_j w_sj sin(arg_j) u_jk ]
+ *     G = k for the RBF kernel, kvar (5/3) (1 + sqrt5 r) exp(-sqrt5 r) for Matern-5/2 (taken as 0 below r2 = 1e-30, where it
+ *     multiplies a zero difference).  Xq: T x d, host or device.  path_idx: T entries in [0, S), HOST memory, checked.  f (T)
+ *     and df (T x d, row-major): host or device; either may be NULL, not both.  Summation order: one 256-thread workgroup per
+ *     point; thread tau adds the kernel terms n = tau, tau + 256, ... and then the feature terms j = tau, tau + 256, ... in
+ *     ascending order into one accumulator per component; the 256 partials are added in one fixed tree (lanes of a wave, then
+ *     the four waves in order); the division by ls_k comes last.  Invariance: the bits of (f[t], df[t]) depend on the set, the
+ *     point, its path index and the centred flag alone - not on T, the other points of the call, the pointer kinds or a NULL
+ *     output.  The first call of a set transposes V_c once (8 S Np bytes, freed with the set).  BOBE_ERR_ARG for T < 1, a NULL
+ *     p / Xq / path_idx, both outputs NULL, or an index out of range.
  * NOT gated (like bobe_gp_predict_cov).  eval / argmax: BOBE_ERR_ARG for C < 1 or a NULL pointer. */
 typedef struct bobe_paths bobe_paths_t;
 int bobe_gp_paths_create(bobe_gp_t* gp, int64_t S, int64_t F, uint64_t seed, const double* u, const double* phase,
@@ -305,6 +318,8 @@ int bobe_gp_paths_create(bobe_gp_t* gp, int64_t S, int64_t F, uint64_t seed, con
 int bobe_gp_paths_get(bobe_paths_t* p, double* u, double* phase, double* w, double* eps);
 int bobe_gp_paths_eval(bobe_paths_t* p, const double* Xq, int64_t C, int centered, double* f);
 int bobe_gp_paths_argmax(bobe_paths_t* p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best);
+int bobe_gp_paths_grad(bobe_paths_t* p, const double* Xq, int64_t T, const int64_t* path_idx, int centered, double* f,
+                       double* df);
 void bobe_gp_paths_destroy(bobe_paths_t* p);
 
 /* EI.fun / LogEI.fun (acquisition.py:226-253, 318-330) for C points: out[c] = +EI (mode 0) or
