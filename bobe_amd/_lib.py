@@ -127,6 +127,11 @@ SIGNATURES = [
     ("bobe_gp_npoints", C.c_int64, [C.c_void_p]),
     ("bobe_debug_gemm", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    ("bobe_debug_tile_gemm_count", C.c_int, []),
+    ("bobe_debug_tile_gemm_info", C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    ("bobe_debug_tile_gemm", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int]),
     ("bobe_debug_kinv", C.c_int, [C.c_void_p, C.c_void_p]),
     ("bobe_debug_linv", C.c_int, [C.c_void_p, C.c_void_p]),
     ("bobe_debug_time_potrf", C.c_int, [C.c_void_p, C.c_int, c_double_p]),

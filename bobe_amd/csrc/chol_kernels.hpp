@@ -739,9 +739,7 @@ __device__ __forceinline__ void chol_panel_body5(double* __restrict__ A, int64_t
 // k_syrk_trail - the same arithmetic per element as the separate update launch, only earlier and for free.
 // (Measured with stand-in MFMA workgroups first, profiles/r03_filler_standin.txt: up to ~8 MFLOP per filler workgroup the
 // factorisation takes exactly as long as without them; beyond that the launch lasts as long as its slowest filler.)
-// (FillJob: gp_types.hpp)
-constexpr int FILL_BK = 32;
-constexpr int FILL_SMEM_DOUBLES = gemm_smem_doubles_exact<KC, KC, 64, 64, FILL_BK>();   // per group; two groups fit the panel's 150 KB
+// (FillJob: gp_types.hpp; FILL_BK, FILL_SMEM_DOUBLES: gemm_f64.hpp)
 static_assert(2 * FILL_SMEM_DOUBLES * 8 <= POTF2_SMEM_BYTES, "update fillers exceed the panel's LDS");
 template <bool FILL = false, int STRIPS = 4>
 __global__ __launch_bounds__(PANEL_THREADS) void k_chol_panel(double* __restrict__ A, int64_t lda, int64_t bsA,

@@ -74,6 +74,14 @@ constexpr int GEMM64_SMEM_BYTES = gemm_smem_doubles<64, 64, BK64>() * 8;
 constexpr int BK32 = 32;
 template <int T> struct TileCfg { static constexpr int bk = (T == 128) ? BK128 : (T == 64 ? BK64 : BK32); };
 constexpr int GEMM32_SMEM_BYTES = gemm_smem_doubles<32, 32, BK32>() * 8;
+// The Cholesky's trailing update (k_syrk_trail, chol_kernels.hpp) and the update fillers of its panel launch
+// (k_chol_panel<true, .>) take K-steps and LDS budgets of their own.  They sit here so that the launches (gp_factor.hip) and
+// the tile-core harness (gp_tile_harness.hip) read the same numbers.
+constexpr int SYRK32_BK = 128, SYRK64_BK = 16;   // BK = 128 = the whole panel: one stage, one LDS buffer
+constexpr int SYRK32_SMEM = gemm_smem_doubles_exact<KC, KC, 32, 32, SYRK32_BK>() * 8 / 2;  //  66,560 B (single buffer)
+constexpr int SYRK64_SMEM = gemm_smem_doubles_exact<KC, KC, 64, 64, SYRK64_BK>() * 8;      //  36,864 B -> four workgroups per CU
+constexpr int FILL_BK = 32;
+constexpr int FILL_SMEM_DOUBLES = gemm_smem_doubles_exact<KC, KC, 64, 64, FILL_BK>();   // per group; two groups fit the panel's 150 KB
 
 // ---- global -> register staging (R*BK/512 x 16 B per thread per operand) -----------------------
 template <int L, int R, int BK>

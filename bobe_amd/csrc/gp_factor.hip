@@ -11,10 +11,7 @@ using namespace bobe;
 
 namespace bobe {
 
-constexpr int SYRK32_BK = 128, SYRK64_BK = 16;   // BK = 128 = the whole panel: one stage, one LDS buffer
-constexpr int SYRK32_SMEM = gemm_smem_doubles_exact<KC, KC, 32, 32, SYRK32_BK>() * 8 / 2;  //  66,560 B (single buffer)
-constexpr int SYRK64_SMEM = gemm_smem_doubles_exact<KC, KC, 64, 64, SYRK64_BK>() * 8;      //  36,864 B -> four workgroups per CU
-
+// (SYRK32_BK, SYRK64_BK, SYRK32_SMEM, SYRK64_SMEM: gemm_f64.hpp)
 void configure_factor_kernels() {
   static bool done[64] = {false};
   if (!first_use_on_device(done)) return;

@@ -11,6 +11,7 @@
 //   gp_paths.hip      pathwise posterior draws of the latent surrogate (random Fourier features + Matheron's rule): path
 //                     sets, their evaluation at query points and per-path argmax
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
+//   gp_tile_harness.hip  test hook: one tile_gemm instantiation per call on caller-supplied operands
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
 // without a HIP device every entry point fails with BOBE_ERR_HIP.
 #pragma once

@@ -528,6 +528,25 @@ int64_t bobe_gp_npoints(bobe_gp_t* gp);
  * p[r*ld+k]; layout 1: at p[k*ld+r].  M, N multiples of 128, K multiple of 16.  Device or host ptrs. */
 int bobe_debug_gemm(int device, int layoutA, int layoutB, int64_t M, int64_t N, int64_t K, const double* A,
                     int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc);
+/* One instantiation ("variant") of the tile core tile_gemm<GLDS, LA, LB, T, NEGA, TRIL, BK> on the caller's operands, with
+ * the dynamic LDS of the launch that ships it.  bobe_debug_tile_gemm_count: the number of variants compiled in.
+ * bobe_debug_tile_gemm_info: info9 = {T, BK, glds, layoutA, layoutB, nega, tril, groups, single_buffer} (layouts as in
+ * bobe_debug_gemm; groups = 2: two 256-thread tile groups per workgroup, side by side in n; single_buffer: LDS for one
+ * K-step only).
+ * bobe_debug_tile_gemm runs a tiles_m x tiles_n grid of T x T tiles.  Tile (p, q), with r = m0 + p T and c = n0 + q T:
+ *   acc = preload ? C[r.., c..] : 0;  acc (+/-)= sum over k in [kbeg, kend) of A(r + i, k) B(c + j, k);
+ *   C[r.., c..] = alpha acc + beta C[r.., c..]
+ * HOST pointers only: A [rows_a x lda], B [rows_b x ldb] and C [rows_c x ldc] are copied in whole (whatever surrounds the
+ * operands included) and the whole of C is copied back.  An array passed more than once (A == B, or A == B == C: the
+ * trailing update's in-place form) is ONE device buffer.  Refused with BOBE_ERR_ARG before anything is launched or
+ * written: an unknown variant; an odd leading dimension; m0, n0 or kbeg not a multiple of T; kend - kbeg not a positive
+ * multiple of BK; more than one K-step on a single_buffer variant; an odd tiles_n with groups = 2; operands or tiles that
+ * do not fit their arrays; an array that is both read and written where the two regions meet. */
+int bobe_debug_tile_gemm_count(void);
+int bobe_debug_tile_gemm_info(int variant, int* info9);
+int bobe_debug_tile_gemm(int device, int variant, int tiles_m, int tiles_n, int64_t m0, int64_t n0, int64_t kbeg,
+                         int64_t kend, const double* A, int64_t lda, int64_t rows_a, const double* B, int64_t ldb,
+                         int64_t rows_b, double* C, int64_t ldc, int64_t rows_c, double alpha, double beta, int preload);
 /* K^-1 (N x N, full symmetric) from the current factorisation — used by the parity tests */
 int bobe_debug_kinv(bobe_gp_t* gp, double* Kinv);
 /* L^-1 (N x N lower) from the current factorisation */
