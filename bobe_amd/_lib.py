@@ -74,6 +74,9 @@ SIGNATURES = [
     ("bobe_gp_paths_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     ("bobe_gp_paths_argmax", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("bobe_gp_paths_grad", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("bobe_gp_paths_hmc_run", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p]),
     ("bobe_gp_paths_destroy", None, [C.c_void_p]),
     ("bobe_gp_wip_grad", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -143,6 +146,7 @@ SIGNATURES = [
     ("bobe_gp_profile_read", C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
     ("bobe_debug_mfma_peak", C.c_int, [C.c_int, C.c_int, c_double_p]),
     ("bobe_debug_wave_sums", C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("bobe_debug_paths_chain_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -295,7 +295,14 @@ class PathwiseTS(AcquisitionFunction):
     ``acq_kwargs['ts_polish'] = R`` (default 0: the pool picks above, bit for bit) carries the argmax to the continuum: member
     s starts from the R best pool rows of path s and takes the maximum of its path over the unit cube
     (``PosteriorPaths.maximize``, at most ``acq_kwargs['ts_polish_maxiter']`` = 100 L-BFGS-B iterations; ``_polished_batch``
-    has the replacement rule); it needs ``ts_mode='max'`` and draws the same numbers from ``rng``."""
+    has the replacement rule); it needs ``ts_mode='max'`` and draws the same numbers from ``rng``.
+    ``acq_kwargs['ts_chain_steps'] = n`` (default 0 or absent: the pool picks above, bit for bit, and the same numbers from
+    ``rng``) turns the Gumbel-max pick into a Thompson sample from exp(f_s) in the continuum: member s starts at its pool
+    pick and runs ``acq_kwargs['ts_chain_warmup']`` (default 50) adapting HMC iterations, then n more, on path s
+    (``PosteriorPaths.hmc_run``: all members in one launch per phase; inverse masses from the pool's spread in logit
+    coordinates; one more ``rng.integers`` draw seeds the chains) and returns the chain's end state.  It needs
+    ``ts_mode='posterior'``.  An end point that is infeasible under the GP's gate or within 1e-12 of an earlier member's falls
+    back to the member's pool pick."""
 
     name: str = "PathwiseTS"
 
@@ -312,6 +319,7 @@ class PathwiseTS(AcquisitionFunction):
         if mode not in ("max", "posterior"):
             raise ValueError(f"ts_mode must be 'max' or 'posterior', not {mode!r}")
         polish = _ts_polish(acq_kwargs, mode)
+        chain_steps, chain_warmup = _ts_chain_steps(acq_kwargs, mode)
         pool = acq_kwargs.get("candidates")
         if pool is None:
             pool = acq_kwargs["mc_samples"]["x"]
@@ -342,7 +350,41 @@ class PathwiseTS(AcquisitionFunction):
                     picks[s] = int(np.argmax(row))
                     vals[s] = paths.y_mean + paths.y_std * row[picks[s]]
                 taken.add(int(picks[s]))
+            if chain_steps > 0:
+                return self._chain_batch(gp, paths, pool_host, picks, vals, chain_steps, chain_warmup,
+                                         int(rng.integers(0, 2 ** 62)))
         return np.array(pool_host[picks]), np.array(vals)
+
+    @staticmethod
+    def _chain_batch(gp, paths, pool_host, picks, vals, n_steps, n_warmup, seed):
+        """``ts_chain_steps`` = n > 0: member s runs one HMC chain on path s from its pool pick - ``n_warmup`` adapting
+        iterations, then n with the averaged step size - and takes the end state (value: the path there).  The inverse mass
+        of every chain is the variance of the pool in logit coordinates + 1e-3.  An end point that the GP's gate refuses, or
+        that lies within 1e-12 (max-norm) of an earlier member's point, is replaced by the member's pool pick."""
+        n_batch, d = len(picks), pool_host.shape[1]
+        logit = lambda x: np.log(x) - np.log1p(-x)
+        inv_mass = np.var(logit(np.clip(pool_host, 1e-6, 1.0 - 1e-6)), axis=0) + 1e-3
+        idx = np.arange(n_batch, dtype=np.int64)
+        state = paths.hmc_state(logit(np.clip(pool_host[picks], 1e-6, 1.0 - 1e-6)), idx, 1.0)
+        adapt = np.tile(np.array([0.1, 0.0, 0.0, 0.0, 0.0]), (n_batch, 1))
+        if n_warmup > 0:
+            paths.hmc_run(state, adapt, inv_mass, idx, seed, 0, n_warmup, True)
+            adapt[:, 0] = np.where(adapt[:, 3] != 0.0, np.clip(np.exp(adapt[:, 3]), 1e-4, 2.0), adapt[:, 0])
+        paths.hmc_run(state, adapt, inv_mass, idx, seed, n_warmup, n_steps, False)
+        x_end, v_end = state[:, 2 * d:3 * d], state[:, 3 * d + 1]
+        gated = bool(getattr(gp, "_gated", lambda: False)())
+        ok = np.ones(n_batch, dtype=bool)
+        if gated:
+            from .clf import gate_eval
+            ok = gate_eval(gp._lib, gp._h, np.ascontiguousarray(x_end), gp.ndim)[1] > 0.0
+        pts, out_vals = [], []
+        for s in range(n_batch):
+            x, v = x_end[s], v_end[s]
+            if not (ok[s] and np.isfinite(v) and all(np.max(np.abs(x - q)) > _TS_DUPLICATE_TOL for q in pts)):
+                x, v = pool_host[picks[s]], vals[s]
+            pts.append(np.array(x))
+            out_vals.append(float(v))
+        return np.array(pts), np.array(out_vals)
 
     @staticmethod
     def _polished_batch(gp, paths, pool, pool_host, n_batch, n_starts, maxiter):
@@ -396,6 +438,18 @@ def _ts_polish(acq_kwargs, mode) -> int:
     if int(r) > 0 and mode == "posterior":
         raise ValueError("ts_polish needs ts_mode='max': a Gumbel-max draw from a pool has no continuum form")
     return int(r)
+
+
+def _ts_chain_steps(acq_kwargs, mode):
+    """``acq_kwargs['ts_chain_steps']`` / ``['ts_chain_warmup']``: HMC iterations of a Thompson member on its path, 0 (default)
+    = none.  Checked before anything touches the device."""
+    n, w = acq_kwargs.get("ts_chain_steps", 0), acq_kwargs.get("ts_chain_warmup", 50)
+    for name, v in (("ts_chain_steps", n), ("ts_chain_warmup", w)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 0:
+            raise ValueError(f"{name} must be a non-negative integer, not {v!r}")
+    if int(n) > 0 and mode != "posterior":
+        raise ValueError("ts_chain_steps needs ts_mode='posterior': the chain continues a draw from exp(f_s), not an argmax")
+    return int(n), int(w)
 
 
 def get_mc_samples(gp: GP, warmup_steps=512, num_samples=1024, thinning=4, method="NUTS", num_chains=4,

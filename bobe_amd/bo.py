@@ -211,6 +211,7 @@ class BOBE:
         self.wip_batch_mode = "believer"
         self.mc_weighted = False
         self.ts_polish = 0
+        self.ts_chain_steps, self.ts_chain_warmup = 0, 50
         self.min_delta_seen = np.inf
         self.current_iteration = 0
         self.start_iteration = 0
@@ -581,7 +582,8 @@ class BOBE:
             num_chains: int = 4, mc_points_method: str = "NUTS", zeta_ei: float = 0.01, *,
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
             mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
-            ts_polish: int = 0, wip_batch_mode: str = "believer") -> dict:
+            ts_polish: int = 0, ts_chain_steps: int = 0, ts_chain_warmup: int = 50, path_posterior: int = 0,
+            wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
@@ -597,7 +599,14 @@ class BOBE:
         log-weights (``get_mc_points(weighted=True)``, ``acq_kwargs['mc_log_weights']``) instead of equal-weight draws; the
         default changes nothing, and ``ts_polish`` - for ``acq='ts'``: R > 0 hands ``acq_kwargs['ts_polish'] = R`` to
         ``PathwiseTS``, which then maximises every path over the unit cube by L-BFGS-B from its R best pool rows
-        (``PosteriorPaths.maximize``); 0 (default): the pool picks, and an ``acq_kwargs`` without the key.
+        (``PosteriorPaths.maximize``); 0 (default): the pool picks, and an ``acq_kwargs`` without the key, and
+        ``ts_chain_steps`` - for ``acq='ts'``: n > 0 hands ``acq_kwargs['ts_mode'] = 'posterior'``, ``['ts_chain_steps'] = n``
+        and ``['ts_chain_warmup']`` to ``PathwiseTS``, whose member s then runs an HMC chain on path s from its pool pick
+        (``PosteriorPaths.hmc_run``) - a Thompson sample from exp(f_s) in the continuum; 0 (default): no such keys, and
+        ``path_posterior`` - K > 0: after the run, K posterior paths of the final surrogate are sampled
+        (``samplers.sample_paths_hmc`` with the run's HMC settings) and ``results['path_posterior']`` holds
+        ``samplers.path_posterior_summary`` of them in physical parameters - how far the constraints move between plausible
+        surrogates; its generator is seeded by one draw from the run's, taken only when K > 0 (0, the default: no key, no draw).
         ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
         samples.  ``acq`` may be a tuple of stages, run one after the other on the
@@ -635,6 +644,13 @@ class BOBE:
         if isinstance(ts_polish, bool) or int(ts_polish) != ts_polish or int(ts_polish) < 0:
             raise ValueError(f"ts_polish must be a non-negative integer, not {ts_polish!r}")
         self.ts_polish = int(ts_polish)
+        for name, v in (("ts_chain_steps", ts_chain_steps), ("ts_chain_warmup", ts_chain_warmup),
+                        ("path_posterior", path_posterior)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 0:
+                raise ValueError(f"{name} must be a non-negative integer, not {v!r}")
+        if int(ts_chain_steps) > 0 and self.ts_polish > 0:
+            raise ValueError("ts_chain_steps needs ts_mode='posterior' and ts_polish ts_mode='max': choose one")
+        self.ts_chain_steps, self.ts_chain_warmup = int(ts_chain_steps), int(ts_chain_warmup)
         self.loo_diagnostics, self.loo_history = bool(loo_diagnostics), []
         self.converged, self.convergence_counter = False, 0
         self.min_delta_seen = np.inf
@@ -707,8 +723,19 @@ class BOBE:
         self.finalise_results()
         if self.loo_diagnostics:
             self.results_dict["loo_history"] = list(self.loo_history)
+        if int(path_posterior) > 0:
+            self.results_dict["path_posterior"] = self._path_posterior(int(path_posterior))
         self.start_iteration = self.current_iteration            # (a further run() on this object counts on)
         return self.results_dict
+
+    def _path_posterior(self, n_paths: int) -> dict:
+        """``run(path_posterior=K)``: the summary of K per-path posteriors of the final surrogate, physical parameters"""
+        from .samplers import path_posterior_summary, sample_paths_hmc
+        seed = int(self.np_rng.integers(0, 2 ** 62))
+        with self.gp.sample_paths(n_paths, 2048, seed=seed) as paths:
+            out = sample_paths_hmc(paths, warmup_steps=self.num_hmc_warmup, num_samples=self.num_hmc_samples,
+                                   thinning=self.hmc_thinning, rng=np.random.default_rng(seed))
+        return path_posterior_summary(out, param_bounds=self.param_bounds)
 
     def run_EI(self, ii=0):
         """bo.py:1174-1224: one point per iteration; stops on the (log-)EI goal or the budgets."""
@@ -779,6 +806,9 @@ class BOBE:
             acq_kwargs = {"mc_samples": self.mc_samples, "mc_points_size": self.mc_points_size}
             if self.ts_polish > 0:
                 acq_kwargs["ts_polish"] = self.ts_polish
+            if self.ts_chain_steps > 0:
+                acq_kwargs.update(ts_mode="posterior", ts_chain_steps=self.ts_chain_steps,
+                                  ts_chain_warmup=self.ts_chain_warmup)
             if self.mc_weighted and self.mc_samples.get("weights") is not None:
                 acq_kwargs["mc_points"], acq_kwargs["mc_log_weights"] = get_mc_points(
                     self.mc_samples, mc_points_size=self.mc_points_size, weighted=True)

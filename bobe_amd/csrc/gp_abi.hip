@@ -436,6 +436,26 @@ int bobe_gp_paths_grad(bobe_paths_t* p, const double* Xq, int64_t T, const int64
   API_END
 }
 
+int bobe_gp_paths_hmc_run(bobe_paths_t* p, int64_t P, const int64_t* path_idx, double* state, double* adapt,
+                          const double* inv_mass, uint64_t seed, int64_t it0, int niter, int do_adapt, double y_std,
+                          double y_mean, double temp, int hist_from, double* hist, int thin, double* keep, double* dbg) {
+  API_BEGIN
+  NEED(p && path_idx && state && adapt && inv_mass, "NULL argument");
+  NEED(!is_device_ptr(path_idx) && !is_device_ptr(state) && !is_device_ptr(adapt) && !is_device_ptr(inv_mass) &&
+           !is_device_ptr(hist) && !is_device_ptr(keep) && !is_device_ptr(dbg),
+       "bobe_gp_paths_hmc_run takes host pointers");
+  return paths_hmc_run(*p, P, path_idx, state, adapt, inv_mass, seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from,
+                       hist, thin, keep, dbg);
+  API_END
+}
+
+int bobe_debug_paths_chain_layout(bobe_paths_t* p, int* info4) {
+  API_BEGIN
+  NEED(p && info4, "NULL argument");
+  return paths_chain_layout(*p, info4);
+  API_END
+}
+
 void bobe_gp_paths_destroy(bobe_paths_t* p) { paths_destroy(p); }
 
 int bobe_gp_wip_grad(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,

@@ -739,5 +739,9 @@ int paths_get(bobe_paths& p, double* u, double* phase, double* w, double* eps);
 int paths_eval(bobe_paths& p, const double* Xq, int64_t C, int centered, double* f);
 int paths_argmax(bobe_paths& p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best);
 int paths_grad(bobe_paths& p, const double* Xq, int64_t T, const int64_t* path_idx, int centered, double* f, double* df);
+int paths_hmc_run(bobe_paths& p, int64_t P, const int64_t* path_idx, double* state, double* adapt, const double* inv_mass,
+                  uint64_t seed, int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp,
+                  int hist_from, double* hist, int thin, double* keep, double* dbg);
+int paths_chain_layout(bobe_paths& p, int* info4);
 void paths_destroy(bobe_paths* p);
 }  // namespace bobe

@@ -4,7 +4,8 @@
 // A path set is a SNAPSHOT of the handle's factorised state: it owns the scaled training coordinates, alpha, the
 // hyper-parameters, the frequencies / phases / weights and V_c = -K^-1 (Phi(X) W^T + E^T); the parent's factor is read while
 // the set is created and never again.  The parent's stream, chunk and launch helpers are used by every call, so the set is
-// destroyed before its parent.  Kernels: paths_kernels.hpp.  Every call-scoped buffer is a CallBuf.  paths_grad (value and
+// destroyed before its parent.  paths_hmc_run (whole HMC chains on a path, k_paths_hmc_run) also reads the parent's classifier
+// gate at call time: the gate is not part of the snapshot.  Kernels: paths_kernels.hpp.  Every call-scoped buffer is a CallBuf.  paths_grad (value and
 // input gradient of one path per point, k_paths_grad) adds one lazily built member, the transposed coefficients VcT.
 #include "gp_handle.hpp"
 
@@ -44,6 +45,8 @@ void configure_paths_kernels() {
   allow_big_lds(k_paths_tiles<64, false, true>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_paths_tiles<32, false, false>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_paths_tiles<32, false, true>, GEMM32_SMEM_BYTES);
+  // (the chain kernel keeps training rows in up to 148 KB of LDS, like k_hmc_run)
+  for_each_kern_dcap([](auto KE, auto DC) { allow_big_lds((k_paths_hmc_run<KE, DC>), CHAIN_LDS_BYTES); });
 }
 }  // namespace bobe
 
@@ -166,6 +169,15 @@ void run_chunks(bobe_paths& p, const double* Xq, int64_t C, bool centered, doubl
     g.prof_end(BOBE_PROF_CROSSVV);
   }
   g.sync();     // (the call's buffers are freed on return)
+}
+
+// VcT, the transposed coefficients: built by the set's first paths_grad / paths_hmc_run call
+void ensure_vct(bobe_paths& p) {
+  if (p.VcT.p) return;
+  p.VcT.ensure((size_t)p.S * p.Np * sizeof(double));
+  hipLaunchKernelGGL(k_paths_transpose_vc, dim3((unsigned)p.S, (unsigned)((p.Np + 255) / 256)), dim3(256), 0, p.g->stream,
+                     (const double*)p.VW.d(), p.Sp, p.Np, p.VcT.d(), p.Np);
+  LAUNCH_CHECK();
 }
 
 }  // namespace
@@ -309,12 +321,7 @@ int paths_grad(bobe_paths& p, const double* Xq, int64_t T, const int64_t* path_i
   bobe_gp& g = *p.g;
   g.use();
   const int d = p.d;
-  if (!p.VcT.p) {
-    p.VcT.ensure((size_t)p.S * p.Np * sizeof(double));
-    hipLaunchKernelGGL(k_paths_transpose_vc, dim3((unsigned)p.S, (unsigned)((p.Np + 255) / 256)), dim3(256), 0, g.stream,
-                       (const double*)p.VW.d(), p.Sp, p.Np, p.VcT.d(), p.Np);
-    LAUNCH_CHECK();
-  }
+  ensure_vct(p);
   CallBuf xin, idx, fout, dout;
   const double* xq = Xq;
   if (!is_device_ptr(Xq)) {
@@ -344,6 +351,76 @@ int paths_grad(bobe_paths& p, const double* Xq, int64_t T, const int64_t* path_i
   LAUNCH_CHECK();
   if (fd != f) HIPCHK(hipMemcpyAsync(f, fd, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, g.stream));
   if (dd != df) HIPCHK(hipMemcpyAsync(df, dd, (size_t)T * d * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  g.sync();     // (the call's buffers are freed on return)
+  return BOBE_OK;
+}
+
+// where a chain workgroup of k_paths_hmc_run keeps this set's training rows, and its features per thread
+static void chain_layout(const bobe_paths& p, int* reg, int* lds, int* streamed, int* feat, int* lgroups) {
+  int rmax = 0;
+  with_dcap(p.d, [&](auto DC) { rmax = ChainRows<DC>::PATHS; });
+  const int lg = chain_lds_groups(p.N, p.d, rmax);
+  const int64_t r = std::min<int64_t>(p.N, 256 * (int64_t)rmax);
+  const int64_t l = std::min<int64_t>(p.N - r, 256 * (int64_t)lg);
+  *reg = (int)r;
+  *lds = (int)l;
+  *streamed = (int)(p.N - r - l);
+  *feat = (int)((p.F + 255) / 256);
+  *lgroups = lg;
+}
+
+int paths_chain_layout(bobe_paths& p, int* info4) {
+  int lg = 0;
+  chain_layout(p, info4, info4 + 1, info4 + 2, info4 + 3, &lg);
+  return BOBE_OK;
+}
+
+int paths_hmc_run(bobe_paths& p, int64_t P, const int64_t* path_idx, double* state, double* adapt, const double* inv_mass,
+                  uint64_t seed, int64_t it0, int niter, int do_adapt, double y_std, double y_mean, double temp,
+                  int hist_from, double* hist, int thin, double* keep, double* dbg) {
+  if (P <= 0 || P > INT_MAX || niter < 1 || it0 < 0 || !(temp > 0.0) || thin < 1 || hist_from < 0 || hist_from > niter)
+    throw Err(BOBE_ERR_ARG, "bad argument");
+  for (int64_t c = 0; c < P; ++c)
+    if (path_idx[c] < 0 || path_idx[c] >= p.S) throw Err(BOBE_ERR_ARG, "path_idx out of range");
+  bobe_gp& g = *p.g;
+  g.use();
+  ensure_vct(p);
+  const int d = p.d;
+  const size_t sw = 3 * (size_t)d + 2, ns = (size_t)P * sw, na = (size_t)P * 5, ni = (size_t)P * d;
+  const size_t nh = hist ? (size_t)(niter - hist_from) * P * d : 0;
+  const size_t nk = keep ? (size_t)(niter / thin) * P * (d + 1) : 0;
+  const size_t nd = dbg ? (size_t)P * (d + 3) : 0;
+  // staging: state | adapt | inv_mass | hist | keep | dbg, and the path indices
+  CallBuf stage, idx;
+  stage.ensure((ns + na + ni + nh + nk + nd) * sizeof(double));
+  idx.ensure((size_t)P * sizeof(int64_t));
+  double* dS = stage.d();
+  double* dA = dS + ns;
+  double* dI = dA + na;
+  double* dH = dI + ni;
+  double* dK = dH + nh;
+  double* dD = dK + nk;
+  HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(dI, inv_mass, ni * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(idx.p, path_idx, (size_t)P * sizeof(int64_t), hipMemcpyHostToDevice, g.stream));
+  int reg, lds, streamed, feat, lg;
+  chain_layout(p, &reg, &lds, &streamed, &feat, &lg);
+  const double amp = std::sqrt(2.0 * p.hyp.kvar / (double)p.F);
+  with_kern_dcap(p.hyp.kern, d, [&](auto KE, auto DC) {
+    hipLaunchKernelGGL((k_paths_hmc_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
+                       g.stream, (const double*)p.XsT.d(), p.Np, p.N, p.hyp, (const double*)p.alpha.d(),
+                       (const double*)p.VcT.d(), p.Np, (const double*)p.U.d(), (const double*)p.B.d(),
+                       (const double*)p.W.d(), p.F, amp, (const int64_t*)idx.p, P, dS, dA, (const double*)dI,
+                       (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from, hist ? dH : nullptr,
+                       thin, keep ? dK : nullptr, dbg ? dD : nullptr, g.gate, lg);
+  });
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (hist) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (keep) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (dbg) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, g.stream));
   g.sync();     // (the call's buffers are freed on return)
   return BOBE_OK;
 }

@@ -84,7 +84,8 @@ class PosteriorPaths:
     """S draws f_s of the posterior of the latent surrogate, f_s(x) = phi(x)^T w_s + k(x, X) K^-1 (y - Phi(X) w_s - eps_s) with F
     random Fourier features.  A snapshot of the GP at the time of ``GP.sample_paths``: later ``update`` / ``fit`` calls on the
     GP do not change it.  Holds device memory until ``close()`` (or the end of a ``with`` block, or collection); it is
-    destroyed before its GP's handle.  Not gated."""
+    destroyed before its GP's handle.  ``evaluate`` / ``argmax`` / ``value_and_grad`` / ``maximize`` are not gated; ``hmc_run`` /
+    ``sample`` apply the GP's classifier gate as it is set when they are called (the gate is not part of the snapshot)."""
 
     def __init__(self, gp, n_paths, n_features, seed, u=None, phase=None, w=None, eps=None):
         self._gp = gp
@@ -108,6 +109,15 @@ class PosteriorPaths:
         self.y_mean, self.y_std = float(gp.y_mean), float(gp.y_std)
         self._finalizer = weakref.finalize(self, _destroy, self._lib, self._h)
         gp._paths.add(self)
+
+    @property
+    def ndim(self) -> int:
+        return self._d
+
+    @property
+    def gp(self):
+        """The GP the set was drawn from (its training data give the samplers their starts, its gate applies to them)."""
+        return self._gp
 
     def _handle(self):
         if not self._h.value:
@@ -178,6 +188,63 @@ class PosteriorPaths:
         for k in ("value", "start_value", "restart_value", "start_values"):
             out[k] = self.y_mean + self.y_std * out[k]
         return out
+
+    def chain_layout(self) -> dict:
+        """Where a chain workgroup of ``hmc_run`` keeps this set's training rows (``bobe_debug_paths_chain_layout``):
+        ``registers`` / ``lds`` / ``streamed`` row counts and ``features_per_thread``."""
+        info = (C.c_int * 4)()
+        _lib.check(self._lib.bobe_debug_paths_chain_layout(self._handle(), info), "bobe_debug_paths_chain_layout")
+        return {"registers": int(info[0]), "lds": int(info[1]), "streamed": int(info[2]), "features_per_thread": int(info[3])}
+
+    def hmc_run(self, state, adapt, inv_mass, path_index, seed: int, it0: int, niter: int, do_adapt: bool, temp: float = 1.0,
+                hist_from=None, thin: int = 0, debug: bool = False):
+        """``GP.hmc_run`` on paths: ``niter`` whole HMC trajectories of every chain in ONE launch (``bobe_gp_paths_hmc_run``),
+        chain c on the posterior implied by the draw ``path_index[c]`` (one index serves every chain), in the snapshot's units
+        (its ``y_std`` / ``y_mean``).  ``state`` (P, 3d+2) = [u, dlogp/du, x, logp, mean] and ``adapt`` (P, 5) are updated in
+        place; ``inv_mass`` is per chain, (P, d) (a (d,) vector serves every chain).  Returns (hist, keep, dbg) as
+        ``GP.hmc_run`` does.  The parent GP's classifier gate, as set at call time, applies: it is not part of the snapshot."""
+        P, d = state.shape[0], self._d
+        if state.shape != (P, 3 * d + 2) or adapt.shape != (P, 5) or not (state.flags.c_contiguous and adapt.flags.c_contiguous) \
+                or state.dtype != np.float64 or adapt.dtype != np.float64:
+            raise ValueError("state must be a C-contiguous float64 (P, 3d+2) array and adapt a (P, 5) one")
+        im = np.ascontiguousarray(np.broadcast_to(_lib.as_f64(inv_mass), (P, d)))
+        idx = np.ascontiguousarray(np.broadcast_to(np.asarray(path_index, dtype=np.int64).reshape(-1), (P,)))
+        niter = int(niter)
+        if hist_from is not None and not 0 <= int(hist_from) <= niter:
+            raise ValueError("hist_from must be in [0, niter]")
+        if thin < 0 or niter < 1:
+            raise ValueError("niter must be positive and thin non-negative")
+        hist = np.empty((niter - int(hist_from), P, d)) if hist_from is not None else None
+        keep = np.empty((niter // thin, P, d + 1)) if thin else None
+        dbg = np.empty((P, d + 3)) if debug else None
+        _lib.check(self._lib.bobe_gp_paths_hmc_run(self._handle(), P, _lib.ptr(idx), _lib.ptr(state), _lib.ptr(adapt),
+                                                   _lib.ptr(im), int(seed) & (2 ** 64 - 1), int(it0), niter,
+                                                   int(bool(do_adapt)), float(self.y_std), float(self.y_mean), float(temp),
+                                                   int(hist_from or 0), _lib.ptr(hist) if hist is not None else None,
+                                                   int(thin) if thin else 1, _lib.ptr(keep) if keep is not None else None,
+                                                   _lib.ptr(dbg) if dbg is not None else None), "bobe_gp_paths_hmc_run")
+        return hist, keep, dbg
+
+    def hmc_state(self, U, path_index, temp: float = 1.0) -> np.ndarray:
+        """The (P, 3d+2) chain state [u, dlogp/du, x, logp, mean] of ``hmc_run`` at the logit positions ``U`` (P, d), chain c
+        on path ``path_index[c]``: values and gradients from ``value_and_grad``; a point the parent GP's gate refuses gets
+        mean = minus_inf and no gradient, as in the kernel."""
+        U = _lib.as_f64(U)
+        X = np.clip(1.0 / (1.0 + np.exp(-U)), 1e-12, 1.0 - 1e-12)
+        mean, gx = self.value_and_grad(X, path_index)
+        gp = self._gp
+        if hasattr(gp, "_gated") and gp._gated():
+            bad = ~(np.asarray(gp._device_proba(X)).reshape(-1) >= gp.probability_threshold)
+            mean = np.where(bad, gp.minus_inf, mean)
+            gx = np.where(bad[:, None], 0.0, gx)
+        lp = mean / temp + np.sum(np.log(X) + np.log1p(-X), axis=1)
+        g = gx / temp * (X * (1.0 - X)) + (1.0 - 2.0 * X)
+        return np.ascontiguousarray(np.concatenate([U, g, X, lp[:, None], mean[:, None]], axis=1))
+
+    def sample(self, **kwargs) -> dict:
+        """``samplers.sample_paths_hmc(self, **kwargs)``: HMC samples of the posterior implied by every path of the set."""
+        from .samplers import sample_paths_hmc
+        return sample_paths_hmc(self, **kwargs)
 
     def argmax(self, x, bias=None):
         """(indices (S,), values (S,)): for every path the row of ``x`` that maximises f_s(x) + bias[s] (``bias``: (S, C), in the

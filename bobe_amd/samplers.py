@@ -661,3 +661,151 @@ def _nuts_chains(gp, rng, U, g, X, lp, mean, warmup_steps, keep_per_chain, n_kee
     samples_x = keep[:, :, :d].reshape(-1, d)[:n_keep_total]
     logps = keep[:, :, d].reshape(-1)[:n_keep_total]
     return {"x": samples_x, "logp": logps, "best": samples_x[int(np.argmax(logps))], "method": "MCMC"}
+
+
+# --------------------------------------------------------------------------------------------------------------
+# HMC on pathwise posterior draws of the surrogate (PosteriorPaths.hmc_run, bobe_gp_paths_hmc_run)
+# --------------------------------------------------------------------------------------------------------------
+def _check_paths_hmc_args(n_paths, d, chains_per_path, warmup_steps, num_samples, thinning, temp, init):
+    """The argument rules of ``sample_paths_hmc``; returns ``init`` as an (S, R, d) array or None.  Raises ``ValueError``
+    before anything touches the device."""
+    if int(chains_per_path) != chains_per_path or chains_per_path < 1:
+        raise ValueError(f"chains_per_path must be a positive integer, not {chains_per_path!r}")
+    if not (np.isfinite(temp) and temp > 0.0):
+        raise ValueError(f"temp must be positive and finite, not {temp!r}")
+    if warmup_steps is not None and warmup_steps < 0:
+        raise ValueError("warmup_steps must be non-negative")
+    if num_samples is not None and num_samples < 1:
+        raise ValueError("num_samples must be positive")
+    if thinning is not None and thinning < 1:
+        raise ValueError("thinning must be positive")
+    if init is None:
+        return None
+    init = np.asarray(init, dtype=np.float64)
+    R = int(chains_per_path)
+    if init.shape == (R, d):
+        init = np.broadcast_to(init, (n_paths, R, d))
+    if init.shape != (n_paths, R, d):
+        raise ValueError(f"init must have shape ({R}, {d}) or ({n_paths}, {R}, {d}), not {init.shape}")
+    if not np.all(np.isfinite(init)) or np.any(init < 0.0) or np.any(init > 1.0):
+        raise ValueError("init must lie in the unit cube")
+    return np.array(init)
+
+
+def _pool_paths_window(state, adapt, hist, inv_mass, n_paths, rng, cull, update_mass):
+    """What ``sample_paths_hmc`` does at the end of a warm-up window, PER PATH (chains s R .. (s + 1) R - 1 belong to path
+    s): a chain more than 20 + 2 d log units below its path's best restarts from the state of a randomly chosen healthy
+    chain of the SAME path (``cull``); with ``update_mass`` the rows of ``inv_mass`` of the path become the variance of the
+    window's recorded positions ``hist`` (T, P, d) over its healthy chains + 1e-3.  In place; returns the healthy mask."""
+    P, d = inv_mass.shape
+    R = P // n_paths
+    healthy_all = np.ones(P, dtype=bool)
+    for s in range(n_paths):
+        sel = np.arange(s * R, (s + 1) * R)
+        healthy = np.ones(R, dtype=bool)
+        if cull:
+            lp_now = state[sel, 3 * d]
+            with np.errstate(invalid="ignore"):
+                top = np.max(np.where(np.isnan(lp_now), -np.inf, lp_now))
+                lost = ~(lp_now >= top - (20.0 + 2.0 * d))
+            if lost.any() and not lost.all():
+                healthy = ~lost
+                src = rng.choice(sel[healthy], size=int(lost.sum()))
+                state[sel[lost]] = state[src]
+                adapt[sel[lost]] = adapt[src]
+        if update_mass:
+            inv_mass[sel] = np.var(hist[:, sel[healthy], :].reshape(-1, d), axis=0) + 1e-3
+        healthy_all[sel] = healthy
+    return healthy_all
+
+
+def sample_paths_hmc(paths, chains_per_path: int = 16, warmup_steps=None, num_samples=None, thinning=None,
+                     temp: float = 1.0, rng=None, init=None, cull_lost_chains: bool = True, diagnostics=None) -> Dict:
+    """HMC samples of the posterior implied by every DRAW of the surrogate: for each of the S paths of ``paths`` (a
+    ``PosteriorPaths`` set) the density exp(f_s(x) / temp) over the unit cube, f_s in the snapshot's physical units.
+
+    S x ``chains_per_path`` chains run as ONE batch on the device (``PosteriorPaths.hmc_run``: a warm-up window or the whole
+    sampling phase is one launch), with the window cuts (25 / 50 / 75 / 100 % of the warm-up) and the dual-averaging
+    restarts of the device branch of ``sample_GP_NUTS``.  The diagonal mass matrix and the lost-chain cull are pooled PER
+    PATH: paths differ in shape, so a path's chains share one inverse mass and a lost chain restarts from a healthy chain
+    of its own path.  Starts: ``init`` (shape (R, d), the same for every path, or (S, R, d); unit-cube coordinates), else per
+    path the best training point of the set's GP and R - 1 ``get_random_point`` draws.  ``warmup_steps``, ``num_samples``,
+    ``thinning``: ``get_hmc_settings``; every path returns n = max(1, num_samples // thinning) samples.  ``rng``: a NumPy
+    generator or a seed.  A classifier gate set on the GP at call time applies (the gate is not part of the snapshot).
+
+    Returns ``{'x': (S, n, d), 'logp': (S, n) - y_mean + y_std f_s at the samples -, 'best': (S, d), 'method': 'MCMC-paths'}``."""
+    S, d = int(paths.n_paths), int(paths.ndim)
+    init = _check_paths_hmc_args(S, d, chains_per_path, warmup_steps, num_samples, thinning, temp, init)
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    warmup_steps, num_samples, thinning = get_hmc_settings(d, warmup_steps, num_samples, thinning)
+    warmup_steps, num_samples, thinning = int(warmup_steps), int(num_samples), int(thinning)
+    R = int(chains_per_path)
+    P = S * R
+    n_keep = max(1, num_samples // thinning)
+    keep_per_chain = -(-n_keep // R)
+    path_index = np.repeat(np.arange(S, dtype=np.int64), R)
+    if init is None:
+        gp = paths.gp
+        best = gp.train_x[int(np.argmax(gp.train_y))]
+        init = np.empty((S, R, d))
+        for s in range(S):
+            init[s, 0] = np.clip(best + 1e-3 * rng.normal(size=d), 1e-6, 1 - 1e-6)
+            for r in range(1, R):
+                init[s, r] = gp.get_random_point(rng=rng)
+    X0 = np.clip(init.reshape(P, d), 1e-6, 1.0 - 1e-6)
+    U = np.log(X0) - np.log1p(-X0)
+    state = paths.hmc_state(U, path_index, temp)
+    adapt = np.tile(np.array([0.1, math.log(1.0), 0.0, 0.0, 0.0]), (P, 1))
+    inv_mass = np.ones((P, d))
+    seed = int(rng.integers(0, 2 ** 62))
+    cuts = sorted({int(warmup_steps * f) for f in (0.25, 0.5, 0.75)} | {warmup_steps})
+    it = 0
+    for cut in cuts:
+        n_it = cut - it
+        if n_it <= 0:
+            continue
+        last = cut == warmup_steps
+        hist, _, _ = paths.hmc_run(state, adapt, inv_mass, path_index, seed, it, n_it, True, temp,
+                                   hist_from=None if last else n_it // 2)
+        it = cut
+        _pool_paths_window(state, adapt, hist, inv_mass, S, rng, cull_lost_chains, not last)
+        if not last:                                           # restarted dual averaging for the new metric
+            adapt[:, 1] = np.log(10.0 * adapt[:, 0])
+            adapt[:, 2:5] = 0.0
+    if warmup_steps > 0:                                       # the averaged step size of the warm-up
+        adapt[:, 0] = np.where(adapt[:, 3] != 0.0, np.clip(np.exp(adapt[:, 3]), 1e-4, 2.0), adapt[:, 0])
+    if isinstance(diagnostics, dict):
+        diagnostics.update(eps=adapt[:, 0].copy(), inv_mass=inv_mass.copy(), state=state.copy(), adapt=adapt.copy(),
+                           seed=seed, it=it, path_index=path_index.copy())
+    _, keep, _ = paths.hmc_run(state, adapt, inv_mass, path_index, seed, it, keep_per_chain * thinning, False, temp,
+                               thin=thinning)
+    keep = keep.reshape(keep_per_chain, S, R, d + 1).transpose(1, 0, 2, 3).reshape(S, keep_per_chain * R, d + 1)[:, :n_keep]
+    x, logp = np.ascontiguousarray(keep[:, :, :d]), np.ascontiguousarray(keep[:, :, d])
+    if isinstance(diagnostics, dict):                          # (per-chain means: the tests' standard errors)
+        diagnostics.update(chains_per_path=R, keep_per_chain=keep_per_chain)
+    best = x[np.arange(S), np.argmax(logp, axis=1)]
+    return {"x": x, "logp": logp, "best": best, "method": "MCMC-paths"}
+
+
+def path_posterior_summary(samples, param_bounds=None) -> Dict:
+    """Moments of the per-path posteriors ``sample_paths_hmc`` returns (its dict, or an (S, n, d) array of samples in the
+    unit cube; ``param_bounds`` (2, d) maps them to physical parameters first): ``mean`` (S, d), ``cov`` (S, d, d) and
+    ``std`` (S, d) per path, and the surrogate-induced uncertainty of the constraints - ``mean_of_means`` (d,),
+    ``std_of_means`` (d,) and ``std_of_stds`` (d,), the across-path standard deviations (ddof 1; 0 for a single path) of
+    the per-path means and marginal standard deviations - with ``mean_of_stds`` (d,) and ``n_paths``."""
+    x = np.asarray(samples["x"] if isinstance(samples, dict) else samples, dtype=np.float64)
+    if x.ndim != 3 or x.shape[1] < 2:
+        raise ValueError(f"samples must have shape (S, n >= 2, d), not {x.shape}")
+    S, n, d = x.shape
+    if param_bounds is not None:
+        b = np.asarray(param_bounds, dtype=np.float64)
+        if b.shape != (2, d):
+            raise ValueError(f"param_bounds must have shape (2, {d}), not {b.shape}")
+        x = b[0] + x * (b[1] - b[0])
+    mean = x.mean(axis=1)
+    dev = x - mean[:, None, :]
+    cov = np.einsum("sni,snj->sij", dev, dev) / (n - 1)
+    std = np.sqrt(np.einsum("sii->si", cov))
+    ddof = 1 if S > 1 else 0
+    return {"mean": mean, "cov": cov, "std": std, "mean_of_means": mean.mean(axis=0), "std_of_means": mean.std(axis=0, ddof=ddof),
+            "mean_of_stds": std.mean(axis=0), "std_of_stds": std.std(axis=0, ddof=ddof), "n_paths": S}

@@ -311,7 +311,22 @@ int bobe_gp_posterior_sample(bobe_gp_t* gp, const double* Xq, int64_t C, int64_t
  *     point, its path index and the centred flag alone - not on T, the other points of the call, the pointer kinds or a NULL
  *     output.  The first call of a set transposes V_c once (8 S Np bytes, freed with the set).  BOBE_ERR_ARG for T < 1, a NULL
  *     p / Xq / path_idx, both outputs NULL, or an index out of range.
- * NOT gated (like bobe_gp_predict_cov).  eval / argmax: BOBE_ERR_ARG for C < 1 or a NULL pointer. */
+ *   hmc_run: whole HMC chains on a PATH - bobe_gp_hmc_run (below) in every respect but the target and the mass matrix.  Chain
+ *     c < P samples the posterior implied by the draw s = path_idx[c]: with f and df as under `grad` (uncentred),
+ *       mean slot of state / keep = y_mean + y_std f(x),   logp(u) = mean / temp + sum_k [log x_k + log(1 - x_k)],  u = logit(x).
+ *     state [P][3d+2], adapt [P][5], hist, keep, dbg, the trajectory lengths, the dual averaging and the random-number layout
+ *     are bobe_gp_hmc_run's (a counter hash of (seed, chain, it0 + iteration, index)).  inv_mass is PER CHAIN, [P][d]: paths
+ *     differ in shape and the caller pools the spread per path.  One launch runs `niter` whole trajectories of all P chains;
+ *     the coefficients c_n = V_c[n][s] + alpha_n are formed once per launch and kept with the training rows in registers and
+ *     LDS; thread tau adds its kernel terms and then its features in ascending order, the sums take bobe_gp_hmc_run's tree.
+ *     GATED by the PARENT handle's gate as it is set at call time (the gate is not part of the snapshot): an infeasible point
+ *     has mean = minus_inf and no gradient, and is never accepted.  Invariance: a chain's bits depend on the set, its path
+ *     index, its own state / adapt / inv_mass rows, the seed, its chain number and the iteration numbers - not on P, the
+ *     other chains' paths or where launches are cut.  All pointers are HOST memory (a device pointer: BOBE_ERR_ARG);
+ *     path_idx is checked against [0, S).  BOBE_ERR_ARG for P < 1, niter < 1, it0 < 0, temp <= 0, thin < 1, hist_from outside
+ *     [0, niter], a NULL p / path_idx / state / adapt / inv_mass, or an index out of range.  Shares the transposed V_c with
+ *     `grad`.  y_std, y_mean: the units of the snapshot (the caller's: the set does not keep them).
+ * eval / argmax / grad are NOT gated (like bobe_gp_predict_cov).  eval / argmax: BOBE_ERR_ARG for C < 1 or a NULL pointer. */
 typedef struct bobe_paths bobe_paths_t;
 int bobe_gp_paths_create(bobe_gp_t* gp, int64_t S, int64_t F, uint64_t seed, const double* u, const double* phase,
                          const double* w, const double* eps, bobe_paths_t** out);
@@ -320,6 +335,10 @@ int bobe_gp_paths_eval(bobe_paths_t* p, const double* Xq, int64_t C, int centere
 int bobe_gp_paths_argmax(bobe_paths_t* p, const double* Xq, int64_t C, const double* bias, int64_t* idx, double* best);
 int bobe_gp_paths_grad(bobe_paths_t* p, const double* Xq, int64_t T, const int64_t* path_idx, int centered, double* f,
                        double* df);
+int bobe_gp_paths_hmc_run(bobe_paths_t* p, int64_t P, const int64_t* path_idx, double* state, double* adapt,
+                          const double* inv_mass /* P x d */, uint64_t seed, int64_t it0, int niter, int do_adapt,
+                          double y_std, double y_mean, double temp, int hist_from, double* hist, int thin, double* keep,
+                          double* dbg);
 void bobe_gp_paths_destroy(bobe_paths_t* p);
 
 /* EI.fun / LogEI.fun (acquisition.py:226-253, 318-330) for C points: out[c] = +EI (mode 0) or
@@ -584,6 +603,9 @@ int bobe_debug_mfma_peak(int device, int waves_per_simd, double* tflops);
  * D = 8, 16 or 32; out[j] = sum over the lanes of component j by the all-components butterfly, out[D + j] = the same by the
  * single-value sum. */
 int bobe_debug_wave_sums(int device, int D, const double* in, double* out);
+/* where a chain workgroup of bobe_gp_paths_hmc_run keeps this set's training rows: info4 = rows in registers, rows in LDS,
+ * rows streamed from L2 in every step, features per thread (tests prove with it that they cover every home) */
+int bobe_debug_paths_chain_layout(bobe_paths_t* p, int* info4);
 /* candidate chunk size of the sweep (multiple of 128); 0 returns to the defaults (8192; 32 768 on the substitution path of an
  * ill-conditioned factor) */
 int bobe_gp_set_chunk(bobe_gp_t* gp, int64_t chunk);
