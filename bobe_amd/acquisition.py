@@ -236,12 +236,19 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
 
     def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 100, n_restarts: int = 1, verbose: bool = True,
                        early_stop_patience: int = 25, rng=None):
+        """``acq_kwargs['weighted_polish'] = R`` (default 0: the pool pick, as ever) carries a weighted pick - IMIQR / EIV, or
+        integration points with log-weights - to the continuum: ``_polished_point``."""
         acq_kwargs = acq_kwargs if acq_kwargs is not None else {}
+        polish = _weighted_polish(acq_kwargs)
         mc_points, log_weights = self._integration_points(acq_kwargs, rng)
+        if polish > 0 and self._weighted(log_weights):
+            vals, idx = self.sweep(gp, mc_points, mc_points, log_weights=log_weights)      # every score: the starts come from them
+            return self._polished_point(gp, np.asarray(mc_points), log_weights, np.asarray(vals), int(idx), polish,
+                                        int(acq_kwargs.get("weighted_polish_maxiter", 100)))
         best_val, idx = self.sweep_best(gp, mc_points, mc_points, log_weights=log_weights)   # candidates == integration points
         best_x = np.array(mc_points[idx])
         if self._weighted(log_weights):
-            # (the score gradients - bobe_gp_wip_grad - exist for equal-weight WIPV / WIPStd only)
+            # (without acq_kwargs['weighted_polish'] the weighted scores stay on the pool)
             if not self._pool_only_logged:                 # (once per acquisition object: BOBE.run makes one per stage)
                 log.info(f"{self.name}: weighted scores pick from the candidate pool, without the L-BFGS polish")
                 self._pool_only_logged = True
@@ -255,6 +262,37 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
         return self.acq_optimize(vg, num_params=gp.ndim, x0=best_x, bounds=[0, 1],
                                  optimizer_options=dict(self.optimizer_options), maxiter=maxiter,
                                  n_restarts=n_restarts, verbose=verbose)
+
+    def _polished_point(self, gp, mc_points, log_weights, vals, idx, n_starts, maxiter):
+        """``weighted_polish`` = R > 0: SciPy's L-BFGS-B on the score over the unit cube from the R pool rows with the lowest
+        score (ties: the lower index), all runs in lock step (the drivers of optim.py) - every round ONE ``GP.wip_grad_w``
+        call on the points still waiting, this criterion alone.  Returns the lowest value among the restarts that finished and
+        the pool pick itself; ties go to the pool pick, then to the lower restart; a restart that raised or ended non-finite is
+        skipped - never worse than the pool pick.  Nothing is drawn from a generator.  A design above the entry's limit on N
+        keeps the pool pick (one log line).  Not gated (nor is the equal-weight polish)."""
+        from .optim import _minimize_concurrently
+        best_x, best_val = np.array(mc_points[idx]), float(vals[idx])
+        if gp.train_x.shape[0] > WIP_GRAD_W_MAX_N:
+            log.info(f"{self.name}: {gp.train_x.shape[0]} training points exceed bobe_gp_wip_grad_w's limit of "
+                     f"{WIP_GRAD_W_MAX_N}; the pick stays on the candidate pool")
+            return best_x, best_val
+        d, key = mc_points.shape[1], self._key
+        order = np.argsort(vals, kind="stable")[:min(int(n_starts), len(vals))]
+        starts = np.clip(np.asarray(mc_points[order], dtype=np.float64), 0.0, 1.0)
+
+        def batch(ids, xs):
+            r = gp.wip_grad_w(np.array(xs, dtype=np.float64).reshape(len(ids), d), mc_points, log_weights=log_weights,
+                              criteria=(key,))
+            return [(float(f), np.array(g, dtype=np.float64)) for f, g in zip(r[key], r["d" + key])]
+
+        results = _minimize_concurrently(batch, starts, True, with_ids=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * d,
+                                         options={"maxiter": int(maxiter)})
+        for res in results:
+            if isinstance(res, Exception) or res is None or not np.isfinite(res.fun) or not np.all(np.isfinite(res.x)):
+                continue
+            if float(res.fun) < best_val:
+                best_x, best_val = np.clip(np.array(res.x, dtype=np.float64), 0.0, 1.0), float(res.fun)
+        return best_x, best_val
 
 
 class WIPV(WeightedIntegratedPosteriorBase):
@@ -272,14 +310,15 @@ class WIPStd(WeightedIntegratedPosteriorBase):
 class IMIQR(WeightedIntegratedPosteriorBase):
     """The integrated median interquartile range of the lognormal likelihood estimate exp(f) (Jarvenpaa, Gutmann, Vehtari,
     Marttinen, Bayesian Analysis 2021; no counterpart in the reference): ``log sum_z e^{a_z} 2 sinh(u sqrt(v+))``, of which
-    WIPStd is the small-sigma linearisation.  Picks from the candidate pool."""
+    WIPStd is the small-sigma linearisation.  Picks from the candidate pool; ``acq_kwargs['weighted_polish']`` refines the pick."""
     name: str = "IMIQR"
     _key = "imiqr"
 
 
 class EIV(WeightedIntegratedPosteriorBase):
     """The expected integrated variance of exp(f) (same paper), as the negative log of the candidate's gain R(c): EIV = S -
-    R(c) with log S = ``wip_sweep(...)['log_eiv_total']``.  Picks from the candidate pool."""
+    R(c) with log S = ``wip_sweep(...)['log_eiv_total']``.  Picks from the candidate pool; ``acq_kwargs['weighted_polish']`` refines
+    the pick."""
     name: str = "EIV"
     _key = "eiv"
 
@@ -437,6 +476,17 @@ def _ts_polish(acq_kwargs, mode) -> int:
         raise ValueError(f"ts_polish must be a non-negative integer, not {r!r}")
     if int(r) > 0 and mode == "posterior":
         raise ValueError("ts_polish needs ts_mode='max': a Gumbel-max draw from a pool has no continuum form")
+    return int(r)
+
+
+WIP_GRAD_W_MAX_N = 4096         # bobe_gp_wip_grad_w's limit on the training points (its matrix-vector chain has no tile path)
+
+
+def _weighted_polish(acq_kwargs) -> int:
+    """``acq_kwargs['weighted_polish']``: starts of the L-BFGS-B polish of a weighted pick, an integer 0 (default: none) ... 16"""
+    r = acq_kwargs.get("weighted_polish", 0)
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= 16:
+        raise ValueError(f"weighted_polish must be an integer between 0 and 16, not {r!r}")
     return int(r)
 
 

@@ -211,6 +211,7 @@ class BOBE:
         self.wip_batch_mode = "believer"
         self.mc_weighted = False
         self.ts_polish = 0
+        self.weighted_polish = 0
         self.ts_chain_steps, self.ts_chain_warmup = 0, 50
         self.min_delta_seen = np.inf
         self.current_iteration = 0
@@ -583,7 +584,7 @@ class BOBE:
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
             mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
             ts_polish: int = 0, ts_chain_steps: int = 0, ts_chain_warmup: int = 50, path_posterior: int = 0,
-            wip_batch_mode: str = "believer") -> dict:
+            weighted_polish: int = 0, wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
@@ -606,7 +607,11 @@ class BOBE:
         ``path_posterior`` - K > 0: after the run, K posterior paths of the final surrogate are sampled
         (``samplers.sample_paths_hmc`` with the run's HMC settings) and ``results['path_posterior']`` holds
         ``samplers.path_posterior_summary`` of them in physical parameters - how far the constraints move between plausible
-        surrogates; its generator is seeded by one draw from the run's, taken only when K > 0 (0, the default: no key, no draw).
+        surrogates; its generator is seeded by one draw from the run's, taken only when K > 0 (0, the default: no key, no draw),
+        and ``weighted_polish`` - for ``acq`` 'imiqr' / 'eiv' and for ``mc_weighted=True``: R in 1 .. 16 hands
+        ``acq_kwargs['weighted_polish'] = R`` to the acquisition, which then refines its pool pick by L-BFGS-B on the score from
+        the R best pool rows (``GP.wip_grad_w``; never worse than the pool pick, nothing drawn from the run's generator); 0
+        (default): the pool pick, and an ``acq_kwargs`` without the key.
         ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
         samples.  ``acq`` may be a tuple of stages, run one after the other on the
@@ -644,6 +649,10 @@ class BOBE:
         if isinstance(ts_polish, bool) or int(ts_polish) != ts_polish or int(ts_polish) < 0:
             raise ValueError(f"ts_polish must be a non-negative integer, not {ts_polish!r}")
         self.ts_polish = int(ts_polish)
+        if isinstance(weighted_polish, bool) or not isinstance(weighted_polish, (int, np.integer)) \
+                or not 0 <= int(weighted_polish) <= 16:
+            raise ValueError(f"weighted_polish must be an integer between 0 and 16, not {weighted_polish!r}")
+        self.weighted_polish = int(weighted_polish)
         for name, v in (("ts_chain_steps", ts_chain_steps), ("ts_chain_warmup", ts_chain_warmup),
                         ("path_posterior", path_posterior)):
             if isinstance(v, bool) or int(v) != v or int(v) < 0:
@@ -806,6 +815,8 @@ class BOBE:
             acq_kwargs = {"mc_samples": self.mc_samples, "mc_points_size": self.mc_points_size}
             if self.ts_polish > 0:
                 acq_kwargs["ts_polish"] = self.ts_polish
+            if self.weighted_polish > 0:
+                acq_kwargs["weighted_polish"] = self.weighted_polish
             if self.ts_chain_steps > 0:
                 acq_kwargs.update(ts_mode="posterior", ts_chain_steps=self.ts_chain_steps,
                                   ts_chain_warmup=self.ts_chain_warmup)

@@ -1,5 +1,5 @@
-// Kernels of the importance-weighted scoring pass (bobe_gp_wip_sweep_w, bobe_gp_wip_select_batch_w; gfx950).  Included by
-// gp_criteria.hip only.
+// Kernels of the importance-weighted scoring pass (bobe_gp_wip_sweep_w, bobe_gp_wip_select_batch_w) and of the scores' input
+// gradients (bobe_gp_wip_grad_w, at the end of the file); gfx950.  Included by gp_criteria.hip only.
 //
 // The sweep scores candidate c against integration point z through the fantasy variance v+(z|c) (k_wip_score,
 // sweep_kernels.hpp).  Here every z also carries a log-weight l_z (the log of its quadrature weight under the flat prior on
@@ -211,6 +211,359 @@ __global__ __launch_bounds__(256) void k_wip_score_w(const double* __restrict__ 
     };
     if (do_i) out_i[c] = fold(2);
     if (do_e) out_e[c] = -fold(4);
+  }
+}
+
+// ---- input gradients of the four scores for a HANDFUL of candidates (bobe_gp_wip_grad_w) ---------------------------------
+// The few-candidate chain of bobe_gp_wip_grad (sweep_kernels.hpp, "the same for a HANDFUL of candidates") with one stage more.
+// Each score is a function of the v+_z alone, so d score_k / dx_j = sum_z rho^k_z d v+_z / dx_j with
+//   rho^0 = omega_z        rho^1 = omega_z / (2 sqrt(v+))        rho^3 = exp(e_z - v+ + eiv)
+//   rho^2 = exp(t_z - imiqr) coth(x) u / (2 sqrt(v+)),  t_z = a_z + x + log1p(-e^{-2x}),  x = u sqrt(v+)
+// The two softmax weights need the candidate's FINISHED log-sum-exp over all z (exponents reach 1e5 at y_std ~ 4e3: only
+// exp(t - LSE) <= 1 is ever formed), which the single pass of k_wg_cross cannot supply: it forms the weights while it forms v+.
+// So k_wg_cross_w stops at cross_z, v+_z, the floored flag and one (maximum, sum) pair per workgroup, k_wg_weights_w folds
+// the pairs, forms rho^k w1 (w1 = d v+ / d cross, w2 = d v+ / d s: k_wg_cross's) and the z-side sums, k_wg_rows_w contracts
+// q = W_Z (rho^k w1) with T[j][n] for every requested criterion in one read of W_Z, k_wg_final_w combines.  A floored z is a
+// constant: it contributes its value and no gradient.  No atomics, every sum in a fixed order that depends on the
+// candidate alone - not on C, its place in the group, the pointer kinds or the other criteria requested.
+constexpr int WGW_ROWS = 4;                 // training points per k_wg_rows_w workgroup (k_wg_rows' WG_ROWS)
+constexpr int WGW_ZS = 2 + MAX_D;           // doubles per (candidate, criterion) of k_wg_weights_w: sum rho w2, the score, Dz[j]
+
+struct WgwOut {
+  double* score[4];
+  double* grad[4];
+};
+
+// k_wg_cross up to the per-z quantities: one workgroup = 64 integration points (lane) x 4 interleaved quarters of the
+// training points (wave), v in LDS, eight rows in flight.  Writes cross_z, v+_z (floored, times y_std^2) and the floored flag
+// (padding: 0, 0, 1), s_c (workgroup 0), and - mask bits 2 / 3 - the workgroup's (maximum, sum of exp(t - maximum)) of the
+// IMIQR / EIV terms into pairs[(c * gridDim.x + blockIdx.x) * 4 + {0, 1} / {2, 3}]; a workgroup without a point: (-inf, 0).
+template <int KERN, int DCAP>
+__global__ __launch_bounds__(256) void k_wg_cross_w(const double* __restrict__ ZsT, int64_t ldz, int64_t m,
+                                                    const double* __restrict__ VZ, int64_t ldw, int64_t n, int64_t np,
+                                                    const double* __restrict__ v, const double* __restrict__ cand, Hyper h,
+                                                    double kself, const double* __restrict__ basez, double ystd2,
+                                                    const double* __restrict__ zt, int64_t ldt, int mask,
+                                                    double* __restrict__ crossA, double* __restrict__ vplusA,
+                                                    double* __restrict__ flagA, int64_t lda, double* __restrict__ sA,
+                                                    double* __restrict__ pairs) {
+  extern __shared__ double kcs[];                 // [n]: v = L^-1 k_c
+  __shared__ double red[4], redz[4][64], fold[256];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t c = blockIdx.y;
+  v += c * np;
+  double sq = 0.0;
+  for (int64_t i = t; i < n; i += 256) {
+    const double vi = v[i];
+    kcs[i] = vi;
+    sq += vi * vi;
+  }
+  sq = wave_sum(sq);
+  if (lane == 0) red[wave] = sq;
+  __syncthreads();
+  const double s = kself - ((red[0] + red[1]) + (red[2] + red[3]));
+  const bool sbad = !(s >= 0.0);
+  const int64_t z = (int64_t)blockIdx.x * 64 + lane;
+  double acc = 0.0;
+  {
+    const double* wp = VZ + z;
+    int64_t i = wave;
+    for (; i + 28 < n; i += 32) {                 // eight rows in flight per thread
+      double w8[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) w8[q] = wp[(i + 4 * q) * ldw];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc = __builtin_fma(w8[q], kcs[i + 4 * q], acc);
+    }
+    for (; i < n; i += 4) acc = __builtin_fma(wp[i * ldw], kcs[i], acc);
+  }
+  redz[wave][lane] = acc;
+  __syncthreads();
+  if (wave != 0 && !(mask & 12)) return;          // (uniform per wave; the two maxima below are folded by the whole workgroup)
+  const double wk = (redz[0][lane] + redz[1][lane]) + (redz[2][lane] + redz[3][lane]);
+  double cross = 0.0, vs = 0.0, fl = 1.0, ti = -INFINITY, te = -INFINITY;
+  if (wave == 0 && z < m) {
+    double r2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) {
+      const double dz = (j < h.d) ? ZsT[j * ldz + z] - cand[c * h.d + j] / h.ls[j] : 0.0;
+      r2 += dz * dz;
+    }
+    cross = kern_eval<KERN>(r2, h.kvar) - wk;
+    double vp = basez[z] - (cross * cross) / s;
+    bool floored = sbad;
+    if (vp != vp) floored = true;
+    if (vp < NOISE_FLOOR) floored = true;
+    if (floored) vp = NOISE_FLOOR;
+    vs = vp * ystd2;
+    fl = floored ? 1.0 : 0.0;
+    if (mask & 4) {
+      const double x = IMIQR_U * sqrt(vs);
+      ti = zt[ldt + z] + x + log1p(-exp(-2.0 * x));
+    }
+    if (mask & 8) te = zt[3 * ldt + z] - vs;
+  }
+  if (wave == 0) {
+    crossA[c * lda + z] = cross;
+    vplusA[c * lda + z] = vs;
+    flagA[c * lda + z] = fl;
+    if (blockIdx.x == 0 && lane == 0) sA[c] = s;
+  }
+  // the pairs: the maximum is exact in any order (block_fold256 over wave 0's terms, -inf elsewhere), the sum of
+  // exp(t - maximum) <= 1 runs in chain_wave_sum's order
+  double* pp = pairs + (c * gridDim.x + blockIdx.x) * 4;
+  const bool in = wave == 0 && z < m;
+  if (mask & 4) {                                 // uniform
+    const double mx = block_fold256<true>(fold, ti);
+    if (wave == 0) {
+      const double sm = chain_wave_sum(in ? exp(ti - mx) : 0.0);
+      if (lane == 0) {
+        pp[0] = mx;
+        pp[1] = (mx == -INFINITY) ? 0.0 : sm;
+      }
+    }
+  }
+  if (mask & 8) {
+    const double mx = block_fold256<true>(fold, te);
+    if (wave == 0) {
+      const double sm = chain_wave_sum(in ? exp(te - mx) : 0.0);
+      if (lane == 0) {
+        pp[2] = mx;
+        pp[3] = (mx == -INFINITY) ? 0.0 : sm;
+      }
+    }
+  }
+}
+
+// One workgroup of 256 per candidate: the workgroups' pairs -> imiqr, eiv (ascending workgroup order: the maximum, then the
+// sum of s_w exp(m_w - maximum)); then, criterion by criterion (mask), thread t owning z = t, t + 256, ...: rho^k_z, the
+// weight vector rho^k w1 into wv[(vidx * ctot + c) * lda + z] (vidx: the criterion's rank among the requested ones; padding
+// and floored z: 0), and this thread's share of sum rho w2, of the value (criteria 0, 1) and of Dz[j] = sum rho w1 G_z (s_zj -
+// s_xj) - G_z and the differences recomputed from ZsT.  The shares are summed lanes first (chain_wave_sum), then the four waves
+// in order.  zs[(c * 4 + k) * WGW_ZS + ...]: sum rho w2, the score, Dz[j].
+// equal: no log-weights were given - omega_z is 1 / M itself, not the table's (the same bits for a finite state: a_z = -mu_z +
+// mu_z = 0 exactly; on a NaN state - alpha is NaN then - wipv / wipstd stay at the floor with zero gradients, as
+// bobe_gp_wip_grad leaves them, instead of turning NaN through mu_z).
+template <int KERN, int DCAP>
+__global__ __launch_bounds__(256) void k_wg_weights_w(const double* __restrict__ ZsT, int64_t ldz, int64_t m, int64_t mp,
+                                                      const double* __restrict__ cand, Hyper h, double ystd2,
+                                                      const double* __restrict__ zt, int64_t ldt, int mask, int equal,
+                                                      const double* __restrict__ crossA, const double* __restrict__ vplusA,
+                                                      const double* __restrict__ flagA, int64_t lda,
+                                                      const double* __restrict__ sA, const double* __restrict__ pairs,
+                                                      int nzw, int64_t ctot, double* __restrict__ wv,
+                                                      double* __restrict__ zs) {
+  __shared__ double red[4][WGW_ZS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t c = blockIdx.x;
+  crossA += c * lda;
+  vplusA += c * lda;
+  flagA += c * lda;
+  const double s = sA[c];
+  const double inv_m = 1.0 / (double)m;
+  const double* pp = pairs + c * nzw * 4;
+  double lse[2] = {0.0, 0.0};                      // LSE of the IMIQR terms, of the EIV terms (every thread, same bits)
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    if (!(mask & (4 << r))) continue;
+    double mx = -INFINITY;
+    for (int w = 0; w < nzw; ++w) {
+      const double y = pp[w * 4 + 2 * r];
+      mx = (y > mx || y != y) ? y : mx;
+    }
+    double sm = 0.0;
+    for (int w = 0; w < nzw; ++w) {
+      const double sw = pp[w * 4 + 2 * r + 1];
+      sm += (sw == 0.0) ? 0.0 : sw * exp(pp[w * 4 + 2 * r] - mx);
+    }
+    lse[r] = mx + log(sm);
+  }
+  double xc[DCAP];
+#pragma unroll
+  for (int j = 0; j < DCAP; ++j) xc[j] = (j < h.d) ? cand[c * h.d + j] / h.ls[j] : 0.0;
+  int vidx = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (!(mask & (1 << k))) continue;              // uniform
+    double* wk = wv + (vidx * ctot + c) * lda;
+    ++vidx;
+    double s2 = 0.0, val = 0.0, dzs[DCAP];
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) dzs[j] = 0.0;
+    for (int64_t z = t; z < mp; z += 256) {
+      if (z >= m) {
+        wk[z] = 0.0;
+        continue;
+      }
+      const double cross = crossA[z], vs = vplusA[z];
+      const bool floored = flagA[z] != 0.0;
+      const double sr = sqrt(vs);
+      double rho;
+      if (k == 0) {
+        rho = equal ? inv_m : zt[2 * ldt + z];
+        val += rho * vs;
+      } else if (k == 1) {
+        const double om = equal ? inv_m : zt[2 * ldt + z];
+        rho = om / (2.0 * sr);
+        val += om * sr;
+      } else if (k == 2) {
+        const double x = IMIQR_U * sr, em = exp(-2.0 * x);
+        const double tz = zt[ldt + z] + x + log1p(-em);
+        rho = exp(tz - lse[0]) * ((1.0 + em) / (-expm1(-2.0 * x))) * (IMIQR_U / (2.0 * sr));
+      } else {
+        rho = exp(zt[3 * ldt + z] - vs - lse[1]);
+      }
+      if (floored) {
+        wk[z] = 0.0;
+        continue;
+      }
+      const double w1 = -2.0 * cross / s * ystd2, w2 = (cross * cross) / (s * s) * ystd2;
+      const double a = rho * w1;
+      wk[z] = a;
+      s2 += rho * w2;
+      double dz[DCAP];
+      double r2 = 0.0;
+#pragma unroll
+      for (int j = 0; j < DCAP; ++j) {
+        dz[j] = (j < h.d) ? ZsT[j * ldz + z] - xc[j] : 0.0;
+        r2 += dz[j] * dz[j];
+      }
+      const double kz = kern_eval<KERN>(r2, h.kvar);
+      const double ag = a * kern_grad_factor<KERN>(r2, h.kvar, kz);
+#pragma unroll
+      for (int j = 0; j < DCAP; ++j) dzs[j] = __builtin_fma(ag, dz[j], dzs[j]);
+    }
+    __syncthreads();                               // (the previous criterion's readers of red are through)
+    {
+      const double a = chain_wave_sum(s2), b = chain_wave_sum(val);
+      if (lane == 0) {
+        red[wave][0] = a;
+        red[wave][1] = b;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) {
+      if (j < h.d) {                               // uniform
+        const double a = chain_wave_sum(dzs[j]);
+        if (lane == 0) red[wave][2 + j] = a;
+      }
+    }
+    __syncthreads();
+    if (t < 2 + h.d) {
+      double r = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+      if (t == 1 && k == 2) r = lse[0];
+      if (t == 1 && k == 3) r = -lse[1];
+      zs[(c * 4 + k) * WGW_ZS + t] = r;
+    }
+  }
+}
+
+// k_wg_rows for NV weight vectors (1 .. 4) instead of the fixed pair: one workgroup = WGW_ROWS training points, one per wave;
+// lanes run over the integration points, and W_Z's row is read once whatever NV is.  partN[(c * gridDim.x + blockIdx.x) *
+// (NV + 1) * MAX_D + r * MAX_D + j]: r < NV the n-side sum Q_r[j] = sum_n q_r[n] T[j][n], r = NV ds[j] = sum_n u_n T[j][n].
+template <int KERN, int DCAP, int NV>
+__global__ __launch_bounds__(256) void k_wg_rows_w(const double* __restrict__ XsT, int64_t ldx, int64_t n, int64_t np,
+                                                   const double* __restrict__ cand, Hyper h,
+                                                   const double* __restrict__ W, int64_t ldw, int64_t mp,
+                                                   const double* __restrict__ wv, int64_t lda, int64_t ctot,
+                                                   const double* __restrict__ u, double* __restrict__ partN) {
+  __shared__ double red[4][NV + 1][DCAP];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t c = blockIdx.y;
+  u += c * np;
+  const double xl = (lane < h.d) ? cand[c * h.d + lane] / h.ls[lane] : 0.0;      // this lane's coordinate (lane = j)
+  double xc[DCAP];
+#pragma unroll
+  for (int j = 0; j < DCAP; ++j) xc[j] = (j < h.d) ? cand[c * h.d + j] / h.ls[j] : 0.0;
+  double aq[NV], au = 0.0;
+#pragma unroll
+  for (int r = 0; r < NV; ++r) aq[r] = 0.0;
+  const int64_t i = (int64_t)blockIdx.x * WGW_ROWS + wave;
+  if (i < n) {                                    // uniform per wave
+    double q[NV];
+#pragma unroll
+    for (int r = 0; r < NV; ++r) q[r] = 0.0;
+    for (int64_t z = lane; z < mp; z += 64) {
+      const double w = W[i * ldw + z];
+#pragma unroll
+      for (int r = 0; r < NV; ++r) q[r] = __builtin_fma(wv[(r * ctot + c) * lda + z], w, q[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < NV; ++r) q[r] = chain_wave_sum(q[r]);
+    double r2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) {
+      const double df = (j < h.d) ? XsT[j * ldx + i] - xc[j] : 0.0;
+      r2 += df * df;
+    }
+    const double kv = kern_eval<KERN>(r2, h.kvar);
+    const double tj = (lane < h.d) ? kern_grad_factor<KERN>(r2, h.kvar, kv) * (XsT[lane * ldx + i] - xl) : 0.0;
+#pragma unroll
+    for (int r = 0; r < NV; ++r) aq[r] = __builtin_fma(q[r], tj, aq[r]);
+    au = __builtin_fma(u[i], tj, au);
+  }
+  if (lane < DCAP) {
+#pragma unroll
+    for (int r = 0; r < NV; ++r) red[wave][r][lane] = aq[r];
+    red[wave][NV][lane] = au;
+  }
+  __syncthreads();
+  if (t < (NV + 1) * DCAP) {
+    const int k = t / DCAP, j = t % DCAP;
+    partN[(c * gridDim.x + blockIdx.x) * (NV + 1) * MAX_D + k * MAX_D + j] =
+        (red[0][k][j] + red[1][k][j]) + (red[2][k][j] + red[3][k][j]);
+  }
+}
+
+// the n-side partials of k_wg_rows_w (nnw of them, nv + 1 rows each) and the z-side sums of k_wg_weights_w -> scores and
+// gradients of candidate blockIdx.x, in k_wg_final's order: thread (j = t & 31, part = t >> 5) adds the partials part,
+// part + 8, ... of coordinate j, the eight parts are combined in order.  The outputs of criterion k at out.score[k] + c0 + c,
+// out.grad[k] + (c0 + c) d (NULL: not written).
+__global__ __launch_bounds__(256) void k_wg_final_w(const double* __restrict__ zs, const double* __restrict__ partN, int nnw,
+                                                    int nv, int mask, Hyper h, int64_t c0, WgwOut out) {
+  __shared__ double acc[8][5][32];
+  const int t = threadIdx.x, j = t & 31, part = t >> 5;
+  const int64_t c = blockIdx.x;
+  const double* pn = partN + c * nnw * (nv + 1) * MAX_D;
+  {
+    // (all rows of four partials are loaded before any is added: one row after the other, one partial per trip, left this
+    // stage waiting on (nv + 1) nnw / 8 load latencies in a row - 73 us at N = 4096 with one criterion.  Each row's sum keeps
+    // its order.)
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int nr = nv + 1;
+    int w = part;
+    for (; w + 24 < nnw; w += 32) {
+      double x[4][5];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 5; ++r) x[q][r] = (r < nr) ? pn[((w + 8 * q) * nr + r) * MAX_D + j] : 0.0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 5; ++r) a[r] += x[q][r];
+    }
+    for (; w < nnw; w += 8)
+#pragma unroll
+      for (int r = 0; r < 5; ++r) a[r] += (r < nr) ? pn[(w * nr + r) * MAX_D + j] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 5; ++r) acc[part][r][j] = a[r];
+  }
+  __syncthreads();
+  if (part != 0) return;
+  for (int r = 0; r <= nv; ++r) {                // the totals stay in LDS (column j is this thread's alone): no indexed registers
+    double v = acc[0][r][j];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) v += acc[q][r][j];
+    acc[0][r][j] = v;
+  }
+  const double dsj = (j < h.d) ? -2.0 * acc[0][nv][j] / h.ls[j] : 0.0;
+  int vidx = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (!(mask & (1 << k))) continue;
+    const double* zk = zs + (c * 4 + k) * WGW_ZS;
+    if (j == 0 && out.score[k]) out.score[k][c0 + c] = zk[1];
+    if (j < h.d && out.grad[k]) out.grad[k][(c0 + c) * h.d + j] = (zk[2 + j] - acc[0][vidx][j]) / h.ls[j] + zk[0] * dsj;
+    ++vidx;
   }
 }
 

@@ -467,6 +467,20 @@ int bobe_gp_wip_grad(bobe_gp_t* g, const double* cand, int64_t C, const double* 
   API_END
 }
 
+int bobe_gp_wip_grad_w(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                       const double* logw, double* const scores[4], double* const grads[4]) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  double* sc[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* gr[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < 4; ++k) {
+    if (scores) sc[k] = scores[k];
+    if (grads) gr[k] = grads[k];
+  }
+  return g->wip_grad_w(cand, C, Z, M, y_std, logw, sc, gr);
+  API_END
+}
+
 int bobe_gp_acq_ei(bobe_gp_t* g, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out) {
   API_BEGIN
   NEED(g && Xq && out, "NULL argument");

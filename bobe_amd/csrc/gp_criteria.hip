@@ -6,6 +6,9 @@
 // before it returns.  One buffer of the handle is written: kXZ, the sweep workspace's K(X, Z), which prepare_z fills and
 // nothing reads once prepare_z is through (the substitution path overwrites it there) - scratch, rewritten here with its
 // own bits; the handle's Z-side STATE (ZsT, V_Z, base_z and prepare_z's cache of them) is read, never written.
+// bobe_gp_wip_grad_w (values and input gradients of the four scores through bobe_gp_wip_grad's few-candidate chain) is the one
+// entry here that goes through prepare_z itself and keeps something between calls: the per-z table beside prepare_z's cache
+// (bobe_gp::zw), its workspace and its staged outputs.
 #include "gp_handle.hpp"
 
 #include "batch_kernels.hpp"
@@ -95,6 +98,143 @@ int bobe_gp::wip_sweep_w(const double* cand, int64_t C, const double* Z, int64_t
   for (int k = 0; k < 4; ++k) {
     if (argmin) argmin[k] = am[k];
     if (mins) mins[k] = mv[k];
+  }
+  return BOBE_OK;
+}
+
+// Values and input gradients of the four scores (criteria_kernels.hpp, "input gradients of the four scores").  Per group of up
+// to 16 candidates: wg_front (bobe_gp_wip_grad's first stages) -> k_wg_cross_w -> k_wg_weights_w -> k_wg_rows_w -> k_wg_final_w.
+int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                        double* const scores[4], double* const grads[4]) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
+  int mask = 0, nv = 0;
+  for (int k = 0; k < 4; ++k)
+    if (scores[k] || grads[k]) {
+      mask |= 1 << k;
+      ++nv;
+    }
+  if (!mask) throw Err(BOBE_ERR_ARG, "bobe_gp_wip_grad_w: no criterion requested (every scores[k] and grads[k] is NULL)");
+  if (N > WGW_MAX_N)
+    throw Err(BOBE_ERR_ARG, "bobe_gp_wip_grad_w: " + std::to_string(N) + " training points exceed the matrix-vector chain's " +
+                                "limit of " + std::to_string(WGW_MAX_N) + " (there is no tile path)");
+  use();
+  const int64_t Mp = round_up(M, TILE), G = std::min<int64_t>(C, 16);
+  const double kself = hyp.kvar + hyp.noise;
+  const bool cand_pinned = C <= 16 && !is_device_ptr(cand);
+  const double* cin = cand_pinned ? nullptr : fetch(cand, (size_t)C * d, in_stage);
+  prepare_z(Z, M, Mp, true);                             // ZsT, V_Z, W_Z, base_z (forget_z on a miss drops the table too)
+  // the per-z table: the handle's copy while Z, the log-weights and y_std are the ones it was made for
+  const bool host_lw = logw && !is_device_ptr(logw);
+  const bool hit = zw_valid && zw_m == M && zw_ystd == y_std && zw_has_logw == (logw != nullptr) && (!logw || host_lw) &&
+                   (!logw || std::memcmp(zw_logw.data(), logw, (size_t)M * sizeof(double)) == 0);
+  if (!hit) {
+    zw_valid = false;
+    zw.logw = logw;
+    wip_zterms(zw, M, Mp, y_std, basez.d(), true);
+    zw.logw = nullptr;
+    // (a device Z leaves prepare_z without a cache - z_seen_m < 0 - and device log-weights cannot be compared: no table kept)
+    if (z_seen_m == M && (!logw || host_lw)) {
+      zw_valid = true;
+      zw_m = M;
+      zw_ystd = y_std;
+      zw_has_logw = logw != nullptr;
+      if (logw) zw_logw.assign(logw, logw + M);
+    }
+  }
+  const int nzw = (int)(Mp / 64), nnw = (int)((N + WGW_ROWS - 1) / WGW_ROWS);
+  const size_t n_vec = (size_t)G * Np, n_a = (size_t)G * Mp;
+  const size_t n_pn = (size_t)G * nnw * (nv + 1) * MAX_D;
+  wgw_ws.ensure((6 * n_vec + (3 + 4) * n_a + 16 + (size_t)G * nzw * 4 + (size_t)G * 4 * WGW_ZS + n_pn) * sizeof(double));
+  double* kc = wgw_ws.d();
+  double* vv = kc + n_vec;
+  double* uu = vv + n_vec;
+  double* t1 = uu + n_vec;
+  double* t2 = t1 + n_vec;
+  double* t3 = t2 + n_vec;
+  double* crossA = t3 + n_vec;
+  double* vplusA = crossA + n_a;
+  double* flagA = vplusA + n_a;
+  double* wv = flagA + n_a;                         // [nv][G][Mp]
+  double* sA = wv + 4 * n_a;
+  double* pairs = sA + 16;
+  double* zs = pairs + (size_t)G * nzw * 4;
+  double* pn = zs + (size_t)G * 4 * WGW_ZS;
+  // outputs: a device pointer is written directly; the host ones share one block, requested arrays back to back - the pinned
+  // result block (128 doubles, written by the last stage itself: no copy command) when there is no device output, one group
+  // and they fit, else a staged block that ONE copy brings back
+  size_t n_out = 0;
+  bool any_dev = false;
+  WgwOut out;
+  size_t off_s[4] = {0, 0, 0, 0}, off_g[4] = {0, 0, 0, 0};
+  for (int k = 0; k < 4; ++k) {
+    any_dev = any_dev || is_device_ptr(scores[k]) || is_device_ptr(grads[k]);
+    if (scores[k] && !is_device_ptr(scores[k])) { off_s[k] = n_out; n_out += (size_t)C; }
+    if (grads[k] && !is_device_ptr(grads[k])) { off_g[k] = n_out; n_out += (size_t)C * d; }
+  }
+  const bool packed = C <= 16 && n_out <= 128 && !any_dev;
+  double* base = h_res;
+  if (!packed && n_out) {
+    wgw_out.ensure(n_out * sizeof(double));
+    base = wgw_out.d();
+  }
+  for (int k = 0; k < 4; ++k) {
+    out.score[k] = !scores[k] ? nullptr : (is_device_ptr(scores[k]) ? scores[k] : base + off_s[k]);
+    out.grad[k] = !grads[k] ? nullptr : (is_device_ptr(grads[k]) ? grads[k] : base + off_g[k]);
+  }
+  const Hyper& h = hyp;
+  for (int64_t c0 = 0; c0 < C; c0 += 16) {
+    const int64_t g = std::min<int64_t>(16, C - c0);
+    double* cdev = nullptr;
+    const double* cfirst;
+    const double* clater;
+    if (cand_pinned) {                              // (one group: the pinned block is written once per call)
+      if (!h_in) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_in), 16 * MAX_D * sizeof(double), hipHostMallocDefault));
+      std::memcpy(h_in, cand, (size_t)C * d * sizeof(double));
+      in_stage.ensure((size_t)16 * MAX_D * sizeof(double));
+      cdev = in_stage.d();
+      cfirst = h_in;
+      clater = cdev;
+    } else {
+      cfirst = clater = cin + c0 * d;
+    }
+    wg_front(cfirst, cdev, g, kc, vv, uu, t1, t2, t3);
+    with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
+      hipLaunchKernelGGL((k_wg_cross_w<KE, DC>), dim3((unsigned)nzw, (unsigned)g), dim3(256), (size_t)N * sizeof(double),
+                         stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)vv, clater,
+                         h, kself, (const double*)basez.d(), y_std * y_std, (const double*)zw.zt.d(), zw.ldt, mask, crossA,
+                         vplusA, flagA, Mp, sA, pairs);
+      hipLaunchKernelGGL((k_wg_weights_w<KE, DC>), dim3((unsigned)g), dim3(256), 0, stream, (const double*)ZsT.d(), Mp, M,
+                         Mp, clater, h, y_std * y_std, (const double*)zw.zt.d(), zw.ldt, mask, logw ? 0 : 1,
+                         (const double*)crossA, (const double*)vplusA, (const double*)flagA, Mp, (const double*)sA,
+                         (const double*)pairs, nzw, G, wv, zs);
+      auto rows = [&](auto NV) {
+        // (KE, DC are captured: their types carry the values)
+        hipLaunchKernelGGL((k_wg_rows_w<decltype(KE)::value, decltype(DC)::value, decltype(NV)::value>),
+                           dim3((unsigned)nnw, (unsigned)g), dim3(256), 0, stream, (const double*)XsT.d(), Np, N, Np, clater, h,
+                           (const double*)WZ.d(), Mp, Mp, (const double*)wv, Mp, G, (const double*)uu, pn);
+      };
+      switch (nv) {
+        case 1: rows(std::integral_constant<int, 1>{}); break;
+        case 2: rows(std::integral_constant<int, 2>{}); break;
+        case 3: rows(std::integral_constant<int, 3>{}); break;
+        default: rows(std::integral_constant<int, 4>{}); break;
+      }
+    });
+    hipLaunchKernelGGL(k_wg_final_w, dim3((unsigned)g), dim3(256), 0, stream, (const double*)zs, (const double*)pn, nnw, nv,
+                       mask, h, c0, out);
+    LAUNCH_CHECK();
+  }
+  const double* hb = h_res;
+  if (!packed && n_out) {
+    wgw_host.resize(n_out);
+    HIPCHK(hipMemcpyAsync(wgw_host.data(), wgw_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, stream));
+    hb = wgw_host.data();
+  }
+  sync();
+  for (int k = 0; k < 4; ++k) {
+    if (scores[k] && !is_device_ptr(scores[k])) std::memcpy(scores[k], hb + off_s[k], (size_t)C * sizeof(double));
+    if (grads[k] && !is_device_ptr(grads[k])) std::memcpy(grads[k], hb + off_g[k], (size_t)C * d * sizeof(double));
   }
   return BOBE_OK;
 }

@@ -7,7 +7,8 @@
 //   gp_posterior.hip  joint posterior covariance at query points and correlated draws from it
 //   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
 //   gp_batch.hip      one-sweep batch selection for WIPV / WIPStd (the sweep's intermediates kept, rank-one downdates)
-//   gp_criteria.hip   importance-weighted integration points, IMIQR / EIV: the weighted scoring pass of the sweep and the batch
+//   gp_criteria.hip   importance-weighted integration points, IMIQR / EIV: the weighted scoring pass of the sweep and the batch,
+//                     the input gradients of the four scores (few-candidate chain)
 //   gp_paths.hip      pathwise posterior draws of the latent surrogate (random Fourier features + Matheron's rule): path
 //                     sets, their evaluation at query points and per-path argmax
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
@@ -350,7 +351,15 @@ struct bobe_gp {
   std::vector<double> z_seen;
   int64_t z_seen_m = -1;
   bool wz_ready = false;        // W_Z = K^-1 K(X,Z) (the score GRADIENTS need it; the sweep itself does not)
-  void forget_z() { z_seen_m = -1; wz_ready = false; }
+  void forget_z() { z_seen_m = -1; wz_ready = false; zw_valid = false; }
+  // bobe_gp_wip_grad_w keeps the weighted scorer's per-z table (mu, a, omega, e, l) beside them: valid while prepare_z's cache
+  // is valid AND the log-weights (host memory; device ones are never taken as seen) have the same bytes, or are absent
+  // again, and y_std is the same.  A hit launches neither wip_zterms' K(X,Z) assembly nor k_wip_zterms.
+  bobe::SweepW zw;              // (its buffers are released with the handle)
+  bool zw_valid = false, zw_has_logw = false;
+  std::vector<double> zw_logw;
+  double zw_ystd = 0.0;
+  int64_t zw_m = -1;
   int64_t chunk = 8192;
   bool chunk_set = false;       // bobe_gp_set_chunk was called: the caller's chunk holds for the substitution path too
 
@@ -360,6 +369,8 @@ struct bobe_gp {
   int num_cus = 0;
   // sweep / predict workspace
   DBuf wg_ws;     // workspace of bobe_gp_wip_grad's few-candidates path
+  DBuf wgw_ws, wgw_out;   // workspace and staged outputs of bobe_gp_wip_grad_w
+  std::vector<double> wgw_host;   // where the one copy of the staged outputs lands before they go to the caller's arrays
   DBuf in_stage, z_stage, CsT, ZsT, kXC, kXZ, VZ, WZ, basez, sc, qpart, pv, ps, o_mean, o_var, o_wipv, o_wipstd,
       o_misc, kin_a, kin_b, kout, vxc, vxc2;
   // the inverse's problem table (probs) by depth: whole levels, and their leading / trailing parts (tri_split.hpp)
@@ -667,6 +678,9 @@ struct bobe_gp {
   void sweep(const bobe::SweepReq& r);
   void wip_grad(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv, double* wipstd,
                 double* dwipv, double* dwipstd);
+  // the front of the few-candidate chains: k_wg_col, solve_alpha and - refine_v - the vector refinement step
+  void wg_front(const double* cfirst, double* cdev, int64_t C, double* kc, double* vv, double* uu, double* t1, double* t2,
+                double* t3);
   void predict_grad(const double* Xq, int64_t C, double* mean, double* var, double* dmean, double* dvar);
   int append(const double* X_new, int64_t b, const double* y_all);
 
@@ -710,6 +724,10 @@ struct bobe_gp {
                   double* const outs[4], double* log_s, int64_t* argmin, double* mins);
   int wip_select_batch_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                          int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores);
+  // values and input gradients of the four scores through the few-candidate chain, in groups of 16 (WGW_MAX_N: its limit on N)
+  static constexpr int64_t WGW_MAX_N = 4096;      // (k_wg_cross_w keeps v in N doubles of LDS)
+  int wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                 double* const scores[4], double* const grads[4]);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

@@ -331,6 +331,34 @@ void bobe_gp::sweep(const SweepReq& r) {
   }
 }
 
+// The front of the few-candidate chains (bobe_gp_wip_grad, bobe_gp_wip_grad_w): k_c = k(X, c) into kc (cfirst may be pinned
+// host memory; cdev then receives the device copy of the coordinates), v = Linv k_c, u = Linv^T v and - refine_v - one step of
+// iterative refinement in vector form.  C vectors of Np each; t1 .. t3: the refinement's temporaries.
+void bobe_gp::wg_front(const double* cfirst, double* cdev, int64_t C, double* kc, double* vv, double* uu, double* t1,
+                       double* t2, double* t3) {
+  const Hyper& h = hyp;
+  const size_t n_vec = (size_t)C * Np;
+  part.ensure((size_t)C * nb * Np * sizeof(double));
+  const double* li = Linv.d();
+  with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
+    hipLaunchKernelGGL((k_wg_col<KE, DC>), dim3((unsigned)(Np / 256 + 1), (unsigned)C), dim3(256), 0, stream,
+                       (const double*)XsT.d(), Np, N, Np, cfirst, h, kc, cdev);
+  });
+  solve_alpha(li, vv, uu, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)kc, Np);
+  if (refine_v) {   // one step of iterative refinement in vector form: v += Linv (k - L v), u += Linv^T of the same
+    const unsigned gv = (unsigned)((n_vec + 255) / 256);
+    hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), (unsigned)C), dim3(256), 0, stream, (const double*)A.d(),
+                       Np, Np, (const double*)vv, t1, (int64_t)0, Np, Np);
+    hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, t1, (const double*)kc, (const double*)t1, -1.0,
+                       (int64_t)n_vec);
+    solve_alpha(li, t2, t3, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)t1, Np);
+    hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, vv, (const double*)vv, (const double*)t2, 1.0,
+                       (int64_t)n_vec);
+    hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, uu, (const double*)uu, (const double*)t3, 1.0,
+                       (int64_t)n_vec);
+  }
+}
+
 void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv,
                        double* wipstd, double* dwipv, double* dwipstd) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
@@ -380,24 +408,7 @@ void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M
     double* t2 = t1 + n_vec;
     double* t3 = t2 + n_vec;
     const Hyper& h = hyp;
-    const double* li = Linv.d();
-    with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
-      hipLaunchKernelGGL((k_wg_col<KE, DC>), dim3((unsigned)(Np / 256 + 1), (unsigned)C), dim3(256), 0, stream,
-                         (const double*)XsT.d(), Np, N, Np, cfirst, h, kc, cdev);
-    });
-    solve_alpha(li, vv, uu, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)kc, Np);
-    if (refine_v) {   // one step of iterative refinement in vector form: v += Linv (k - L v), u += Linv^T of the same
-      const unsigned gv = (unsigned)((n_vec + 255) / 256);
-      hipLaunchKernelGGL(k_gemv_lower, dim3((unsigned)(Np / 4), (unsigned)C), dim3(256), 0, stream, (const double*)A.d(),
-                         Np, Np, (const double*)vv, t1, (int64_t)0, Np, Np);
-      hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, t1, (const double*)kc, (const double*)t1, -1.0,
-                         (int64_t)n_vec);
-      solve_alpha(li, t2, t3, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)t1, Np);
-      hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, vv, (const double*)vv, (const double*)t2, 1.0,
-                         (int64_t)n_vec);
-      hipLaunchKernelGGL(k_vec_axpy, dim3(gv), dim3(256), 0, stream, uu, (const double*)uu, (const double*)t3, 1.0,
-                         (int64_t)n_vec);
-    }
+    wg_front(cfirst, cdev, C, kc, vv, uu, t1, t2, t3);
     with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
       hipLaunchKernelGGL((k_wg_cross<KE, DC>), dim3((unsigned)nzw, (unsigned)C), dim3(256), (size_t)N * sizeof(double),
                          stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)kc,

@@ -998,6 +998,35 @@ class GP:
                    "bobe_gp_wip_grad")
         return wipv, wipstd, dv, ds
 
+    def wip_grad_w(self, candidates, mc_points, *, log_weights=None, criteria=None):
+        """Values and input gradients of the weighted scores (``bobe_gp_wip_grad_w``): a dict with ``<key>`` (C,) and
+        ``d<key>`` (C, d) for every requested criterion (``criteria``: a subset of ``wipv, wipstd, imiqr, eiv``; None: all
+        four).  ``candidates`` / ``mc_points``: NumPy arrays or torch CUDA tensors.  ``log_weights`` and the units are those
+        of ``wip_sweep(log_weights=, criteria=)``: physical, the y_mean shifts of ``imiqr`` / ``eiv`` included in the values
+        (constants: the gradients do not see them).  Matrix-vector work in groups of 16 candidates, for at most 4096 training
+        points."""
+        keys = self.CRITERIA if criteria is None else tuple(criteria)
+        for k in keys:
+            if k not in self.CRITERIA:
+                raise ValueError(f"criteria must be among {self.CRITERIA}, not {k!r}")
+        cand = candidates if hasattr(candidates, "data_ptr") else _lib.as_f64(np.atleast_2d(candidates))
+        z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
+        c, m = int(cand.shape[0]), int(z.shape[0])
+        lw = self._log_weights(log_weights, m)
+        vals = [np.empty(c) if k in keys else None for k in self.CRITERIA]
+        grads = [np.empty((c, self.ndim)) if k in keys else None for k in self.CRITERIA]
+        pv = (C.c_void_p * 4)(*[_lib.ptr(a).value for a in vals])
+        pg = (C.c_void_p * 4)(*[_lib.ptr(a).value for a in grads])
+        _lib.check(self._lib.bobe_gp_wip_grad_w(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), _lib.ptr(lw),
+                                                pv, pg), "bobe_gp_wip_grad_w")
+        shift = {"wipv": 0.0, "wipstd": 0.0, "imiqr": float(self.y_mean), "eiv": -2.0 * float(self.y_mean)}
+        out = {}
+        for i, k in enumerate(self.CRITERIA):
+            if k in keys:
+                out[k] = vals[i] + shift[k] if shift[k] else vals[i]
+                out["d" + k] = grads[i]
+        return out
+
     def predict_grad(self, x, mean_only=False):
         """Standardised (mean, var, dmean/dx, dvar/dx) of ``predict_single`` (gp.py:476-489) for C points: what the
         reference gets by JAX autodiff through the GP (acquisition.py:246-253, samplers.py:268-276).

@@ -254,6 +254,24 @@ int bobe_gp_fantasy_var(bobe_gp_t* gp, const double* cand, int64_t C, const doub
 int bobe_gp_wip_grad(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                      double* wipv, double* wipstd, double* dwipv, double* dwipstd);
 
+/* bobe_gp_wip_grad for bobe_gp_wip_sweep_w's four scores (a build addition; it stands in for what the reference takes with
+ * jax.grad of the score in the local refinement, acquisition.py:385-412).  Each score is a function of the v+_z alone, and
+ * d v+_z/dx_j = y_std^2 [-2 cross_z/s d cross_z/dx_j + cross_z^2/s^2 d s/dx_j] (a z at a floor of gp.py:574-576 is a constant:
+ * zero gradient), so d score_k/dx_j = sum_z rho^k_z d v+_z/dx_j with
+ *   rho^0 = omega_z,   rho^1 = omega_z / (2 sqrt(v+)),   rho^3 = exp(e_z - v+ + eiv),   e_z = l_z + 2 mu_z + 2 b_z,
+ *   rho^2 = exp(t_z - imiqr) coth(x) u / (2 sqrt(v+)),   t_z = a_z + x + log1p(-exp(-2x)),   x = u sqrt(v+);
+ * the two softmax weights are formed against the candidate's finished log-sum-exp, so no exponent above 0 is taken.
+ * scores[k] (C each) / grads[k] (C x d each), k = 0 wipv, 1 wipstd, 2 imiqr, 3 eiv: host or device; criterion k is computed
+ * when either is non-NULL (scores / grads themselves may be NULL).  Units and logw (M, host or device, NULL: l_z = -mu_z) as
+ * in bobe_gp_wip_sweep_w: physical, no y_mean.  Matrix-vector work in groups of 16 candidates - there is no tile path - for
+ * at most 4096 training points.  A candidate's bits depend on the state, Z, logw, y_std and the candidate alone: not on C,
+ * its neighbours, the pointer kinds, the other criteria requested or the handle's caches (Z's quantities and the per-z table
+ * are kept while the same host Z, host logw and y_std arrive again).  NOT gated.
+ * BOBE_ERR_ARG: NULL cand / Z, C or M < 1, no criterion requested, more than 4096 training points; BOBE_ERR_STATE without a
+ * factorised state; a NaN state behaves as in bobe_gp_wip_grad (BOBE_OK). */
+int bobe_gp_wip_grad_w(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                       const double* logw, double* const scores[4], double* const grads[4]);
+
 /* The JOINT posterior of the latent-plus-noise process at C query points Xq (C x d), 1 <= C <= 16384 - what scikit-learn's
  * GaussianProcessRegressor.predict(return_cov=True) (plus noise I) and sample_y return; the reference has no counterpart.
  * Standardised units.  Every work buffer (V: N x C, Sigma and its factor: C x C each) belongs to the call and is freed before
