@@ -65,6 +65,8 @@ __global__ __launch_bounds__(256) void k_gate(Gate gt, const double* __restrict_
 // mean-only arithmetic).  In:  U, Pm = p0 + eps/2 * g(U)  (P x d).  Per step: u += eps * inv_mass * p; evaluate;
 // p += (eps | eps/2 on the last step) * g.  Out: U, Pm (final), logp, grad, mean (physical units), X.
 // Fixed reduction order (4 waves x lanes, then a fixed tree): a chain's trajectory does not depend on the batch.
+// (Not built from chain_common.hpp's pieces on purpose: it sums the lanes with wave_sum, not chain_wave_sum, and keeps no
+// rows resident - folding it in would move its bits.)
 template <int KERN, int DCAP>
 __global__ __launch_bounds__(256) void k_hmc_leapfrog(const double* __restrict__ XsT, int64_t ldx, int64_t n,
                                                       const double* __restrict__ alpha, Hyper h,
@@ -154,21 +156,18 @@ __global__ __launch_bounds__(256) void k_hmc_leapfrog(const double* __restrict__
   }
 }
 
-// ---- whole HMC chains on the device ---------------------------------------------------------------------------
-// `niter` trajectories of every chain in ONE launch (one workgroup = one chain): momentum draw, 4-12 leapfrog steps (the
-// arithmetic of k_hmc_leapfrog), Metropolis test, and - while warming up - the chain's own dual-averaging step-size
-// update (Hoffman & Gelman 2014, what NumPyro's warm-up does per chain).  The host only cuts the run at the
-// mass-matrix windows.  Random numbers are a counter hash (splitmix64 finaliser) of (seed, chain, iteration, index):
-// a chain's path depends on nothing but its own seed, whatever the batch or the launch boundaries.
-//   S     [P][3d+2]  chain state in/out: u (d), g = dlogp/du (d), x (d), logp, mean (physical units)
-//   adapt [P][5]     eps, mu, hbar, log_eps_bar, m (dual averaging; only eps is read when do_adapt == 0)
-//   hist  [niter - hist_from][P][d]   u after iterations >= hist_from of this launch        (may be null)
-//   keep  [niter / thin][P][d+1]      x and mean after every thin-th iteration of this launch (may be null)
-//   dbg   [P][d+3]   last iteration's p0 (d), L, uniform, acceptance probability             (may be null)
-// (hmc_mix64 / hmc_u01: kernels_common.hpp)
-
-// (ChainRows, CHAIN_LDS_BYTES, chain_lds_groups - where a chain workgroup keeps its training rows: chain_common.hpp)
-
+// ---- whole HMC chains on the posterior mean ------------------------------------------------------------------------
+// The contract (one 256-thread workgroup per chain, the state / adapt / hist / keep / dbg layouts, the random numbers, dual
+// averaging) is the comment above hmc_chain_run (chain_common.hpp), and this kernel is that body on the target of
+// k_hmc_leapfrog - coefficients alpha, one inv_mass vector for every chain, nothing beyond the training rows, multiply-adds
+// left to the compiler's contraction - written out.  It stays its OWN COPY for speed alone: built on hmc_chain_run (the
+// target would be {RMAX = ChainRows::HMC, FMA = false, coef = CoefMean, no extra terms}) it gave the same bits with fewer
+// registers, but ran 2 - 5 % slower per leapfrog step on every line of tools/paths_hmc_timing.py
+// (profiles/chain_core_unify_ab.txt), and the cause was not found.  A change to the transition is made in both places;
+// tests/test_gpu_paths_hmc.py (the same chain under both kernels) holds them together.
+// Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950), rbf / matern, with ChainRows<DCAP>::HMC = 14 / 6 / 2 rows
+// in registers: DCAP 8: 256 VGPRs + 210 / 228 AGPRs, DCAP 16: 256 + 227 / 245, DCAP 32: 256 + 220 / 230; one wave per SIMD
+// and scratch 0 in all six.  LDS: 704 / 1280 / 2432 bytes static.
 template <int KERN, int DCAP>
 __global__ __launch_bounds__(256) void k_hmc_run(const double* __restrict__ XsT, int64_t ldx, int64_t n,
                                                  const double* __restrict__ alpha, Hyper h, int64_t P,
@@ -407,10 +406,9 @@ __global__ __launch_bounds__(256) void k_hmc_run(const double* __restrict__ XsT,
 }
 
 // ---- No-U-Turn sampling on the device (NumPyro's NUTS, the reference's sampler: samplers.py:216-330) ---------------
-// `niter` NUTS transitions of every chain in ONE launch, one 256-thread workgroup per chain; the target, the state layout
-// and the one-point evaluation (training points in registers / LDS / streamed, the mean and gradient reduction order, the
-// gate) are those of k_hmc_run.  The code is duplicated rather than shared, so that k_hmc_run's instruction stream stays
-// exactly what it was.
+// `niter` NUTS transitions of every chain in ONE launch, one 256-thread workgroup per chain; the target and the state layout
+// are those of k_hmc_run, and the one-point evaluation is chain_common.hpp's (ChainTrain, chain_point, chain_reduce,
+// chain_wsum: the same rows, arithmetic, reduction order and gate).
 //
 // Contract (tests/nuts_restatement.py restates it in NumPy):
 //   Metric.  Sigma = the d x d inverse metric, C = lower Cholesky factor of M = Sigma^-1 (both from the host).  Momentum
@@ -470,7 +468,7 @@ __global__ __launch_bounds__(256) void k_nuts_run(const double* __restrict__ XsT
   __shared__ double sig[DCAP * SLD], zb[DCAP], pv[DCAP], phs[DCAP];
   __shared__ double ck_p[NUTS_MAX_DEPTH][DCAP], ck_v[NUTS_MAX_DEPTH][DCAP], ck_r[NUTS_MAX_DEPTH][DCAP];
   __shared__ int stop_leaf, stop_tree;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, wave = t >> 6;
   const int64_t c = blockIdx.x;
   const int d = h.d, sw = 3 * d + 2;
   const bool own = t < d;                      // coordinate thread (all of them in wave 0)
@@ -496,22 +494,7 @@ __global__ __launch_bounds__(256) void k_nuts_run(const double* __restrict__ XsT
     a_m = ad[4];
   }
   const unsigned long long ckey = hmc_mix64(seed ^ hmc_mix64((unsigned long long)c));
-  constexpr int RMAX = ChainRows<DCAP>::NUTS, UNR = ChainRows<DCAP>::STREAM;
-  const int nrow = (int)((n + NT - 1) / NT);
-  const int lld = NT * lgroups;
-  double cx[RMAX][DCAP], ca[RMAX];
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    const int64_t i = t + NT * r;
-    ca[r] = (i < n) ? alpha[i] : 0.0;
-#pragma unroll
-    for (int j = 0; j < DCAP; ++j) cx[r][j] = (j < d && i < n) ? XsT[j * ldx + i] : 0.0;
-  }
-  for (int q = 0; q < lgroups; ++q) {
-    const int64_t i = t + (int64_t)NT * (RMAX + q);
-    for (int j = 0; j < d; ++j) lrows[j * lld + q * NT + t] = (i < n) ? XsT[j * ldx + i] : 0.0;
-    lrows[d * lld + q * NT + t] = (i < n) ? alpha[i] : 0.0;
-  }
+  const ChainTrain<DCAP, ChainRows<DCAP>::NUTS, CoefMean> rows(XsT, ldx, n, d, CoefMean{alpha}, lrows, lgroups, t);
   __syncthreads();
   const double inv_ls = own ? 1.0 / h.ls[t] : 0.0;
   auto sig_dot = [&](const double* vec) {                    // row t of Sigma against a vector in LDS
@@ -525,58 +508,13 @@ __global__ __launch_bounds__(256) void k_nuts_run(const double* __restrict__ XsT
     double ms = 0.0, gm[DCAP];
 #pragma unroll
     for (int j = 0; j < DCAP; ++j) gm[j] = 0.0;
-    auto point = [&](const double (&xr)[DCAP], double a) {
-      double r2 = 0.0;
-#pragma unroll
-      for (int j = 0; j < DCAP; ++j) {
-        const double df = (j < d) ? xr[j] - xs[j] : 0.0;
-        r2 += df * df;
-      }
-      const double kv = kern_eval<KERN>(r2, h.kvar);
-      const double ag = a * kern_grad_factor<KERN>(r2, h.kvar, kv);
-      ms += a * kv;
-#pragma unroll
-      for (int j = 0; j < DCAP; ++j) gm[j] += ag * ((j < d) ? xr[j] - xs[j] : 0.0);
-    };
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r)
-      if (r < nrow) point(cx[r], ca[r]);
-    for (int q = 0; q < lgroups; ++q) {
-      double xr[DCAP];
-#pragma unroll
-      for (int j = 0; j < DCAP; ++j) xr[j] = (j < d) ? lrows[j * lld + q * NT + t] : 0.0;
-      point(xr, lrows[d * lld + q * NT + t]);
-    }
-    for (int64_t i = t + (int64_t)NT * (RMAX + lgroups); i < n; i += UNR * NT) {
-      double xr[UNR][DCAP], ar[UNR];
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) {
-        const int64_t iq = i + q * NT;
-        ar[q] = (iq < n) ? alpha[iq] : 0.0;
-#pragma unroll
-        for (int j = 0; j < DCAP; ++j) xr[q][j] = (j < d && iq < n) ? XsT[j * ldx + iq] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) point(xr[q], ar[q]);
-    }
-    ms = chain_wave_sum(ms);
-    if (lane == 0) red[wave][DCAP] = ms;
-    {
-      const double v = wave_sum_components<DCAP>(gm, lane);
-      if ((lane & (64 / DCAP - 1)) == 0) red[wave][lane / (64 / DCAP)] = v;
-    }
-    if (gate_on(gt)) {
-      const double gs = gate_partial<DCAP>(gt, x, d, t);
-      if (lane == 0) gred[wave] = gs;
-    }
+    double xsr[DCAP];
+    chain_load_point<DCAP>(xs, d, xsr);
+    rows.for_each([&](const double (&xr)[DCAP], double a) { chain_point<KERN, DCAP, false>(xr, a, xsr, d, h.kvar, ms, gm); });
+    chain_reduce<DCAP>(ms, gm, gt, x, d, t, red, gred);
     __syncthreads();
   };
-  auto wsum = [&](int j) {
-    double sres = red[0][j];
-#pragma unroll
-    for (int w_ = 1; w_ < NW; ++w_) sres += red[w_][j];
-    return sres;
-  };
+  auto wsum = [&](int j) { return chain_wsum(&red[0][j], DCAP + 1); };
   for (int it = 0; it < niter; ++it) {
     const unsigned long long ikey = ckey + ((unsigned long long)(it0 + it) << 14);
     const double eps = a_eps;
@@ -784,7 +722,7 @@ __global__ __launch_bounds__(256) void k_rwalk(const double* __restrict__ XsT, i
   extern __shared__ double lrows[];
   __shared__ double x[DCAP], xp[DCAP], xs[DCAP], z[DCAP], red[NW], gred[4], lx, stp[DCAP * DCAP];
   __shared__ int inside_s, na_s, ni_s;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, wave = t >> 6;
   const int64_t c = blockIdx.x;
   const int d = h.d;
   if (t < d) x[t] = X[c * d + t];
@@ -796,22 +734,7 @@ __global__ __launch_bounds__(256) void k_rwalk(const double* __restrict__ XsT, i
   }
   const unsigned long long ckey = hmc_mix64(seed ^ hmc_mix64((unsigned long long)c));
   // training points in registers, in LDS and streamed, like k_hmc_run (only the mean is needed here)
-  constexpr int RMAX = ChainRows<DCAP>::WALK, UNR = ChainRows<DCAP>::STREAM;
-  const int nrow = (int)((n + NT - 1) / NT);
-  const int lld = NT * lgroups;
-  double cx[RMAX][DCAP], ca[RMAX];
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    const int64_t i = t + NT * r;
-    ca[r] = (i < n) ? alpha[i] : 0.0;
-#pragma unroll
-    for (int j = 0; j < DCAP; ++j) cx[r][j] = (j < d && i < n) ? XsT[j * ldx + i] : 0.0;
-  }
-  for (int q = 0; q < lgroups; ++q) {
-    const int64_t i = t + (int64_t)NT * (RMAX + q);
-    for (int j = 0; j < d; ++j) lrows[j * lld + q * NT + t] = (i < n) ? XsT[j * ldx + i] : 0.0;
-    lrows[d * lld + q * NT + t] = (i < n) ? alpha[i] : 0.0;
-  }
+  const ChainTrain<DCAP, ChainRows<DCAP>::WALK, CoefMean> rows(XsT, ldx, n, d, CoefMean{alpha}, lrows, lgroups, t);
   __syncthreads();
   for (int s = 0; s < walks; ++s) {
     const unsigned long long ikey = ckey + ((unsigned long long)s << 12);
@@ -837,49 +760,13 @@ __global__ __launch_bounds__(256) void k_rwalk(const double* __restrict__ XsT, i
     }
     __syncthreads();
     if (inside_s) {                                                        // (uniform: a proposal outside costs no evaluation)
-      double ms = 0.0;
-      auto point = [&](const double (&xr)[DCAP], double a) {
-        double r2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < DCAP; ++j) {
-          const double df = (j < d) ? xr[j] - xs[j] : 0.0;
-          r2 += df * df;
-        }
-        ms += a * kern_eval<KERN>(r2, h.kvar);
-      };
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r)
-        if (r < nrow) point(cx[r], ca[r]);
-      for (int q = 0; q < lgroups; ++q) {
-        double xr[DCAP];
-#pragma unroll
-        for (int j = 0; j < DCAP; ++j) xr[j] = (j < d) ? lrows[j * lld + q * NT + t] : 0.0;
-        point(xr, lrows[d * lld + q * NT + t]);
-      }
-      for (int64_t i = t + (int64_t)NT * (RMAX + lgroups); i < n; i += UNR * NT) {
-        double xr[UNR][DCAP], ar[UNR];
-#pragma unroll
-        for (int q = 0; q < UNR; ++q) {                                // (all loads of the group first)
-          const int64_t iq = i + q * NT;
-          ar[q] = (iq < n) ? alpha[iq] : 0.0;
-#pragma unroll
-          for (int j = 0; j < DCAP; ++j) xr[q][j] = (j < d && iq < n) ? XsT[j * ldx + iq] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < UNR; ++q) point(xr[q], ar[q]);
-      }
-      ms = chain_wave_sum(ms);
-      if (lane == 0) red[wave] = ms;
-      if (gate_on(gt)) {
-        const double gs = gate_partial<DCAP>(gt, xp, d, t);
-        if (lane == 0) gred[wave] = gs;
-      }
+      double ms = 0.0, xsr[DCAP];
+      chain_load_point<DCAP>(xs, d, xsr);
+      rows.for_each([&](const double (&xr)[DCAP], double a) { chain_point_value<KERN, DCAP>(xr, a, xsr, d, h.kvar, ms); });
+      chain_reduce_value<DCAP>(ms, gt, xp, d, t, red, gred);
       __syncthreads();
       if (t == 0) {
-        double m = red[0];
-#pragma unroll
-        for (int w_ = 1; w_ < NW; ++w_) m += red[w_];
-        m = m * ystd + ymean;
+        double m = chain_wsum(red, 1) * ystd + ymean;
         if (gate_on(gt) && !gate_feasible(gt, gate_combine(gt, gred))) m = gt.minus_inf;
         const int acc = m > lstar;
         inside_s = acc;                                                    // (reused: accepted)

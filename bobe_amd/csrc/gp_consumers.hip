@@ -200,35 +200,19 @@ void bobe_gp::hmc_run(int64_t P, double* state, double* adapt, const double* inv
   if (P <= 0 || niter < 1 || it0 < 0 || !(temp > 0.0) || thin < 1 || hist_from < 0 || hist_from > niter)
     throw Err(BOBE_ERR_ARG, "bad argument");
   use();
-  const size_t sw = 3 * (size_t)d + 2, ns = (size_t)P * sw, na = (size_t)P * 5;
-  const size_t nh = hist ? (size_t)(niter - hist_from) * P * d : 0;
-  const size_t nk = keep ? (size_t)(niter / thin) * P * (d + 1) : 0;
-  const size_t nd = dbg ? (size_t)P * (d + 3) : 0;
-  // staging: state | adapt | inv_mass | hist | keep | dbg
-  in_stage.ensure((ns + na + d + nh + nk + nd) * sizeof(double));
-  double* dS = in_stage.d();
-  double* dA = dS + ns;
-  double* dI = dA + na;
-  double* dH = dI + d;
-  double* dK = dH + nh;
-  double* dD = dK + nk;
-  HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(dI, inv_mass, (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream));
+  const ChainStage st(in_stage, P, d, (size_t)d, niter, hist_from, hist != nullptr, thin, keep != nullptr, 0,
+                      dbg ? (size_t)P * (d + 3) : 0);
+  st.copy_in(stream, state, adapt, inv_mass);
   // training points of a chain's workgroup: registers first, then LDS (chain_lds_groups), the rest streamed
   with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
     const int lg = chain_lds_groups(N, d, ChainRows<DC>::HMC);
     hipLaunchKernelGGL((k_hmc_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
-                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA, (const double*)dI,
-                       (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from, hist ? dH : nullptr,
-                       thin, keep ? dK : nullptr, dbg ? dD : nullptr, gate, lg);
+                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, st.dS, st.dA,
+                       (const double*)st.dI, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from,
+                       st.dH, thin, st.dK, st.dD, gate, lg);
   });
   LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (hist) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (keep) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (dbg) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, stream));
+  st.copy_out(stream, state, adapt, hist, keep, nullptr, dbg);
   sync();
 }
 
@@ -287,37 +271,19 @@ void bobe_gp::nuts_run(int64_t P, double* state, double* adapt, const double* in
   if (!chol(Cv)) throw Err(BOBE_ERR_ARG, "the inverse of inv_metric is not positive definite");
   std::copy(Cv.begin(), Cv.end(), Cm);
   use();
-  const size_t sw = 3 * (size_t)d + 2, ns = (size_t)P * sw, na = (size_t)P * 5, nm = 2 * (size_t)d * d;
-  const size_t nh = hist ? (size_t)(niter - hist_from) * P * d : 0;
-  const size_t nk = keep ? (size_t)(niter / thin) * P * (d + 1) : 0;
-  const size_t nt = stats ? (size_t)niter * P * 4 : 0;
-  const size_t nd = dbg ? (size_t)P * d : 0;
-  // staging: state | adapt | metric | hist | keep | stats | dbg
-  in_stage.ensure((ns + na + nm + nh + nk + nt + nd) * sizeof(double));
-  double* dS = in_stage.d();
-  double* dA = dS + ns;
-  double* dM = dA + na;
-  double* dH = dM + nm;
-  double* dK = dH + nh;
-  double* dT = dK + nk;
-  double* dD = dT + nt;
-  HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(dM, met.data(), nm * sizeof(double), hipMemcpyHostToDevice, stream));
+  // (the metric, Sigma then C, goes where hmc_run stages inv_mass)
+  const ChainStage st(in_stage, P, d, met.size(), niter, hist_from, hist != nullptr, thin, keep != nullptr,
+                      stats ? (size_t)niter * P * 4 : 0, dbg ? (size_t)P * d : 0);
+  st.copy_in(stream, state, adapt, met.data());
   with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
     const int lg = chain_lds_groups(N, d, ChainRows<DC>::NUTS, NUTS_LDS_BYTES);
     hipLaunchKernelGGL((k_nuts_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
-                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, dS, dA, (const double*)dM,
-                       max_depth, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from,
-                       hist ? dH : nullptr, thin, keep ? dK : nullptr, stats ? dT : nullptr, dbg ? dD : nullptr, gate, lg);
+                       stream, (const double*)XsT.d(), Np, N, (const double*)alpha.d(), hyp, P, st.dS, st.dA,
+                       (const double*)st.dI, max_depth, (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp,
+                       hist_from, st.dH, thin, st.dK, st.dT, st.dD, gate, lg);
   });
   LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (hist) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (keep) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (stats) HIPCHK(hipMemcpyAsync(stats, dT, nt * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (dbg) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, stream));
+  st.copy_out(stream, state, adapt, hist, keep, stats, dbg);
   sync();
 }
 

@@ -3,14 +3,17 @@
 //   gp_factor.hip     K(X,X) assembly, blocked Cholesky + launch plan, triangular inverse, alpha, MLL value / gradient
 //                     (single evaluation, evaluation slots, lock-step batch, graph replay), state restore
 //   gp_sweep.hip      prediction / acquisition sweep, score and posterior gradients, rank-b append
-//   gp_consumers.hip  HMC on the surrogate, EI / LogEI, the classifier gate, GP.kernel, device clone
+//   gp_consumers.hip  HMC / NUTS / constrained random walks on the surrogate, EI / LogEI, the classifier gate, GP.kernel,
+//                     device clone.  (What its chain kernels share with gp_paths.hip's - the rows' homes, the one-point
+//                     evaluation, the HMC transition - is chain_common.hpp; the host staging of a chain call is ChainStage,
+//                     below.)
 //   gp_posterior.hip  joint posterior covariance at query points and correlated draws from it
 //   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
 //   gp_batch.hip      one-sweep batch selection for WIPV / WIPStd (the sweep's intermediates kept, rank-one downdates)
 //   gp_criteria.hip   importance-weighted integration points, IMIQR / EIV: the weighted scoring pass of the sweep and the batch,
 //                     the input gradients of the four scores (few-candidate chain)
 //   gp_paths.hip      pathwise posterior draws of the latent surrogate (random Fourier features + Matheron's rule): path
-//                     sets, their evaluation at query points and per-path argmax
+//                     sets, their evaluation at query points and per-path argmax, input gradients, whole HMC chains on a path
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
 //   gp_tile_harness.hip  test hook: one tile_gemm instantiation per call on caller-supplied operands
 // Host side only: buffer management, launch sequencing, host/device pointer handling.  No CPU compute path exists:
@@ -94,6 +97,43 @@ struct CallBuf : DBuf {
   CallBuf(const CallBuf&) = delete;
   CallBuf& operator=(const CallBuf&) = delete;
   ~CallBuf() { release(); }
+};
+
+// The staging of one chain call (hmc_run, nuts_run, paths_hmc_run), host pointers in and out, in the buffer the caller
+// names: state [P][3d+2] | adapt [P][5] | mass (ni doubles: inv_mass, d or P d, or NUTS's metric, 2 d d) | hist | keep |
+// stats (NUTS: nt) | dbg (nd).  An output the caller did not ask for takes no room, and its device pointer is null.
+struct ChainStage {
+  size_t ns, na, ni, nh, nk, nt, nd;
+  double *dS, *dA, *dI, *dH, *dK, *dT, *dD;
+  ChainStage(DBuf& buf, int64_t P, int d, size_t ni_, int niter, int hist_from, bool hist, int thin, bool keep, size_t nt_,
+             size_t nd_)
+      : ns((size_t)P * (3 * (size_t)d + 2)), na((size_t)P * 5), ni(ni_),
+        nh(hist ? (size_t)(niter - hist_from) * P * d : 0), nk(keep ? (size_t)(niter / thin) * P * (d + 1) : 0), nt(nt_),
+        nd(nd_) {
+    buf.ensure((ns + na + ni + nh + nk + nt + nd) * sizeof(double));
+    dS = buf.d();
+    dA = dS + ns;
+    dI = dA + na;
+    double* const h0 = dI + ni;
+    dH = nh ? h0 : nullptr;
+    dK = nk ? h0 + nh : nullptr;
+    dT = nt ? h0 + nh + nk : nullptr;
+    dD = nd ? h0 + nh + nk + nt : nullptr;
+  }
+  void copy_in(hipStream_t stream, const double* state, const double* adapt, const double* mass) const {
+    HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dI, mass, ni * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
+  void copy_out(hipStream_t stream, double* state, double* adapt, double* hist, double* keep, double* stats,
+                double* dbg) const {
+    HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (dH) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (dK) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (dT) HIPCHK(hipMemcpyAsync(stats, dT, nt * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (dD) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, stream));
+  }
 };
 
 // The factorisation's rank test.  A pivot (L_jj^2) below 64 ulp of the kernel matrix's diagonal k(x,x) + noise is as large as

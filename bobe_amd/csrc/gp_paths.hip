@@ -386,23 +386,12 @@ int paths_hmc_run(bobe_paths& p, int64_t P, const int64_t* path_idx, double* sta
   g.use();
   ensure_vct(p);
   const int d = p.d;
-  const size_t sw = 3 * (size_t)d + 2, ns = (size_t)P * sw, na = (size_t)P * 5, ni = (size_t)P * d;
-  const size_t nh = hist ? (size_t)(niter - hist_from) * P * d : 0;
-  const size_t nk = keep ? (size_t)(niter / thin) * P * (d + 1) : 0;
-  const size_t nd = dbg ? (size_t)P * (d + 3) : 0;
-  // staging: state | adapt | inv_mass | hist | keep | dbg, and the path indices
+  // the chain staging (inv_mass per chain), and the path indices
   CallBuf stage, idx;
-  stage.ensure((ns + na + ni + nh + nk + nd) * sizeof(double));
+  const ChainStage st(stage, P, d, (size_t)P * d, niter, hist_from, hist != nullptr, thin, keep != nullptr, 0,
+                      dbg ? (size_t)P * (d + 3) : 0);
   idx.ensure((size_t)P * sizeof(int64_t));
-  double* dS = stage.d();
-  double* dA = dS + ns;
-  double* dI = dA + na;
-  double* dH = dI + ni;
-  double* dK = dH + nh;
-  double* dD = dK + nk;
-  HIPCHK(hipMemcpyAsync(dS, state, ns * sizeof(double), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(dA, adapt, na * sizeof(double), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(dI, inv_mass, ni * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  st.copy_in(g.stream, state, adapt, inv_mass);
   HIPCHK(hipMemcpyAsync(idx.p, path_idx, (size_t)P * sizeof(int64_t), hipMemcpyHostToDevice, g.stream));
   int reg, lds, streamed, feat, lg;
   chain_layout(p, &reg, &lds, &streamed, &feat, &lg);
@@ -411,16 +400,12 @@ int paths_hmc_run(bobe_paths& p, int64_t P, const int64_t* path_idx, double* sta
     hipLaunchKernelGGL((k_paths_hmc_run<KE, DC>), dim3((unsigned)P), dim3(256), (size_t)lg * 256 * (d + 1) * sizeof(double),
                        g.stream, (const double*)p.XsT.d(), p.Np, p.N, p.hyp, (const double*)p.alpha.d(),
                        (const double*)p.VcT.d(), p.Np, (const double*)p.U.d(), (const double*)p.B.d(),
-                       (const double*)p.W.d(), p.F, amp, (const int64_t*)idx.p, P, dS, dA, (const double*)dI,
-                       (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from, hist ? dH : nullptr,
-                       thin, keep ? dK : nullptr, dbg ? dD : nullptr, g.gate, lg);
+                       (const double*)p.W.d(), p.F, amp, (const int64_t*)idx.p, P, st.dS, st.dA, (const double*)st.dI,
+                       (unsigned long long)seed, it0, niter, do_adapt, y_std, y_mean, temp, hist_from, st.dH, thin, st.dK,
+                       st.dD, g.gate, lg);
   });
   LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(state, dS, ns * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipMemcpyAsync(adapt, dA, na * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  if (hist) HIPCHK(hipMemcpyAsync(hist, dH, nh * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  if (keep) HIPCHK(hipMemcpyAsync(keep, dK, nk * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  if (dbg) HIPCHK(hipMemcpyAsync(dbg, dD, nd * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  st.copy_out(g.stream, state, adapt, hist, keep, nullptr, dbg);
   g.sync();     // (the call's buffers are freed on return)
   return BOBE_OK;
 }

@@ -355,33 +355,70 @@ __global__ __launch_bounds__(256) void k_paths_grad(const double* __restrict__ X
 }
 
 // ---- whole HMC chains on a posterior PATH (bobe_gp_paths_hmc_run) ---------------------------------------------------------------
-// k_hmc_run (consumer_kernels.hpp) with one change, the target: chain c samples the posterior implied by the path
-// s = pidx[c] of the set instead of the posterior mean.  With xs = x / ls, c_n = VcT[s][n] + alpha[n], amp = sqrt(2 kvar / F):
+// hmc_chain_run (chain_common.hpp: the contract, the state / adapt / hist / keep / dbg layouts, the random numbers) on a
+// target of its own: chain c samples the posterior implied by the path s = pidx[c] of the set instead of the posterior mean.  With
+// xs = x / ls, c_n = VcT[s][n] + alpha[n], amp = sqrt(2 kvar / F):
 //   f(x)      = sum_n c_n k(r2_n) + amp sum_j w_sj cos(u_j . xs + b_j)
 //   df/dx_k   = (1 / ls_k) [ sum_n c_n G(r2_n) (xs_nk - xs_k) - amp sum_j w_sj sin(u_j . xs + b_j) u_jk ]      (k_paths_grad)
 //   mean slot = ymean + ystd f,   logp(u) = mean / temp + sum_k [log x_k + log(1 - x_k)],   u = logit(x)
-// Everything else is k_hmc_run's contract: one 256-thread workgroup per chain, niter whole trajectories per launch, state
-// [P][3d+2], adapt [P][5], the hist / keep / dbg layouts, the clip of x at 1e-12, L = 4 + hash % 9 leapfrog steps, dual
-// averaging (t0 10, gamma 0.05, kappa 0.75, target 0.8, eps in [1e-4, 2]) and the random numbers: ckey = mix(seed ^ mix(c)),
-// ikey = ckey + ((it0 + it) << 12), indices 2t / 2t + 1 for the momentum of coordinate t, 4000 for L, 4001 for the Metropolis
-// uniform.  Deviation: inv_mass is PER CHAIN, [P][d] - paths differ in shape and the host pools the spread per path.
-// The coefficients c_n are formed once per launch (vc[n] + alpha[n], one rounding) and live where k_hmc_run keeps alpha:
-// ChainRows<DCAP>::PATHS rows per thread in registers, lgroups groups of 256 rows in LDS, the rest streamed in ascending
-// order.  After its kernel terms thread t adds the features j = t, t + 256, ... < F in ascending order into the same 1 + d
-// accumulators, the argument reduced as in k_paths_features (tt = arg / 2 pi - rint(arg / 2 pi), sincospi(2 tt)); U, phase
-// and the path's row of W are streamed from L2 in every step (U alone is 256 KB at F = 4096, d = 8: more than a CU's LDS).  The sums: k_hmc_run's tree (chain_wave_sum /
-// wave_sum_components, then the waves ((w0 + w1) + w2) + w3).  The gate is the PARENT handle's at call time (it is not part
-// of the snapshot): an infeasible point has mean = minus_inf and no gradient.  No atomics: a chain's bits depend on the set,
-// its path index, its own state / adapt / inv_mass rows, the seed, its chain number and the iteration numbers - not on P,
-// the other chains' paths or where launches are cut.  The code is duplicated rather than shared, so that k_hmc_run's and
-// k_paths_grad's instruction streams stay exactly what they were.
-// The feature loop keeps ChainRows<DCAP>::STREAM features in flight per thread (2; 1 at DCAP 32): all loads of the group
-// first, as the streamed rows do - one wave per SIMD hides no latency by itself.  A feature past F enters with weight 0.
-// Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950), rbf / matern, with ChainRows<DCAP>::PATHS = 14 / 6 / 1 rows
-// in registers: DCAP 8: 256 VGPRs + 228 / 239 AGPRs, DCAP 16: 256 + 246 / 256, DCAP 32: 256 + 187 / 191; one wave per SIMD
-// and scratch 0 in all six.  One row more spills (DCAP 8 and 16 have fewer than a row's registers left; 2 rows at DCAP 32
-// spill 12 bytes per lane in the Matern variant, next to the 32 frequencies of a feature).  LDS: 704 / 1280 / 2432 bytes
-// static.
+// inv_mass is PER CHAIN, [P][d] - paths differ in shape and the host pools the spread per path.  The coefficients c_n are
+// formed once per launch (CoefPath) and live where k_hmc_run keeps alpha, ChainRows<DCAP>::PATHS rows per thread in
+// registers.  After its kernel terms thread t adds the features j = t, t + 256, ... < F in ascending order into the same 1 + d
+// accumulators (extra), the argument reduced as in k_paths_features (tt = arg / 2 pi - rint(arg / 2 pi), sincospi(2 tt)); U,
+// phase and the path's row of W are streamed from L2 in every step (U alone is 256 KB at F = 4096, d = 8: more than a CU's
+// LDS).  The feature loop keeps ChainRows<DCAP>::STREAM features in flight per thread (2; 1 at DCAP 32): all loads of the
+// group first, as the streamed rows do - one wave per SIMD hides no latency by itself.  A feature past F enters with weight 0;
+// coordinates >= d of the point read as 0 (chain_load_point).  The gate is the PARENT handle's at call time (it is not part of the
+// snapshot).  A chain's bits depend on the set, its path index, its own state / adapt / inv_mass rows, the seed, its chain
+// number and the iteration numbers - not on P, the other chains' paths or where launches are cut.
+// Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950; profiles/chain_core_unify_resources.txt), rbf / matern,
+// with ChainRows<DCAP>::PATHS = 14 / 6 / 1 rows in registers: DCAP 8: 256 VGPRs + 228 / 236 AGPRs, DCAP 16: 256 + 246 / 252,
+// DCAP 32: 256 + 187 / 191; one wave per SIMD and scratch 0 in all six.  One row more: 7 rows at DCAP 16 spill 100 / 156
+// bytes per lane and 2 rows at DCAP 32 spill 12 bytes per lane in the Matern variant (next to the 32 frequencies of a
+// feature); 15 rows at DCAP 8 would fit (246 / 254 AGPRs) and are not taken here.  LDS: 704 / 1280 / 2432 bytes static.
+template <int DCAP>
+struct HmcPathTarget {
+  static constexpr int RMAX = ChainRows<DCAP>::PATHS, FUN = ChainRows<DCAP>::STREAM;
+  static constexpr bool FMA = true;
+  const double* alpha;
+  const double* vc;                            // this chain's path: its row of VcT ...
+  const double* U;
+  const double* phase;
+  const double* ws;                            // ... and of W
+  int64_t F;
+  double amp;
+  const double* inv_mass;                      // this chain's row
+  __device__ __forceinline__ CoefPath coef() const { return {vc, alpha}; }
+  __device__ __forceinline__ void extra(const double (&xs)[DCAP], int d, int t, double& ms, double (&gm)[DCAP]) const {
+    for (int64_t j = t; j < F; j += FUN * 256) {               // this thread's features, ascending, FUN in flight
+      double uv[FUN][DCAP], ph[FUN], wv[FUN];
+#pragma unroll
+      for (int q = 0; q < FUN; ++q) {                          // (all loads of the group first; a feature past F has weight 0)
+        const int64_t jq = j + q * 256;
+        ph[q] = (jq < F) ? phase[jq] : 0.0;
+        wv[q] = (jq < F) ? ws[jq] : 0.0;
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) uv[q][k] = (k < d && jq < F) ? U[jq * d + k] : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < FUN; ++q) {
+        double arg = ph[q];
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) arg = __builtin_fma(uv[q][k], xs[k], arg);
+        double tt = arg * PATHS_INV_TWO_PI;
+        tt -= rint(tt);
+        double sn, cs;
+        sincospi(2.0 * tt, &sn, &cs);
+        const double wa = amp * wv[q];
+        ms = __builtin_fma(wa, cs, ms);
+        const double mw = -(wa * sn);
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) gm[k] = __builtin_fma(mw, uv[q][k], gm[k]);
+      }
+    }
+  }
+};
+
 template <int KERN, int DCAP>
 __global__ __launch_bounds__(256) void k_paths_hmc_run(const double* __restrict__ XsT, int64_t ldx, int64_t n, Hyper h,
                                                        const double* __restrict__ alpha, const double* __restrict__ VcT,
@@ -394,257 +431,10 @@ __global__ __launch_bounds__(256) void k_paths_hmc_run(const double* __restrict_
                                                        double temp, int hist_from, double* __restrict__ hist, int thin,
                                                        double* __restrict__ keep, double* __restrict__ dbg, Gate gt,
                                                        int lgroups) {
-  constexpr int NT = 256, NW = NT / 64;
-  extern __shared__ double lrows[];            // [d + 1][256 lgroups]: training rows and their c_n resident in LDS
-  __shared__ double x[DCAP], xs[DCAP], red[NW][DCAP + 1], lp_s, mean_s, gred[4], kin_s[2];
-  __shared__ double u0[DCAP], g0[DCAP], x0[DCAP], lp0, mean0, eps_s;
-  __shared__ int acc_s;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t c = blockIdx.x;
-  const int d = h.d, sw = 3 * d + 2;
-  double* Sc = S + c * sw;
-  double* ad = adapt + c * 5;
-  if (t < d) {
-    u0[t] = Sc[t];
-    g0[t] = Sc[d + t];
-    x0[t] = Sc[2 * d + t];
-  }
-  if (t < DCAP) {                              // (coordinates >= d read as 0 by the feature loop)
-    x[t] = 0.0;
-    xs[t] = 0.0;
-  }
-  if (t == 0) {
-    lp0 = Sc[3 * d];
-    mean0 = Sc[3 * d + 1];
-    eps_s = ad[0];
-  }
-  const unsigned long long ckey = hmc_mix64(seed ^ hmc_mix64((unsigned long long)c));
-  const int64_t s_path = pidx[c];
-  const double* vc = VcT + s_path * ldt;
-  const double* ws = W + s_path * F;
-  constexpr int RMAX = ChainRows<DCAP>::PATHS, UNR = ChainRows<DCAP>::STREAM, FUN = ChainRows<DCAP>::STREAM;
-  const int nrow = (int)((n + NT - 1) / NT);
-  const int lld = NT * lgroups;
-  double cx[RMAX][DCAP], ca[RMAX];
-#pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    const int64_t i = t + NT * r;
-    ca[r] = (i < n) ? vc[i] + alpha[i] : 0.0;
-#pragma unroll
-    for (int j = 0; j < DCAP; ++j) cx[r][j] = (j < d && i < n) ? XsT[j * ldx + i] : 0.0;
-  }
-  for (int q = 0; q < lgroups; ++q) {
-    const int64_t i = t + (int64_t)NT * (RMAX + q);
-    for (int j = 0; j < d; ++j) lrows[j * lld + q * NT + t] = (i < n) ? XsT[j * ldx + i] : 0.0;
-    lrows[d * lld + q * NT + t] = (i < n) ? vc[i] + alpha[i] : 0.0;
-  }
-  __syncthreads();
-  const double im_r = (t < d) ? inv_mass[c * d + t] : 0.0, inv_ls = (t < d) ? 1.0 / h.ls[t] : 0.0;
-  double a_eps = 0.0, a_mu = 0.0, a_hbar = 0.0, a_leb = 0.0, a_m = 0.0;
-  if (t == 0) {
-    a_eps = ad[0];
-    a_mu = ad[1];
-    a_hbar = ad[2];
-    a_leb = ad[3];
-    a_m = ad[4];
-  }
-  for (int it = 0; it < niter; ++it) {
-    const unsigned long long ikey = ckey + ((unsigned long long)(it0 + it) << 12);
-    const double eps = eps_s;
-    double u_r = 0.0, pm_r = 0.0, p0_r = 0.0, g_r = 0.0, x_r = 0.0;
-    // position update of thread t < d, and the point in cube coordinates for everybody
-    auto advance = [&]() {
-      u_r += eps * im_r * pm_r;
-      double xv = 1.0 / (1.0 + exp(-u_r));
-      xv = xv < 1e-12 ? 1e-12 : (xv > 1.0 - 1e-12 ? 1.0 - 1e-12 : xv);
-      x_r = xv;
-      x[t] = xv;
-      xs[t] = xv * inv_ls;
-    };
-    if (t < d) {                                               // momentum ~ N(0, M), M = diag(1 / inv_mass)
-      const double a = hmc_u01(hmc_mix64(ikey + 2 * t)), b = hmc_u01(hmc_mix64(ikey + 2 * t + 1));
-      const double z = sqrt(-2.0 * log(a)) * cos(6.283185307179586 * b);
-      p0_r = z / sqrt(im_r);
-      pm_r = p0_r + 0.5 * eps * g0[t];
-      u_r = u0[t];
-      advance();
-    }
-    const int L = 4 + (int)(hmc_mix64(ikey + 4000) % 9ull);    // (every thread: the same counter hash)
-    __syncthreads();
-    for (int s = 0; s < L; ++s) {
-      double ms = 0.0, gm[DCAP];
-#pragma unroll
-      for (int j = 0; j < DCAP; ++j) gm[j] = 0.0;
-      // one training point: value and gradient contributions (the difference is formed twice rather than kept)
-      auto point = [&](const double (&xr)[DCAP], double a) {
-        double r2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < DCAP; ++j) {
-          const double df = (j < d) ? xr[j] - xs[j] : 0.0;
-          r2 = __builtin_fma(df, df, r2);
-        }
-        const double kv = kern_eval<KERN>(r2, h.kvar);
-        const double ag = a * kern_grad_factor<KERN>(r2, h.kvar, kv);
-        ms = __builtin_fma(a, kv, ms);
-#pragma unroll
-        for (int j = 0; j < DCAP; ++j) gm[j] = __builtin_fma(ag, (j < d) ? xr[j] - xs[j] : 0.0, gm[j]);
-      };
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r)
-        if (r < nrow) point(cx[r], ca[r]);                     // (uniform) this thread's points in registers,
-      for (int q = 0; q < lgroups; ++q) {                      // in LDS,
-        double xr[DCAP];
-#pragma unroll
-        for (int j = 0; j < DCAP; ++j) xr[j] = (j < d) ? lrows[j * lld + q * NT + t] : 0.0;
-        point(xr, lrows[d * lld + q * NT + t]);
-      }
-      for (int64_t i = t + (int64_t)NT * (RMAX + lgroups); i < n; i += UNR * NT) {  // and streamed: ascending rows throughout
-        double xr[UNR][DCAP], ar[UNR];
-#pragma unroll
-        for (int q = 0; q < UNR; ++q) {                                // (all loads of the group first)
-          const int64_t iq = i + q * NT;
-          ar[q] = (iq < n) ? vc[iq] + alpha[iq] : 0.0;
-#pragma unroll
-          for (int j = 0; j < DCAP; ++j) xr[q][j] = (j < d && iq < n) ? XsT[j * ldx + iq] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < UNR; ++q) point(xr[q], ar[q]);
-      }
-      for (int64_t j = t; j < F; j += FUN * NT) {              // then this thread's features, ascending, FUN in flight
-        double uv[FUN][DCAP], ph[FUN], wv[FUN];
-#pragma unroll
-        for (int q = 0; q < FUN; ++q) {                        // (all loads of the group first; a feature past F has weight 0)
-          const int64_t jq = j + q * NT;
-          ph[q] = (jq < F) ? phase[jq] : 0.0;
-          wv[q] = (jq < F) ? ws[jq] : 0.0;
-#pragma unroll
-          for (int k = 0; k < DCAP; ++k) uv[q][k] = (k < d && jq < F) ? U[jq * d + k] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < FUN; ++q) {
-          double arg = ph[q];
-#pragma unroll
-          for (int k = 0; k < DCAP; ++k) arg = __builtin_fma(uv[q][k], xs[k], arg);
-          double tt = arg * PATHS_INV_TWO_PI;
-          tt -= rint(tt);
-          double sn, cs;
-          sincospi(2.0 * tt, &sn, &cs);
-          const double wa = amp * wv[q];
-          ms = __builtin_fma(wa, cs, ms);
-          const double mw = -(wa * sn);
-#pragma unroll
-          for (int k = 0; k < DCAP; ++k) gm[k] = __builtin_fma(mw, uv[q][k], gm[k]);
-        }
-      }
-      ms = chain_wave_sum(ms);
-      if (lane == 0) red[wave][DCAP] = ms;
-      {
-        const double v = wave_sum_components<DCAP>(gm, lane);
-        if ((lane & (64 / DCAP - 1)) == 0) red[wave][lane / (64 / DCAP)] = v;
-      }
-      // the parent's classifier gate: an infeasible point has mean = minus_inf and no gradient - its trajectory ends in a
-      // state that the Metropolis test never accepts
-      if (gate_on(gt)) {                                       // (the gate's 256 partial sums: k_gate's order)
-        const double gs = gate_partial<DCAP>(gt, x, d, t);
-        if (lane == 0) gred[wave] = gs;
-      }
-      __syncthreads();
-      const bool ok = gate_on(gt) ? gate_feasible(gt, gate_combine(gt, gred)) : true;
-      // (the waves' sums in wave order: ((r0 + r1) + r2) + r3)
-      auto wsum = [&](int j) {
-        double sres = red[0][j];
-#pragma unroll
-        for (int w_ = 1; w_ < NW; ++w_) sres += red[w_][j];
-        return sres;
-      };
-      const bool last = s == L - 1;
-      if (t < d) {
-        const double dm = ok ? wsum(t) * inv_ls : 0.0;
-        g_r = dm * ystd / temp * (x_r * (1.0 - x_r)) + (1.0 - 2.0 * x_r);
-        pm_r += (last ? 0.5 * eps : eps) * g_r;
-        if (!last) advance();
-      }
-      if (last) {
-        if (wave == 0) {                                       // kinetic energies at both ends (lanes = coordinates)
-          const double k0 = chain_wave_sum(p0_r * p0_r * im_r), k1 = chain_wave_sum(pm_r * pm_r * im_r);
-          if (lane == 0) {
-            kin_s[0] = k0;
-            kin_s[1] = k1;
-          }
-        } else if (wave == 1) {                                // the end point's log-density
-          double jl = (lane < d) ? log(x[lane]) + log1p(-x[lane]) : 0.0;
-          jl = chain_wave_sum(jl);
-          if (lane == 0) {
-            const double m = ok ? wsum(DCAP) * ystd + ymean : gt.minus_inf;
-            mean_s = m;
-            lp_s = m / temp + jl;
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if (t == 0) {                                              // Metropolis test and the chain's step-size update
-      const double h0 = lp0 - 0.5 * kin_s[0], h1 = lp_s - 0.5 * kin_s[1];
-      double ap = 0.0;
-      if (isfinite(h1)) ap = h1 >= h0 ? 1.0 : exp(h1 - h0);
-      const double r = hmc_u01(hmc_mix64(ikey + 4001));
-      const int acc = r < ap;
-      acc_s = acc;
-      if (acc) {
-        lp0 = lp_s;
-        mean0 = mean_s;
-      }
-      if (do_adapt) {
-        constexpr double t0 = 10.0, gamma = 0.05, kappa = 0.75, target = 0.8;
-        const double m = a_m + 1.0;
-        const double hbar = (1.0 - 1.0 / (m + t0)) * a_hbar + (target - ap) / (m + t0);
-        const double le = a_mu - sqrt(m) / gamma * hbar;
-        const double eta = pow(m, -kappa);
-        a_hbar = hbar;
-        a_leb = eta * le + (1.0 - eta) * a_leb;
-        a_m = m;
-        double e = exp(le);
-        e = e < 1e-4 ? 1e-4 : (e > 2.0 ? 2.0 : e);
-        a_eps = e;
-        eps_s = e;
-      }
-      if (dbg && it == niter - 1) {
-        double* dc = dbg + c * (d + 3);
-        dc[d] = (double)L;
-        dc[d + 1] = r;
-        dc[d + 2] = ap;
-      }
-    }
-    if (dbg && it == niter - 1 && t < d) dbg[c * (d + 3) + t] = p0_r;
-    __syncthreads();
-    if (t < d) {
-      if (acc_s) {
-        u0[t] = u_r;
-        g0[t] = g_r;
-        x0[t] = x_r;
-      }
-      if (hist && it >= hist_from) hist[((int64_t)(it - hist_from) * P + c) * d + t] = u0[t];
-      if (keep && (it + 1) % thin == 0) keep[((int64_t)((it + 1) / thin - 1) * P + c) * (d + 1) + t] = x0[t];
-    }
-    if (t == 0 && keep && (it + 1) % thin == 0) keep[((int64_t)((it + 1) / thin - 1) * P + c) * (d + 1) + d] = mean0;
-    // (no barrier here, for k_hmc_run's reasons: u0 / g0 / x0 are read by their own thread only, x / xs are written by
-    //  advance() after every reader of this iteration has passed the barrier above, eps_s and acc_s were written before it)
-  }
-  if (t < d) {
-    Sc[t] = u0[t];
-    Sc[d + t] = g0[t];
-    Sc[2 * d + t] = x0[t];
-  }
-  if (t == 0) {
-    Sc[3 * d] = lp0;
-    Sc[3 * d + 1] = mean0;
-    if (do_adapt) {
-      ad[0] = a_eps;
-      ad[2] = a_hbar;
-      ad[3] = a_leb;
-      ad[4] = a_m;
-    }
-  }
+  const int64_t c = blockIdx.x, s_path = pidx[c];
+  const HmcPathTarget<DCAP> tg{alpha, VcT + s_path * ldt, U, phase, W + s_path * F, F, amp, inv_mass + c * h.d};
+  hmc_chain_run<KERN, DCAP>(tg, XsT, ldx, n, h, P, S, adapt, seed, it0, niter, do_adapt, ystd, ymean, temp, hist_from, hist,
+                            thin, keep, dbg, gt, lgroups);
 }
 
 }  // namespace bobe

@@ -166,6 +166,49 @@ def test_a_set_without_randomness_collapses_to_the_mean_sampler(kernel, d, n, F)
         assert np.allclose(b, a, rtol=1e-10, atol=1e-10) and not np.array_equal(a, st0)
 
 
+@pytest.mark.parametrize("kernel", ["rbf", "matern"])
+@pytest.mark.parametrize("n,d", [(200, 3), (2500, 12), (1500, 20)])
+def test_the_same_chain_under_both_kernels(kernel, n, d):
+    """k_hmc_run and k_paths_hmc_run are the same HMC transition on two targets (the second through hmc_chain_run, the first
+    written out: chain_common.hpp, consumer_kernels.hpp).  A set created with W = 0 and eps = 0 has V_c = 0, hence c_n =
+    alpha_n exactly, and its feature terms add exact zeros; with every inv_mass row equal to one vector the path chain IS
+    the mean chain: 4 iterations with adaptation from the same state, adapt, seed and it0.  No behaviour may belong to one
+    of the two only.  Rows in registers only (200, 3), registers + LDS (2500, 12) and a streamed rest (1500, 20, where the
+    two kernels keep different numbers of rows in registers but visit them in the same ascending order).
+
+    The draws (momentum, L, uniform) must be the same bits.  State, adapt, hist and keep are NOT the same bits:
+    k_paths_hmc_run spells its multiply-adds as explicit fmas, k_hmc_run leaves them to the compiler's contraction, and each
+    keeps its arithmetic (a k_hmc_run built with explicit fmas gave a difference of exactly 0 in all six cases).  They are
+    held to the tolerance this file and tests/test_gpu_samplers.py hold one chain iteration computed in two ways to, rtol =
+    atol = 1e-10.  Measured on an MI355X, largest deviation as a fraction of that tolerance, state / adapt / hist / keep:
+    rbf d = 3 0.40 / 0.13 / 0.37 / 0.25 (1e-10 absolute in the state), matern d = 3 0.040 / 0.0013 / 0.019 / 0.013, rbf
+    d = 12 0.022 / 0.0015 / 0.016 / 0.011, matern d = 12 0.0037 / 0.0005 / 0.0019 / 0.0036, d = 20 below 0.009 for both
+    families - the same figures before and after k_paths_hmc_run moved onto the shared body."""
+    gp, rng = _gp(n, d, kernel, seed=70 + d)
+    S, P, temp, eps = 2, 8, 1.0, 0.05
+    with gp.sample_paths(S, 300, seed=3, w=np.zeros((S, 300)), eps=np.zeros((S, n))) as ps:
+        idx = (np.arange(P) % S).astype(np.int64)
+        im = rng.uniform(0.5, 2.0, size=d)
+        U0 = rng.normal(scale=0.5, size=(P, d))
+        X = np.clip(expit(U0), 1e-12, 1 - 1e-12)
+        m, _, dm, _ = gp.predict_grad(X, mean_only=True)
+        mean = m * gp.y_std + gp.y_mean
+        lp = mean / temp + np.sum(np.log(X) + np.log1p(-X), axis=1)
+        g = dm * gp.y_std / temp * (X * (1 - X)) + (1 - 2 * X)
+        st0 = np.ascontiguousarray(np.concatenate([U0, g, X, lp[:, None], mean[:, None]], axis=1))
+        a, b, aa, ab = st0.copy(), st0.copy(), _adapt(P, eps), _adapt(P, eps)
+        ha, ka, da = gp.hmc_run(a, aa, im, seed=77, it0=3, niter=4, do_adapt=True, temp=temp, hist_from=0, thin=2, debug=True)
+        hb, kb, db = ps.hmc_run(b, ab, np.tile(im, (P, 1)), idx, seed=77, it0=3, niter=4, do_adapt=True, temp=temp,
+                                hist_from=0, thin=2, debug=True)
+        assert np.array_equal(da[:, :d + 2], db[:, :d + 2])                      # momentum, L, uniform: the same draws
+        for name, p, q in (("state", a, b), ("adapt", aa, ab), ("hist", ha, hb), ("keep", ka, kb)):
+            print(f"same chain {kernel} d={d} N={n}: {name} differs by at most {np.max(np.abs(p - q)):.3g}, "
+                  f"{np.max(np.abs(p - q) / (1e-10 + 1e-10 * np.abs(p))):.3g} of the tolerance")
+            assert p.shape == q.shape and np.allclose(q, p, rtol=1e-10, atol=1e-10), name
+        assert ha.shape == (4, P, d) and ka.shape == (2, P, d + 1)
+        assert not np.array_equal(a, st0) and np.all(aa[:, 4] == 4) and np.all(ab[:, 4] == 4)
+
+
 def _grid(G):
     g = (np.arange(G) + 0.5) / G
     a, b = np.meshgrid(g, g, indexing="ij")
