@@ -161,8 +161,9 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
     _pool_only_logged = False
 
     def _weighted(self, log_weights) -> bool:
-        """True where the scores come from ``bobe_gp_wip_sweep_w``: IMIQR / EIV, or integration points with log-weights."""
-        return self._key in ("imiqr", "eiv") or log_weights is not None
+        """True where the scores come from ``bobe_gp_wip_sweep_w`` / ``bobe_gp_wip_sweep_zvar``: IMIQR / EIV / ZVar, or
+        integration points with log-weights."""
+        return self._key in ("imiqr", "eiv", "zvar") or log_weights is not None
 
     def fun(self, x, gp, mc_points=None, k_train_mc=None, *, log_weights=None):
         if self._weighted(log_weights):
@@ -228,7 +229,7 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
         candidates = acq_kwargs.get("candidates")
         if candidates is None:
             candidates = mc_samples["x"]
-        if log_weights is None:
+        if log_weights is None and self._key != "zvar":
             r = gp.wip_select_batch(candidates, mc_points, n_batch, criterion=self._key)
         else:
             r = gp.wip_select_batch_w(candidates, mc_points, n_batch, criterion=self._key, log_weights=log_weights)
@@ -321,6 +322,24 @@ class EIV(WeightedIntegratedPosteriorBase):
     the pick."""
     name: str = "EIV"
     _key = "eiv"
+
+
+class ZVar(WeightedIntegratedPosteriorBase):
+    """The expected posterior variance of the evidence estimate Z = sum_z e^{l_z} e^{f(z)} after one more evaluation - the
+    Bayesian-quadrature criterion for the lognormal estimate exp(f), which counts the correlation of the surrogate's errors
+    between integration points where WIPV / WIPStd / IMIQR / EIV integrate a pointwise variance (no counterpart in the
+    reference).  The score is ``zvar`` = -log T(c) of ``GP.wip_sweep(criteria=('zvar',))``: the expected reduction of Var Z is
+    ``exp(2 log_ez - zvar)``.  Picks from the candidate pool; no gradient form is built, so ``acq_kwargs['weighted_polish']``
+    > 0 is a ValueError."""
+    name: str = "ZVar"
+    _key = "zvar"
+
+    def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 100, n_restarts: int = 1, verbose: bool = True,
+                       early_stop_patience: int = 25, rng=None):
+        if _weighted_polish(acq_kwargs if acq_kwargs is not None else {}) > 0:
+            raise ValueError("ZVar has no input-gradient form: weighted_polish must be 0")
+        return super().get_next_point(gp, acq_kwargs=acq_kwargs, maxiter=maxiter, n_restarts=n_restarts, verbose=verbose,
+                                      early_stop_patience=early_stop_patience, rng=rng)
 
 
 class PathwiseTS(AcquisitionFunction):

@@ -28,7 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 from scipy.stats import qmc
 
-from .acquisition import (EI, EIV, IMIQR, LogEI, PathwiseTS, WeightedIntegratedPosteriorBase, WIPStd, WIPV, get_mc_points,
+from .acquisition import (EI, EIV, IMIQR, LogEI, PathwiseTS, WeightedIntegratedPosteriorBase, WIPStd, WIPV, ZVar, get_mc_points,
                           get_mc_samples)
 from .dist_sweep import dist_info, merge_best_fit, shard_bounds
 from .gp import GP
@@ -39,6 +39,14 @@ from .utils import (get_logger, get_numpy_rng, scale_from_unit, scale_to_unit, s
 log = get_logger("bo")
 
 _ACQ = {"wipv": WIPV, "wipstd": WIPStd, "ei": EI, "logei": LogEI, "imiqr": IMIQR, "eiv": EIV, "ts": PathwiseTS}
+# later names (consulted after _ACQ at construction, validation and dispatch); they run through
+# run_weighted_integrated_posterior like 'imiqr' / 'eiv'
+_ACQ_MORE = {"zvar": ZVar}
+
+
+def _acq_class(name, default=None):
+    key = str(name).lower()
+    return _ACQ.get(key, _ACQ_MORE.get(key, default))
 
 
 def _factorisable_start(gp: GP, init: np.ndarray) -> np.ndarray:
@@ -216,7 +224,7 @@ class BOBE:
         self.min_delta_seen = np.inf
         self.current_iteration = 0
         self.start_iteration = 0
-        self.acquisition = _ACQ.get(str(acq).lower(), WIPV)(optimizer=optimizer)   # (run() installs its own, bo.py:1147)
+        self.acquisition = _acq_class(acq, WIPV)(optimizer=optimizer)   # (run() installs its own, bo.py:1147)
         self.acquisition_history: List[float] = []
         self.gp_hyperparam_history: List[dict] = []
         self.kl_history: List[dict] = []
@@ -614,7 +622,8 @@ class BOBE:
         (default): the pool pick, and an ``acq_kwargs`` without the key.
         ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
-        samples.  ``acq`` may be a tuple of stages, run one after the other on the
+        samples; ``acq`` 'zvar' (``acquisition.ZVar``) runs it with the expected posterior variance of the evidence estimate as the
+        criterion (pool picks only: ``weighted_polish`` > 0 with it is a ValueError).  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -678,8 +687,10 @@ class BOBE:
         self._current_evals = self.gp.npoints
         acqs = [acq] if isinstance(acq, str) else list(acq)
         for a in acqs:
-            if a.lower() not in _ACQ:
-                raise ValueError(f"Invalid acquisition function '{a}'. Valid options are: {list(_ACQ)}")
+            if _acq_class(a) is None:
+                raise ValueError(f"Invalid acquisition function '{a}'. Valid options are: {list(_ACQ) + list(_ACQ_MORE)}")
+            if a.lower() == "zvar" and self.weighted_polish > 0:
+                raise ValueError("acq='zvar' has no input-gradient form: weighted_polish must be 0")
         self.current_iteration = self.start_iteration
         rs, self._resume_state = self._resume_state, None        # (a second run() on this object starts from its current state)
         # A tuple of acquisition functions runs as stages, one after the other (bo.py:1149-1158); a saved run state names the
@@ -717,13 +728,13 @@ class BOBE:
                     break
                 self.converged, self.convergence_counter = False, 0
                 self.termination_reason = "Max evaluation budget reached"
-            self.acquisition = _ACQ[a.lower()](optimizer=self.optimizer)
+            self.acquisition = _acq_class(a)(optimizer=self.optimizer)
             if a.lower() == "wipv":
                 self.run_WIPV(ii=self.current_iteration)
             elif a.lower() == "wipstd":
                 self.run_WIPStd(ii=self.current_iteration)
-            elif a.lower() in ("imiqr", "eiv", "ts"):
-                self.run_weighted_integrated_posterior(_ACQ[a.lower()], ii=self.current_iteration)
+            elif a.lower() in ("imiqr", "eiv", "ts") or a.lower() in _ACQ_MORE:
+                self.run_weighted_integrated_posterior(_acq_class(a), ii=self.current_iteration)
             else:
                 self.run_EI(ii=self.current_iteration)
         log.info(f"Final best point {self.best} with value = {self.best_f:.6f}, found at iteration {self.best_pt_iteration}")

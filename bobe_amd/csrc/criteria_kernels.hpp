@@ -21,7 +21,7 @@
 namespace bobe {
 
 constexpr double IMIQR_U = 0.6744897501960817;    // Phi^-1(3/4)
-static_assert(ZTERM_ROWS == 5, "k_wip_zterms / k_wip_score_w address the table's rows mu, a, omega, e, l by number");
+static_assert(ZTERM_ROWS == 6, "k_wip_zterms / k_wip_score_w / k_wip_score_zz address the table's rows mu, a, omega, e, l, lambda by number");
 
 // one term more in a running-maximum log-sum-exp (mx = -inf, s = 0 to start with; t finite, see "Domain" above)
 __device__ __forceinline__ void lse_add(double& mx, double& s, double t) {
@@ -54,11 +54,14 @@ __device__ __forceinline__ double block_fold256(double* red, double v) {
 //          -mu_z, a_z, omega = softmax(a) (maximum, then the sum of exp(a - max))
 //   always: e_z = l_z + 2 mu_z + 2 b_z with b_z = y_std^2 * base_z (non-finite or < 1e-12 -> 1e-12), and
 //          *log_s = LSE_z e_z = log sum_z exp(l_z + 2 mu_z + 2 b_z)
+//   lam:   in addition row 5, lambda_z = g_z - *log_ez with g_z = l_z + mu_z + b_z / 2 and *log_ez = LSE_z g_z = log E[Z] (it
+//          follows b_z like the e row: written on every call that asks for it)
 // A later stage of the batch selection calls it with first = 0 on its downdated base_z: mu, a, omega stay.
 static __global__ __launch_bounds__(256) void k_wip_zterms(const double* __restrict__ part, int64_t ldp, int nrb, int64_t m,
                                                            double ystd, const double* __restrict__ logw,
                                                            const double* __restrict__ basez, double* __restrict__ zt,
-                                                           int64_t ldt, int first, double* __restrict__ log_s) {
+                                                           int64_t ldt, int first, double* __restrict__ log_s, int lam,
+                                                           double* __restrict__ log_ez) {
   __shared__ double red[256];
   const int t = threadIdx.x;
   double* mu = zt;
@@ -99,6 +102,143 @@ static __global__ __launch_bounds__(256) void k_wip_zterms(const double* __restr
   for (int64_t z = t; z < m; z += 256) s += exp(e3[z] - emax);
   s = block_fold256<false>(red, s);
   if (t == 0) *log_s = emax + log(s);
+  if (!lam) return;                                // (uniform)
+  // row 5, for k_wip_score_zz: lambda_z = g_z - LSE_z g_z with g_z = l_z + mu_z + b_z / 2, the log of z's share of E[Z]
+  double* lm = zt + 5 * ldt;
+  double gmax = -INFINITY;
+  for (int64_t z = t; z < m; z += 256) {
+    double b = basez[z];
+    if (!(b >= NOISE_FLOOR) || b > 1.79769313486231571e308) b = NOISE_FLOOR;
+    const double g = (ell[z] + mu[z]) + 0.5 * (b * ystd2);
+    lm[z] = g;
+    gmax = (g > gmax || g != g) ? g : gmax;
+  }
+  gmax = block_fold256<true>(red, gmax);
+  double sg = 0.0;
+  for (int64_t z = t; z < m; z += 256) sg += exp(lm[z] - gmax);
+  sg = block_fold256<false>(red, sg);
+  const double lez = gmax + log(sg);
+  for (int64_t z = t; z < m; z += 256) lm[z] -= lez;
+  if (t == 0) *log_ez = lez;
+}
+
+// ---- the evidence-variance scorer (bobe_gp_wip_sweep_zvar): zvar[c] = -log T(c),
+//   T(c) = sum_z sum_z' omega_z omega_z' expm1(r_z r_z'),   omega_z = exp(lambda_z) (the table's row 5),
+//   r_z(c) = y_std cross_z / sqrt(s_c), cross_z formed exactly as k_wip_score_w forms it.
+// The expected variance of Z = sum_z e^{l_z} e^{f(z)} after one observation at c is Var Z - E[Z]^2 T(c) (the law of total
+// variance for the lognormal e^f: the observation moves mu_z by r_z xi, xi ~ N(0, 1), and lowers b_z by r_z^2); the
+// c-independent Var Z is not formed.  Rules:
+//   |r_z| <= sqrt(b_z), b_z = y_std^2 base_z floored as k_wip_zterms floors it (so b+ >= 0: the counterpart of v+ >= 1e-12);
+//   a non-finite cross_z gives r_z = 0; a candidate whose s_c is not > 0 has every r_z = 0;
+//   T <= 0 (every r_z = 0, T underflown or rounding-negative) gives zvar = +inf: the candidate teaches nothing.
+// No exponent above 0 is taken: with h_c = max_z (lambda_z + r_z^2 / 2) every pair has lambda_z + lambda_z' + r_z r_z' <=
+// 2 h_c (r r' <= (r^2 + r'^2) / 2), so with p_z = lambda_z - h_c and E_z = exp(p_z) a pair with |r r'| < 1 adds
+// E_z E_z' expm1(r r'), any other exp(p_z + p_z' + r r') - E_z E_z', and zvar = -(2 h_c + log sum).  One transcendental per
+// pair, C M^2 / 2 of them per launch: the cost grows with the SQUARE of M where the other scorers' grows with M.
+// Shape: one workgroup = ZZ_G candidates (lane within a half-wave) x ZZ_S interleaved z-slices.  Pass 1 finds h_c (one O(M)
+// pass, the slices' maxima folded through LDS).  Pass 2 walks the z' tiles J of ZZ_T points - r and E of the tile for the
+// workgroup's candidates in LDS, [z'][candidate]: a half-wave reads 32 consecutive doubles, conflict-free - and under every J
+// the tiles I <= J, where a thread forms r, p, E of its own z = slice, slice + ZZ_S, ... again from crossT (one kernel
+// evaluation per ZZ_T pairs) and sums over z' in J (z' > z on the diagonal tile; the diagonal pair apart): off-diagonal pairs
+// count twice.  Every sum runs in a fixed order that depends on M and the candidate alone; the slices are combined in order.
+constexpr int ZZ_G = 32, ZZ_S = 8, ZZ_T = 64;
+static_assert(ZZ_G * ZZ_S == 256 && ZZ_S == 8 && ZZ_T % ZZ_S == 0,
+              "k_wip_score_zz: 256 threads = candidates x 8 slices (combined by name at the end), whole rounds per tile");
+
+template <int KERN, int DCAP>
+__global__ __launch_bounds__(256) void k_wip_score_zz(const double* __restrict__ crossT, int64_t ldx,
+                                                      const double* __restrict__ CsT, int64_t ldc,
+                                                      const double* __restrict__ ZsT, int64_t ldz, int64_t m,
+                                                      const double* __restrict__ sc, const double* __restrict__ basez,
+                                                      const double* __restrict__ zt, int64_t ldt, int64_t ncols, Hyper h,
+                                                      double ystd, double* __restrict__ out) {
+  __shared__ double rs[ZZ_T][ZZ_G], es[ZZ_T][ZZ_G], ls[ZZ_T], red[ZZ_S][ZZ_G];
+  const int t = threadIdx.x, cx = t % ZZ_G, sl = t / ZZ_G;
+  const int64_t c = (int64_t)blockIdx.x * ZZ_G + cx;
+  const bool live = c < ncols;
+  const double* lam = zt + 5 * ldt;
+  double xc[DCAP];
+#pragma unroll
+  for (int j = 0; j < DCAP; ++j) xc[j] = (live && j < h.d) ? CsT[j * ldc + c] : 0.0;
+  const double s = live ? sc[c] : 1.0;
+  const double scale = (s > 0.0) ? ystd / sqrt(s) : 0.0;
+  const bool dead = !(s > 0.0);
+  const double ystd2 = ystd * ystd;
+  // r_z of this thread's candidate (z < m, live)
+  auto r_of = [&](int64_t z) {
+    double r2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) {
+      if (j < h.d) {
+        const double df = xc[j] - ZsT[j * ldz + z];
+        r2 += df * df;
+      }
+    }
+    const double cross = kern_eval<KERN>(r2, h.kvar) - crossT[z * ldx + c];
+    double b = basez[z];
+    if (!(b >= NOISE_FLOOR) || b > 1.79769313486231571e308) b = NOISE_FLOOR;
+    const double cap = sqrt(b * ystd2);
+    double r = cross * scale;
+    if (dead || !(fabs(cross) <= 1.79769313486231571e308)) r = 0.0;
+    if (r > cap) r = cap;
+    if (r < -cap) r = -cap;
+    return r;
+  };
+  // pass 1: h_c
+  double hm = -INFINITY;
+  if (live) {
+    for (int64_t z = sl; z < m; z += ZZ_S) {
+      const double r = r_of(z);
+      const double q = lam[z] + 0.5 * (r * r);
+      hm = (q > hm || q != q) ? q : hm;
+    }
+  }
+  red[sl][cx] = hm;
+  __syncthreads();
+  hm = red[0][cx];
+#pragma unroll
+  for (int k = 1; k < ZZ_S; ++k) {
+    const double y = red[k][cx];
+    hm = (y > hm || y != y) ? y : hm;
+  }
+  // pass 2: the pair sum
+  double off = 0.0, dia = 0.0;
+  auto pair = [&](double x, double ee, double pp) {
+    return (fabs(x) < 1.0) ? ee * expm1(x) : exp(pp + x) - ee;
+  };
+  for (int64_t j0 = 0; j0 < m; j0 += ZZ_T) {
+    __syncthreads();
+    const int zn = (m - j0 < ZZ_T) ? (int)(m - j0) : ZZ_T;
+    for (int zz = sl; zz < ZZ_T; zz += ZZ_S) {
+      const bool in = live && zz < zn;
+      const double r = in ? r_of(j0 + zz) : 0.0;
+      rs[zz][cx] = r;
+      es[zz][cx] = in ? exp(lam[j0 + zz] - hm) : 0.0;
+    }
+    if (t < ZZ_T) ls[t] = (t < zn) ? lam[j0 + t] : 0.0;
+    __syncthreads();
+    if (!live) continue;
+    for (int64_t i0 = 0; i0 <= j0; i0 += ZZ_T) {
+      const bool diag = i0 == j0;
+      const int in_ = (m - i0 < ZZ_T) ? (int)(m - i0) : ZZ_T;
+      for (int iz = sl; iz < in_; iz += ZZ_S) {
+        const double r = r_of(i0 + iz);
+        const double p = lam[i0 + iz] - hm;
+        const double e = exp(p);
+        if (diag) dia += pair(r * r, e * e, p + p);
+        for (int zz = diag ? iz + 1 : 0; zz < zn; ++zz)
+          off += pair(r * rs[zz][cx], e * es[zz][cx], p + (ls[zz] - hm));
+      }
+    }
+  }
+  __syncthreads();
+  red[sl][cx] = 2.0 * off + dia;
+  __syncthreads();
+  if (sl == 0 && live) {
+    const double tot = ((red[0][cx] + red[1][cx]) + (red[2][cx] + red[3][cx])) +
+                       ((red[4][cx] + red[5][cx]) + (red[6][cx] + red[7][cx]));
+    out[c] = (tot > 0.0) ? -(2.0 * hm + log(tot)) : ((tot <= 0.0) ? INFINITY : tot);
+  }
 }
 
 // ---- the weighted scorer: k_wip_score's shape (64 candidates x 4 interleaved z-slices per workgroup, z tiles of 128 through

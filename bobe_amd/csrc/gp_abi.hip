@@ -367,6 +367,23 @@ int bobe_gp_wip_select_batch_w(bobe_gp_t* g, const double* cand, int64_t C, cons
   API_END
 }
 
+int bobe_gp_wip_sweep_zvar(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                           const double* logw, double* zvar, double* log_ez, int64_t* argmin, double* min) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  return g->wip_sweep_zvar(cand, C, Z, M, y_std, logw, zvar, log_ez, argmin, min);
+  API_END
+}
+
+int bobe_gp_wip_select_batch_zvar(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                                  const double* logw, int n_batch, int64_t* picks, double* pick_scores,
+                                  double* stage_scores) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  return g->wip_select_batch_zvar(cand, C, Z, M, y_std, logw, n_batch, picks, pick_scores, stage_scores);
+  API_END
+}
+
 int bobe_gp_fantasy_var(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                         double* out) {
   API_BEGIN

@@ -28,11 +28,13 @@ int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, in
 // w (bobe_gp_wip_select_batch_w, gp_criteria.hip): the weighted scorer in place of wip_score - stage 0's row comes from the
 // sweep's own weighted pass and its argmin from k_argmin_masked with nothing masked (k_argmin's rule), a later stage refreshes
 // the table's base_z terms from the call's downdated copy and scores with k_wip_score_w.  Everything else is shared.
+// criterion 4 (bobe_gp_wip_select_batch_zvar only: the _w entry refuses it) is the evidence-variance scorer, k_wip_score_zz
+// into SweepW::zz, with the table's lambda row refreshed at every stage like criterion 3's e row.
 int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch,
                           int criterion, int64_t* picks, double* pick_scores, double* stage_scores, SweepW* w) {
   if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
   if (n_batch < 1 || n_batch > BATCH_MAX || n_batch > C) throw Err(BOBE_ERR_ARG, "n_batch must be in [1, min(C, 64)]");
-  if (criterion < 0 || criterion > (w ? 3 : 1)) throw Err(BOBE_ERR_ARG, "criterion out of range");
+  if (criterion < 0 || criterion > (w ? 4 : 1)) throw Err(BOBE_ERR_ARG, "criterion out of range");
   if (!picks) throw Err(BOBE_ERR_ARG, "picks is NULL");
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   const int64_t Cp = round_up(C, TILE), Mp = round_up(M, TILE);
@@ -75,7 +77,7 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
   rq.keep = &keep;
   if (w) {
     for (double*& o : w->out) o = nullptr;
-    w->out[criterion] = stage_row(0);
+    (criterion == 4 ? w->zz : w->out[criterion]) = stage_row(0);
     rq.w = w;
     sweep(rq);
     hipLaunchKernelGGL(k_argmin_masked, dim3(1), dim3(1024), 0, stream, (const double*)stage_row(0), C, d_picks, 0,
@@ -123,9 +125,14 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
                        (const double*)uzj, (const double*)ucj);
     double* row = stage_row(j);
     if (w) {
-      if (criterion == 3) wip_zterms(*w, M, Mp, y_std, bz.d(), false);
-      w->out[criterion] = row;
-      wip_score_w(*w, xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, 0);
+      if (criterion >= 3) wip_zterms(*w, M, Mp, y_std, bz.d(), false);
+      if (criterion == 4) {
+        w->zz = row;
+        wip_score_zz(*w, xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, 0);
+      } else {
+        w->out[criterion] = row;
+        wip_score_w(*w, xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, 0);
+      }
     } else {
       wip_score(xT.d(), Cp, cst.d(), scb.d(), bz.d(), C, M, Mp, y_std, wipv ? row : nullptr, wipv ? nullptr : row, nullptr);
     }

@@ -30,7 +30,7 @@ void bobe_gp::wip_zterms(SweepW& w, int64_t M, int64_t Mp, double y_std, const d
     kernel_matrix_cross(XsT.d(), Np, N, Np, ZsT.d(), Mp, M, Mp, hyp, kXZ.d(), Mp, (const double*)alpha.d(), w.zpart.d(), Mp);
   }
   hipLaunchKernelGGL(k_wip_zterms, dim3(1), dim3(256), 0, stream, (const double*)w.zpart.d(), Mp, nb, M, y_std, lw, bz,
-                     w.zt.d(), Mp, first ? 1 : 0, w.log_s());
+                     w.zt.d(), Mp, first ? 1 : 0, w.log_s(), w.zz ? 1 : 0, w.log_ez());
   LAUNCH_CHECK();
 }
 
@@ -42,6 +42,15 @@ void bobe_gp::wip_score_w(const SweepW& w, const double* crossT, int64_t ldx, co
   with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
     hipLaunchKernelGGL((k_wip_score_w<KE, DC>), grid, dim3(256), sm, stream, crossT, ldx, cst, ldx, (const double*)ZsT.d(), Mp,
                        M, scs, bz, (const double*)w.zt.d(), w.ldt, ns, hyp, y_std * y_std, at(0), at(1), at(2), at(3));
+  });
+}
+
+void bobe_gp::wip_score_zz(const SweepW& w, const double* crossT, int64_t ldx, const double* cst, const double* scs,
+                           const double* bz, int64_t ns, int64_t M, int64_t Mp, double y_std, int64_t off) {
+  const dim3 grid((unsigned)((ns + ZZ_G - 1) / ZZ_G));
+  with_kern_dcap(hyp.kern, d, [&](auto KE, auto DC) {
+    hipLaunchKernelGGL((k_wip_score_zz<KE, DC>), grid, dim3(256), 0, stream, crossT, ldx, cst, ldx, (const double*)ZsT.d(), Mp,
+                       M, scs, bz, (const double*)w.zt.d(), w.ldt, ns, hyp, y_std, w.zz + off);
   });
 }
 
@@ -237,6 +246,45 @@ int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t 
     if (grads[k] && !is_device_ptr(grads[k])) std::memcpy(grads[k], hb + off_g[k], (size_t)C * d * sizeof(double));
   }
   return BOBE_OK;
+}
+
+// bobe_gp_wip_sweep_zvar: the sweep with the evidence-variance scorer alone (SweepW::zz), its argmin by k_argmin_masked with
+// nothing masked (+inf never beats a finite score; all +inf: index 0) and log E[Z] from behind the table.
+int bobe_gp::wip_sweep_zvar(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                            double* zvar, double* log_ez, int64_t* argmin, double* min) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
+  use();
+  const bool want_min = argmin || min;
+  SweepW w;
+  w.logw = logw;
+  SweepReq rq;
+  rq.cand = cand; rq.C = C; rq.Z = Z; rq.M = M; rq.y_std = y_std;
+  CallBuf stage, dmin;
+  if (zvar && is_device_ptr(zvar)) w.zz = zvar;
+  else { stage.ensure((size_t)C * sizeof(double)); w.zz = stage.d(); }
+  rq.w = &w;
+  sweep(rq);
+  dmin.ensure(2 * sizeof(double));
+  if (want_min)
+    hipLaunchKernelGGL(k_argmin_masked, dim3(1), dim3(1024), 0, stream, (const double*)w.zz, C,
+                       reinterpret_cast<int64_t*>(dmin.d() + 1), 0, dmin.d());
+  LAUNCH_CHECK();
+  if (zvar && w.zz != zvar) HIPCHK(hipMemcpyAsync(zvar, w.zz, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, stream));
+  double hb[2] = {0.0, 0.0};
+  if (want_min) HIPCHK(hipMemcpyAsync(hb, dmin.p, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (log_ez) HIPCHK(hipMemcpyAsync(log_ez, w.log_ez(), sizeof(double), hipMemcpyDefault, stream));
+  sync();
+  if (min) *min = hb[0];
+  if (argmin) std::memcpy(argmin, hb + 1, sizeof(int64_t));
+  return BOBE_OK;
+}
+
+int bobe_gp::wip_select_batch_zvar(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                                   int n_batch, int64_t* picks, double* pick_scores, double* stage_scores) {
+  SweepW w;
+  w.logw = logw;
+  return select_batch(cand, C, Z, M, y_std, n_batch, 4, picks, pick_scores, stage_scores, &w);
 }
 
 int bobe_gp::wip_select_batch_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,

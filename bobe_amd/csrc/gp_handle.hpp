@@ -283,9 +283,13 @@ struct SweepKeep {
 struct SweepW {
   const double* logw = nullptr;     // M log-weights, host or device; NULL: the points are draws of the surrogate posterior
   double* out[4] = {nullptr, nullptr, nullptr, nullptr};   // wipv, wipstd, imiqr, eiv
+  // the fifth output: zvar = -log T(c), the expected evidence variance's candidate term (k_wip_score_zz; bobe_gp_wip_sweep_zvar
+  // / bobe_gp_wip_select_batch_zvar).  NULL: the table's lambda row and log E[Z] are not formed, no launch is added.
+  double* zz = nullptr;
   CallBuf zt, zpart, lstage;        // the table [ZTERM_ROWS x Mp] + log S, the partial sums of K(X,Z)^T alpha, logw staged
   int64_t ldt = 0;
   double* log_s() const { return zt.d() + (int64_t)ZTERM_ROWS * ldt; }   // (zt holds 8 doubles behind the table)
+  double* log_ez() const { return log_s() + 1; }
 };
 
 // What bobe_gp::sweep is asked for: C candidates, optionally scored against M integration points Z (Z = NULL: prediction
@@ -760,8 +764,15 @@ struct bobe_gp {
   // k_wip_score_w on ns candidates (wip_score's arguments); writes w.out[k] + off
   void wip_score_w(const bobe::SweepW& w, const double* crossT, int64_t ldx, const double* cst, const double* scs,
                    const double* bz, int64_t ns, int64_t M, int64_t Mp, double y_std, int64_t off);
+  // k_wip_score_zz on ns candidates (the same arguments); writes w.zz + off
+  void wip_score_zz(const bobe::SweepW& w, const double* crossT, int64_t ldx, const double* cst, const double* scs,
+                    const double* bz, int64_t ns, int64_t M, int64_t Mp, double y_std, int64_t off);
   int wip_sweep_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                   double* const outs[4], double* log_s, int64_t* argmin, double* mins);
+  int wip_sweep_zvar(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                     double* zvar, double* log_ez, int64_t* argmin, double* min);
+  int wip_select_batch_zvar(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                            int n_batch, int64_t* picks, double* pick_scores, double* stage_scores);
   int wip_select_batch_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                          int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores);
   // values and input gradients of the four scores through the few-candidate chain, in groups of 16 (WGW_MAX_N: its limit on N)

@@ -290,7 +290,10 @@ void bobe_gp::sweep(const SweepReq& r) {
       if (!sw || d_wipv || d_wipstd || vo)
         wip_score(xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, d_wipv ? d_wipv + s0 : nullptr,
                   d_wipstd ? d_wipstd + s0 : nullptr, vo);
-      if (sw) wip_score_w(*sw, xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, s0);
+      // (the evidence-variance scorer alone: no launch of the four-score pass with nothing to write)
+      if (sw && (!sw->zz || sw->out[0] || sw->out[1] || sw->out[2] || sw->out[3]))
+        wip_score_w(*sw, xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, s0);
+      if (sw && sw->zz) wip_score_zz(*sw, xT, ldC, cst, scs, basez.d(), ns, M, Mp, y_std, s0);
       prof_end(BOBE_PROF_CROSS);
       LAUNCH_CHECK();
     }

@@ -8,9 +8,10 @@
 namespace bobe {
 
 constexpr int MAX_D = 32;
-// rows of the weighted scorer's per-z table (criteria_kernels.hpp, k_wip_zterms): mu, a, omega, e = l + 2 mu + 2 b, l.  The host
-// sizes the table and places log S behind it (gp_handle.hpp, SweepW) with the same constant.
-constexpr int ZTERM_ROWS = 5;
+// rows of the weighted scorer's per-z table (criteria_kernels.hpp, k_wip_zterms): mu, a, omega, e = l + 2 mu + 2 b, l,
+// lambda = l + mu + b / 2 - log E[Z] (written for the evidence-variance scorer only).  The host sizes the table and places
+// log S and log E[Z] behind it (gp_handle.hpp, SweepW) with the same constant.
+constexpr int ZTERM_ROWS = 6;
 
 struct Hyper {
   double ls[MAX_D];

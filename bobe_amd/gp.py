@@ -871,27 +871,38 @@ class GP:
         return lw
 
     def _wip_sweep_w(self, cand, z, log_weights, criteria):
-        """``bobe_gp_wip_sweep_w``: the requested scores in physical units, their argmins / minima and log S."""
+        """``bobe_gp_wip_sweep_w``: the requested scores in physical units, their argmins / minima and log S; the key 'zvar'
+        goes to ``bobe_gp_wip_sweep_zvar`` (a sweep of its own)."""
         keys = self.CRITERIA if criteria is None else tuple(criteria)
         for k in keys:
-            if k not in self.CRITERIA:
-                raise ValueError(f"criteria must be among {self.CRITERIA}, not {k!r}")
+            if k not in self.CRITERIA and k != "zvar":
+                raise ValueError(f"criteria must be among {self.CRITERIA + ('zvar',)}, not {k!r}")
         c, m = int(cand.shape[0]), int(z.shape[0])
         lw = self._log_weights(log_weights, m)
-        arrs = [np.empty(c) if k in keys else None for k in self.CRITERIA]
-        log_s = C.c_double(0.0)
-        am, mn = np.full(4, -1, dtype=np.int64), np.empty(4)
-        _lib.check(self._lib.bobe_gp_wip_sweep_w(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), _lib.ptr(lw),
-                                                 *[_lib.ptr(a) for a in arrs], C.byref(log_s), _lib.ptr(am), _lib.ptr(mn)),
-                   "bobe_gp_wip_sweep_w")
-        # exp(f) lives on the physical scale: the y_mean the library leaves out shifts the log scores by a constant
-        shift = {"wipv": 0.0, "wipstd": 0.0, "imiqr": float(self.y_mean), "eiv": -2.0 * float(self.y_mean)}
         out = {}
-        for i, k in enumerate(self.CRITERIA):
-            if k in keys:
-                out[k] = arrs[i] + shift[k] if shift[k] else arrs[i]
-                out["argmin_" + k], out["min_" + k] = int(am[i]), float(mn[i]) + shift[k]
-        out["log_eiv_total"] = log_s.value + 2.0 * float(self.y_mean)
+        if any(k in self.CRITERIA for k in keys) or not keys:
+            arrs = [np.empty(c) if k in keys else None for k in self.CRITERIA]
+            log_s = C.c_double(0.0)
+            am, mn = np.full(4, -1, dtype=np.int64), np.empty(4)
+            _lib.check(self._lib.bobe_gp_wip_sweep_w(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std),
+                                                     _lib.ptr(lw), *[_lib.ptr(a) for a in arrs], C.byref(log_s), _lib.ptr(am),
+                                                     _lib.ptr(mn)), "bobe_gp_wip_sweep_w")
+            # exp(f) lives on the physical scale: the y_mean the library leaves out shifts the log scores by a constant
+            shift = {"wipv": 0.0, "wipstd": 0.0, "imiqr": float(self.y_mean), "eiv": -2.0 * float(self.y_mean)}
+            for i, k in enumerate(self.CRITERIA):
+                if k in keys:
+                    out[k] = arrs[i] + shift[k] if shift[k] else arrs[i]
+                    out["argmin_" + k], out["min_" + k] = int(am[i]), float(mn[i]) + shift[k]
+            out["log_eiv_total"] = log_s.value + 2.0 * float(self.y_mean)
+        if "zvar" in keys:
+            zv = np.empty(c)
+            lez, zmin, zam = C.c_double(0.0), C.c_double(0.0), C.c_int64(-1)
+            _lib.check(self._lib.bobe_gp_wip_sweep_zvar(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std),
+                                                        _lib.ptr(lw), _lib.ptr(zv), C.byref(lez), C.byref(zam),
+                                                        C.byref(zmin)), "bobe_gp_wip_sweep_zvar")
+            # (omega is normalised: no y_mean in the score; log E[Z] is on the physical scale)
+            out["zvar"], out["argmin_zvar"], out["min_zvar"] = zv, int(zam.value), float(zmin.value)
+            out["log_ez"] = lez.value + float(self.y_mean)
         return out
 
     def wip_sweep(self, candidates, mc_points, want_mean_var=False, *, log_weights=None, criteria=None):
@@ -904,7 +915,13 @@ class GP:
         a constant; None: the points are draws of the surrogate posterior) and / or ``criteria`` (a subset of ``wipv, wipstd,
         imiqr, eiv``; None with weights: all four) select ``bobe_gp_wip_sweep_w`` instead: the result then holds the requested
         scores (to minimise, physical units), ``argmin_<key>`` / ``min_<key>`` for each, and ``log_eiv_total`` = log S (the
-        expected integrated variance of a candidate is ``exp(log_eiv_total) - exp(-eiv)``)."""
+        expected integrated variance of a candidate is ``exp(log_eiv_total) - exp(-eiv)``).
+
+        ``criteria`` also accepts ``'zvar'`` (never implied by None): ``zvar`` = -log T(c), the candidate's term of the expected
+        posterior variance of the evidence estimate Z after one more evaluation (``bobe_gp_wip_sweep_zvar``; to minimise), with
+        ``argmin_zvar`` / ``min_zvar`` and ``log_ez`` = log E[Z]: the expected reduction of Var Z is ``exp(2 log_ez - zvar)``.
+        Its scoring pass grows with M^2 (a pair sum over the integration points).  Requested together with other keys it costs
+        a second device sweep; the other keys' values are those of a call without it, bit for bit."""
         dev = hasattr(candidates, "data_ptr")
         cand = candidates if dev else _lib.as_f64(np.atleast_2d(candidates))
         z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
@@ -946,9 +963,10 @@ class GP:
                            log_weights=None):
         """``wip_select_batch`` with importance-weighted integration points (``log_weights``, see ``wip_sweep``) and the four
         criteria 'wipv', 'wipstd', 'imiqr', 'eiv' (``bobe_gp_wip_select_batch_w``): stage 0 is the weighted ``wip_sweep``
-        (same bits), the scores are physical ones as there.  Without weights 'wipv' / 'wipstd' take the equal-weight entry."""
-        if criterion not in self.CRITERIA:
-            raise ValueError(f"criterion must be one of {self.CRITERIA}, not {criterion!r}")
+        (same bits), the scores are physical ones as there.  Without weights 'wipv' / 'wipstd' take the equal-weight entry.
+        ``criterion='zvar'`` (see ``wip_sweep``) goes to ``bobe_gp_wip_select_batch_zvar``."""
+        if criterion not in self.CRITERIA and criterion != "zvar":
+            raise ValueError(f"criterion must be one of {self.CRITERIA + ('zvar',)}, not {criterion!r}")
         dev = hasattr(candidates, "data_ptr")
         cand = candidates if dev else _lib.as_f64(np.atleast_2d(candidates))
         z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
@@ -956,7 +974,12 @@ class GP:
         picks = np.full(max(nb, 1), -1, dtype=np.int64)
         scores = np.empty(max(nb, 1))
         stage = np.empty((max(nb, 1), c)) if return_stage_scores else None
-        if log_weights is None and criterion in ("wipv", "wipstd"):
+        if criterion == "zvar":
+            lw = self._log_weights(log_weights, m)
+            _lib.check(self._lib.bobe_gp_wip_select_batch_zvar(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std),
+                                                               _lib.ptr(lw), nb, _lib.ptr(picks), _lib.ptr(scores),
+                                                               _lib.ptr(stage)), "bobe_gp_wip_select_batch_zvar")
+        elif log_weights is None and criterion in ("wipv", "wipstd"):
             _lib.check(self._lib.bobe_gp_wip_select_batch(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), nb,
                                                           0 if criterion == "wipv" else 1, _lib.ptr(picks), _lib.ptr(scores),
                                                           _lib.ptr(stage)), "bobe_gp_wip_select_batch")

@@ -243,6 +243,43 @@ int bobe_gp_wip_select_batch_w(bobe_gp_t* gp, const double* cand, int64_t C, con
                                const double* logw, int n_batch, int criterion, int64_t* picks, double* pick_scores,
                                double* stage_scores);
 
+/* The expected variance of the EVIDENCE estimate after one more evaluation, as a sweep criterion (a build addition: the
+ * Bayesian-quadrature criterion for the lognormal estimate exp(f); the reference has no counterpart).  Notation and units are
+ * bobe_gp_wip_sweep_w's (physical, no y_mean).  Z = sum_z e^{l_z} e^{f(z)}; an observation at c moves mu_z by r_z xi,
+ * xi ~ N(0, 1), and lowers b_z by r_z^2, with r_z(c) = y_std cross_z / sqrt(s_c) (cross_z, s_c: the scorer's).  By the law of
+ * total variance
+ *   E_xi[Var+ Z] = Var Z - E[Z]^2 T(c),   T(c) = sum_z sum_z' omega_z omega_z' expm1(r_z r_z'),
+ *   omega = softmax(l_z + mu_z + b_z / 2),   E[Z] = exp(*log_ez),   *log_ez = LSE_z (l_z + mu_z + b_z / 2).
+ * The posterior covariance among the integration points enters the c-independent Var Z only, which is not formed
+ * (bobe_gp_predict_cov supplies it to a caller who wants the absolute figure).  T >= 0; for small r it tends to
+ * (sum_z omega_z r_z)^2.
+ *   zvar[c] = -log T(c), to MINIMISE; the expected reduction of Var Z is exp(2 *log_ez - zvar[c]).  omega is normalised: the
+ *   score carries no y_mean shift (a caller in physical units adds y_mean to *log_ez).
+ * Rules: |r_z| is capped at sqrt(b_z) (b+ >= 0, the counterpart of the scorer's 1e-12 floor on v+); a non-finite cross_z
+ * gives r_z = 0; a candidate whose s_c is not > 0 has every r_z = 0; T <= 0 - every r_z = 0, T underflown, a
+ * rounding-negative T - gives zvar = +inf: the candidate teaches nothing.  +inf never wins the argmin over a finite score;
+ * all +inf: index 0.  No exponent above 0 is taken (every pair is scaled by the candidate's largest possible pair term), so
+ * y_std ~ 4e3 (r r' ~ 1e7, l + mu + b / 2 spread over 1e5) stays finite.
+ * COST: a pair sum over the integration points per candidate, C M^2 / 2 transcendental terms where the other scorers do
+ * C M - the scoring pass can outweigh the sweep it rides on at M = 512.  M is whatever the sweep accepts.
+ * Every sum runs in a fixed order that depends on the candidate and M alone: the same state gives the same bits whatever
+ * C, the chunk width, the neighbours, host or device pointers.  The launch sequence is bobe_gp_wip_sweep_w's with this scorer
+ * in place of the four-score pass.
+ * logw (M, host or device; NULL: l_z = -mu_z), zvar (C, host or device, may be NULL), log_ez / argmin / min (host, one value
+ * each, may be NULL; argmin: first occurrence, NaN counts as minimal).  NOT gated.  The handle's state is left as it was.
+ * BOBE_ERR_ARG: NULL cand / Z, C or M < 1; BOBE_ERR_STATE without a factorised state; a NaN state behaves as in
+ * bobe_gp_wip_sweep (BOBE_OK; the scores are NaN where mu_z is, +inf where only the cross terms are). */
+int bobe_gp_wip_sweep_zvar(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                           const double* logw, double* zvar, double* log_ez, int64_t* argmin, double* min);
+
+/* bobe_gp_wip_select_batch_w with bobe_gp_wip_sweep_zvar's scorer at every stage.  Row 0 of stage_scores and picks[0] are
+ * bobe_gp_wip_sweep_zvar's bits and argmin.  Under the believer append mu_z does not change: omega's l_z + mu_z part is the
+ * call's, its b_z part (and the cap on r_z) follows the downdated base_z, so omega is formed again at every stage.  Same cap,
+ * argument rules and return codes as bobe_gp_wip_select_batch (there is no criterion argument).  NOT gated. */
+int bobe_gp_wip_select_batch_zvar(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                                  const double* logw, int n_batch, int64_t* picks, double* pick_scores,
+                                  double* stage_scores);
+
 /* GP.fantasy_var (gp.py:552-576) for C candidates at once: out is C x M, out[c][z] = var+(z|c)*y_std^2. */
 int bobe_gp_fantasy_var(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                         double* out);

@@ -1,0 +1,109 @@
+"""The cases of the evidence-variance score's tests (tests/test_zvar_cpu.py, tests/test_gpu_zvar.py) and their references, each
+computed once per process: the float64 restatement and the long-double truth of tests/zvar_restatement.py.  Imports nothing
+from bobe_amd."""
+import functools
+
+import numpy as np
+
+import zvar_restatement as R
+
+# shape: (seed, N, d, C, M, chunk, noise, lengthscale, kernel variance) - the weighted criteria's sweep shapes, then M = 1 and
+# M around the scorer's constants: its 8 interleaved z-slices and its z' tile of 64.  The M-edge cases are there for the pair
+# sum's boundaries and stand on the design of "tile_edge" (130 points in 3-D), not on the 64 points in 2-D of "below_the_unroll":
+# there the posterior variances lie within two decades of the noise (base_z 1e-6 .. 1e-4), and the score of a candidate next
+# to a training point (T about 1e-9) measures the cancellation in the sweep's cross = k - G, not the pair sum - at M = 63 on
+# that design the device, whose G comes from the product with the inverse factor, was 1.9e-6 (1 + |truth|) off where the
+# float64 restatement was 2.5e-8, with the restatement's own sum in the DEVICE's order agreeing with it to the last digit.
+SHAPES = {
+    "tile_edge": (103, 130, 3, 300, 77, 0, 1e-6, 0.4, 2.0),
+    "ragged_4chunks": (100, 333, 5, 1001, 100, 256, 1e-6, 0.4, 2.0),
+    "second_z_tile_of_one": (100, 150, 4, 640, 129, 0, 1e-8, 0.6, 10.0),
+    "below_the_unroll": (138, 64, 2, 40, 5, 0, 1e-6, 0.4, 2.0),
+    "m1": (139, 64, 2, 40, 1, 0, 1e-6, 0.4, 2.0),
+    "m7": (140, 130, 3, 40, 7, 0, 1e-6, 0.4, 2.0),
+    "m8": (141, 130, 3, 40, 8, 0, 1e-6, 0.4, 2.0),
+    "m9": (142, 130, 3, 40, 9, 0, 1e-6, 0.4, 2.0),
+    "m63": (143, 130, 3, 40, 63, 0, 1e-6, 0.4, 2.0),
+    "m64": (144, 130, 3, 40, 64, 0, 1e-6, 0.4, 2.0),
+    "m65": (145, 130, 3, 40, 65, 0, 1e-6, 0.4, 2.0),
+    "cand_is_z": (146, 130, 3, 77, 77, 0, 1e-6, 0.4, 2.0),         # the candidates ARE the integration points
+}
+# (shape, kernel, log-weights given, y_std): both kernels, the three scales and both weightings on every sweep shape's list
+SWEEP_CASES = [
+    ("tile_edge", "rbf", True, 1.0), ("tile_edge", "matern", True, 30.0), ("tile_edge", "rbf", False, 4e3),
+    ("tile_edge", "matern", False, 1.0),
+    ("ragged_4chunks", "rbf", True, 30.0), ("ragged_4chunks", "matern", False, 1.0),
+    ("second_z_tile_of_one", "rbf", False, 1.0), ("second_z_tile_of_one", "matern", True, 4e3),
+    ("below_the_unroll", "rbf", True, 1.0), ("below_the_unroll", "matern", False, 4e3), ("below_the_unroll", "rbf", False, 30.0),
+    ("m1", "rbf", True, 1.0), ("m1", "matern", False, 30.0),
+    ("m7", "rbf", True, 1.0), ("m8", "matern", True, 30.0), ("m9", "rbf", False, 1.0),
+    ("m63", "rbf", True, 30.0), ("m64", "matern", False, 1.0), ("m65", "rbf", True, 4e3),
+    ("cand_is_z", "rbf", True, 1.0), ("cand_is_z", "matern", False, 30.0),
+]
+BATCH_CASE = ("tile_edge", "rbf", True, 1.0, 3)
+GAP_MIN = 1e-6
+
+
+def case_id(case):
+    return "%s-%s-%s-ystd%g" % (case[0], case[1], "weights" if case[2] else "posterior_draws", case[3])
+
+
+def case_data(shape, y_std):
+    """tests/test_gpu_weighted_criteria.py::case_data's points, the targets rescaled to the standard deviation ``y_std``
+    (mean kept), and the log-weights 1.5 N(0, 1)."""
+    seed, n, d, c, m = SHAPES[shape][:5]
+    rng = np.random.default_rng(seed)
+    X, cand, Z = rng.uniform(size=(n, d)), rng.uniform(size=(c, d)), rng.uniform(size=(m, d))
+    y = np.sin(3.0 * X[:, 0]) + X[:, 1] ** 2 - X[:, 2 % d] * X[:, 3 % d] + 0.1 * rng.normal(size=n)
+    lw = 1.5 * rng.normal(size=m)
+    y = (y - np.mean(y)) / np.std(y) * y_std + np.mean(y)
+    if shape == "cand_is_z":
+        cand = Z
+    return X, y, cand, Z, lw
+
+
+def standardise(y):
+    mean, std = float(np.mean(y)), float(np.std(y))
+    return (y - mean) / std, mean, std
+
+
+@functools.lru_cache(maxsize=None)
+def states(shape, kernel, y_std):
+    """(float64 state, long-double state, y_mean, y_std as standardised)."""
+    _, n, d, c, m, _, noise, ell, kvar = SHAPES[shape]
+    X, y, cand, Z, _ = case_data(shape, y_std)
+    ys, y_mean, std = standardise(y)
+    ls = np.full(d, ell)
+    return (R.state(kernel, X, ys, cand, Z, ls, kvar, noise, np.float64),
+            R.state(kernel, X, ys, cand, Z, ls, kvar, noise, np.longdouble), y_mean, std)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_reference(case):
+    """{"f64", "truth": zvar [C], "log_ez_f64", "log_ez": physical (y_mean added), "y_std"} of a sweep case."""
+    shape, kernel, weighted, y_std = case
+    s64, sld, y_mean, std = states(shape, kernel, y_std)
+    lw = case_data(shape, y_std)[4] if weighted else None
+    a, b = R.zvar_scores(s64, std, lw), R.zvar_scores(sld, std, lw)
+    return {"f64": np.asarray(a["zvar"], dtype=np.float64), "truth": b["zvar"], "log_ez_f64": float(a["log_ez"]) + y_mean,
+            "log_ez": b["log_ez"] + np.longdouble(y_mean), "y_std": std}
+
+
+@functools.lru_cache(maxsize=None)
+def batch_reference():
+    """(picks, stage scores, gaps) of BATCH_CASE by literal refits: float64, then the long-double truth."""
+    shape, kernel, weighted, y_std, b = BATCH_CASE
+    _, n, d, c, m, _, noise, ell, kvar = SHAPES[shape]
+    X, y, cand, Z, lw = case_data(shape, y_std)
+    ys, _, std = standardise(y)
+    args = (kernel, X, ys, cand, Z, np.full(d, ell), kvar, noise, std, lw if weighted else None, b)
+    return R.literal_batch_zvar(*args, dtype=np.float64), R.literal_batch_zvar(*args, dtype=np.longdouble)
+
+
+def rule(got, f64, truth):
+    """The device's rule, per candidate: |got - truth| <= 4 |float64 restatement - truth| + 1e-7 (1 + |truth|).  Returns
+    (holds everywhere, worst |got - truth| / (1 + |truth|), worst |f64 - truth| / (1 + |truth|))."""
+    got, f64 = np.asarray(got, dtype=np.longdouble), np.asarray(f64, dtype=np.longdouble)
+    err, ref_err = np.abs(got - truth), np.abs(f64 - truth)
+    ok = bool(np.all(err <= 4 * ref_err + np.longdouble(1e-7) * (1 + np.abs(truth))))
+    return ok, float(np.max(err / (1 + np.abs(truth)))), float(np.max(ref_err / (1 + np.abs(truth))))
