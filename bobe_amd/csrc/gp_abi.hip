@@ -766,6 +766,16 @@ int bobe_debug_linv(bobe_gp_t* g, double* Linv) {
   API_END
 }
 
+int bobe_debug_sweep_terms(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ,
+                           double* crossT, double* sc, double* basez) {
+  API_BEGIN
+  NEED(g, "gp is NULL");
+  if (!g->factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  NEED(cand && Z, "NULL argument");
+  return g->debug_sweep_terms(cand, C, Z, M, V, VZ, crossT, sc, basez);
+  API_END
+}
+
 int bobe_debug_time_potrf(bobe_gp_t* g, int reps, double* ms) {
   API_BEGIN
   NEED(g && ms && reps >= 1, "bad argument");

@@ -147,3 +147,45 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
   sync();
   return BOBE_OK;
 }
+
+// bobe_debug_sweep_terms: the sweep of stage 0 above - bobe_gp_wip_sweep's launches in their order, a WIPV row as the scorer's
+// output - into call-local retention buffers, then V_used, V_Z, crossT, s_c and base_z copied to the host without their
+// padding.  The retention buffers and the score row count against select_batch's cap.
+int bobe_gp::debug_sweep_terms(const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ_out,
+                               double* crossT, double* sc_out, double* basez_out) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
+  const int64_t Cp = round_up(C, TILE), Mp = round_up(M, TILE);
+  if (((size_t)(Np + Mp + d + 1) * (size_t)Cp + (size_t)C) * sizeof(double) > BATCH_KEEP_BYTES)
+    throw Err(BOBE_ERR_ARG, "too many candidates: the call's buffers, (Np + Mp + d + 1) x Cp + C doubles, exceed 16 GiB");
+  use();
+  CallBuf cst, vkeep, xT, scb, scores;
+  cst.ensure((size_t)d * Cp * sizeof(double));
+  vkeep.ensure((size_t)Np * Cp * sizeof(double));
+  xT.ensure((size_t)Mp * Cp * sizeof(double));
+  scb.ensure((size_t)Cp * sizeof(double));
+  scores.ensure((size_t)C * sizeof(double));
+  SweepKeep keep;
+  keep.CsT = cst.d();
+  keep.V = vkeep.d();
+  keep.crossT = xT.d();
+  keep.sc = scb.d();
+  keep.ld = Cp;
+  SweepReq rq;
+  rq.cand = cand; rq.C = C; rq.Z = Z; rq.M = M;
+  rq.wipv = scores.d();
+  rq.keep = &keep;
+  sweep(rq);
+  auto rows_out = [&](double* dst, const double* src, int64_t ld, int64_t rows, int64_t cols) {
+    if (dst)
+      HIPCHK(hipMemcpy2DAsync(dst, (size_t)cols * 8, src, (size_t)ld * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyDeviceToHost,
+                              stream));
+  };
+  rows_out(V, keep.V_used, keep.ldv_used, N, C);
+  rows_out(VZ_out, VZ.d(), Mp, N, M);
+  rows_out(crossT, xT.d(), Cp, M, C);
+  rows_out(sc_out, scb.d(), Cp, 1, C);
+  rows_out(basez_out, basez.d(), Mp, 1, M);
+  sync();
+  return BOBE_OK;
+}

@@ -757,6 +757,9 @@ struct bobe_gp {
   // the batch selection itself; w: score with the weighted scorer (criterion 0 .. 3) instead of wip_score (0 / 1)
   int select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,
                    int64_t* picks, double* pick_scores, double* stage_scores, bobe::SweepW* w);
+  // what the sweep forms on the way to its scores (bobe_debug_sweep_terms): the sweep with a SweepKeep, copied out unpadded
+  int debug_sweep_terms(const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ_out, double* crossT,
+                        double* sc_out, double* basez_out);
 
   // ---- gp_criteria.hip: the importance-weighted scoring pass (criteria_kernels.hpp)
   // the per-z table of w for the base_z in bz (first: mu, a, omega as well; else only the terms that follow base_z)

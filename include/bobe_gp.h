@@ -625,6 +625,15 @@ int bobe_debug_tile_gemm(int device, int variant, int tiles_m, int tiles_n, int6
 int bobe_debug_kinv(bobe_gp_t* gp, double* Kinv);
 /* L^-1 (N x N lower) from the current factorisation */
 int bobe_debug_linv(bobe_gp_t* gp, double* Linv);
+/* What the acquisition sweep forms on the way to its scores, for the tests of the intermediates: runs the sweep of
+ * bobe_gp_wip_sweep (the same launches in the same order, a WIPV row as the scorer's output; stage 0 of
+ * bobe_gp_wip_select_batch) into buffers of the call and copies out, row-major and without padding, V [N x C] = L^-1 K(X, C)
+ * (V_Z when the candidates are the integration points: that path forms no V of its own), VZ [N x M] = L^-1 K(X, Z),
+ * crossT [M x C] = V_Z^T V, sc [C] = kself - |V[:, c]|^2 and basez [M] = kself - |V_Z[:, z]|^2.  Host pointers (cand and Z may
+ * be device memory); every output may be NULL.  BOBE_ERR_STATE without a factor, BOBE_ERR_ARG for C < 1, M < 1, a NULL cand
+ * or Z, or a C over which the call's buffers, (Np + Mp + d + 1) x Cp + C doubles, pass bobe_gp_wip_select_batch's 16 GiB. */
+int bobe_debug_sweep_terms(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ,
+                           double* crossT, double* sc, double* basez);
 /* run only the Cholesky factorisation of the current K `reps` times after ONE untimed pass (first touch of the
  * workspace, clocks) and return the mean device time per factorisation in milliseconds (HIP events on the handle's
  * stream).  The two batch forms below time the same way. */

@@ -60,6 +60,8 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
             "append": lambda: lib.bobe_gp_append(h, _p(q[:1]), 1, _p(np.zeros(n + 1))),
             "debug_kinv": lambda: lib.bobe_debug_kinv(h, _p(L)),
             "debug_linv": lambda: lib.bobe_debug_linv(h, _p(L)),
+            "debug_sweep_terms": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 8, _p(Z), 16, None, None, _p(np.empty((16, 8))),
+                                                                    _p(o8), None),
             "time_potrf": lambda: lib.bobe_debug_time_potrf(h, 1, C.byref(val)),
         }
 
@@ -96,7 +98,7 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
     assert lib.bobe_gp_set_data(h, _p(X), _p(y), n) == 0
     assert lib.bobe_gp_set_hyper(h, _p(ls), 1.0, 1e-6) == 0
     needs_factor = {"predict", "wip_sweep", "fantasy_var", "wip_grad", "acq_ei", "predict_grad", "hmc_leapfrog", "hmc_run",
-                    "rwalk", "get_chol", "append", "debug_kinv", "debug_linv"}
+                    "rwalk", "get_chol", "append", "debug_kinv", "debug_linv", "debug_sweep_terms"}
     c = calls(h)
     for name in sorted(needs_factor):
         rc = c[name]()
@@ -114,6 +116,10 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
         "predict Xq NULL": lambda: lib.bobe_gp_predict(h, None, 8, _p(o8), None, 1),
         "sweep M=0": lambda: lib.bobe_gp_wip_sweep(h, _p(q), 8, _p(Z), 0, 1.0, _p(o8b), None, None, None, None, None, None, None),
         "sweep Z NULL": lambda: lib.bobe_gp_wip_sweep(h, _p(q), 8, None, 16, 1.0, _p(o8b), None, None, None, None, None, None, None),
+        "sweep_terms C=0": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 0, _p(Z), 16, None, None, None, _p(o8b), None),
+        "sweep_terms M=0": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 8, _p(Z), 0, None, None, None, _p(o8b), None),
+        "sweep_terms cand NULL": lambda: lib.bobe_debug_sweep_terms(h, None, 8, _p(Z), 16, None, None, None, _p(o8b), None),
+        "sweep_terms Z NULL": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 8, None, 16, None, None, None, _p(o8b), None),
         "wip_grad C=0": lambda: lib.bobe_gp_wip_grad(h, _p(q), 0, _p(Z), 16, 1.0, _p(o8b), None, None, None),
         "acq_ei out NULL": lambda: lib.bobe_gp_acq_ei(h, _p(q), 8, 0.0, 0.0, 0, None),
         "predict_grad var without dvar": lambda: lib.bobe_gp_predict_grad(h, _p(q), 8, _p(o8b), _p(o8b), _p(g8), None),
