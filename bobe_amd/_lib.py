@@ -145,6 +145,9 @@ SIGNATURES = [
     ("bobe_debug_linv", C.c_int, [C.c_void_p, C.c_void_p]),
     ("bobe_debug_sweep_terms", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("bobe_debug_batch_terms", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     ("bobe_debug_time_potrf", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     ("bobe_debug_time_potrf_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),
     ("bobe_debug_time_potrf_lockstep", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),

@@ -766,6 +766,18 @@ int bobe_debug_linv(bobe_gp_t* g, double* Linv) {
   API_END
 }
 
+int bobe_debug_batch_terms(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                           const double* logw, int criterion, int n_stage, const int64_t* forced, double* crossT, double* sc,
+                           double* basez, double* UC, double* UZ, int64_t* picks, double* stage_scores) {
+  API_BEGIN
+  NEED(g, "gp is NULL");
+  if (!g->factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  NEED(cand && Z, "NULL argument");
+  return g->debug_batch_terms(cand, C, Z, M, y_std, logw, criterion, n_stage, forced, crossT, sc, basez, UC, UZ, picks,
+                              stage_scores);
+  API_END
+}
+
 int bobe_debug_sweep_terms(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ,
                            double* crossT, double* sc, double* basez) {
   API_BEGIN

@@ -30,8 +30,11 @@ int bobe_gp::wip_select_batch(const double* cand, int64_t C, const double* Z, in
 // the table's base_z terms from the call's downdated copy and scores with k_wip_score_w.  Everything else is shared.
 // criterion 4 (bobe_gp_wip_select_batch_zvar only: the _w entry refuses it) is the evidence-variance scorer, k_wip_score_zz
 // into SweepW::zz, with the table's lambda row refreshed at every stage like criterion 3's e row.
+// dbg (bobe_debug_batch_terms): the same launches in the same order; a forced pick is a device-to-device copy over the pick
+// record behind the stage's k_argmin_masked, and the state is copied out before the buffers go.  NULL: nothing is added.
 int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch,
-                          int criterion, int64_t* picks, double* pick_scores, double* stage_scores, SweepW* w) {
+                          int criterion, int64_t* picks, double* pick_scores, double* stage_scores, SweepW* w,
+                          const BatchDebug* dbg) {
   if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
   if (n_batch < 1 || n_batch > BATCH_MAX || n_batch > C) throw Err(BOBE_ERR_ARG, "n_batch must be in [1, min(C, 64)]");
   if (criterion < 0 || criterion > (w ? 4 : 1)) throw Err(BOBE_ERR_ARG, "criterion out of range");
@@ -39,6 +42,13 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   const int64_t Cp = round_up(C, TILE), Mp = round_up(M, TILE);
   const int nu = n_batch - 1;                            // u rows kept
+  const int64_t* forced = dbg && nu > 0 ? dbg->forced : nullptr;
+  if (forced)
+    for (int j = 0; j < nu; ++j) {
+      if (forced[j] < 0 || forced[j] >= C) throw Err(BOBE_ERR_ARG, "a forced pick lies outside [0, C)");
+      for (int i = 0; i < j; ++i)
+        if (forced[i] == forced[j]) throw Err(BOBE_ERR_ARG, "a forced pick is repeated");
+    }
   const bool dev_scores = stage_scores && is_device_ptr(stage_scores);
   const size_t n_stage_rows = dev_scores ? 0 : (stage_scores ? (size_t)n_batch : 1);
   const size_t per_col = (size_t)(Np + Mp + d + 1) + (nu > 0 ? (size_t)(nb + nu) : 0);
@@ -47,7 +57,7 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
                             "score rows x C doubles, exceed 16 GiB");
   use();
   const bool wipv = criterion == 0;
-  CallBuf cst, vkeep, xT, scb, bz, scores, vstar, pin, partc, partz, uc, uz, dpick, dval;
+  CallBuf cst, vkeep, xT, scb, bz, scores, vstar, pin, partc, partz, uc, uz, dpick, dval, dforce;
   cst.ensure((size_t)d * Cp * sizeof(double));
   vkeep.ensure((size_t)Np * Cp * sizeof(double));
   xT.ensure((size_t)Mp * Cp * sizeof(double));
@@ -102,6 +112,18 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
     uc.ensure((size_t)nu * Cp * sizeof(double));
     uz.ensure((size_t)nu * Mp * sizeof(double));
     HIPCHK(hipMemcpyAsync(bz.p, basez.p, (size_t)Mp * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  } else if (dbg) {
+    bz.ensure((size_t)Mp * sizeof(double));
+    HIPCHK(hipMemcpyAsync(bz.p, basez.p, (size_t)Mp * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  }
+  auto force = [&](int j) {                              // stage j's pick, before stage j + 1's k_batch_gather reads it
+    if (forced && j < nu)
+      HIPCHK(hipMemcpyAsync(d_picks + j, static_cast<int64_t*>(dforce.p) + j, sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+  };
+  if (forced) {
+    dforce.ensure((size_t)nu * sizeof(int64_t));
+    HIPCHK(hipMemcpyAsync(dforce.p, forced, (size_t)nu * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    force(0);
   }
   for (int j = 1; j < n_batch; ++j) {
     const int nprev = j - 1;
@@ -139,6 +161,19 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
     hipLaunchKernelGGL(k_argmin_masked, dim3(1), dim3(1024), 0, stream, (const double*)row, C, d_picks, j,
                        static_cast<double*>(dval.p) + j);
     LAUNCH_CHECK();
+    force(j);
+  }
+  if (dbg) {
+    auto rows_out = [&](double* dst, const double* src, int64_t ld, int64_t rows, int64_t cols) {
+      if (dst && rows > 0)
+        HIPCHK(hipMemcpy2DAsync(dst, (size_t)cols * 8, src, (size_t)ld * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyDeviceToHost,
+                                stream));
+    };
+    rows_out(dbg->crossT, xT.d(), Cp, M, C);
+    rows_out(dbg->sc, scb.d(), Cp, 1, C);
+    rows_out(dbg->basez, bz.d(), Mp, 1, M);
+    rows_out(dbg->UC, uc.d(), Cp, nu, C);
+    rows_out(dbg->UZ, uz.d(), Mp, nu, M);
   }
   HIPCHK(hipMemcpyAsync(picks, dpick.p, (size_t)n_batch * sizeof(int64_t), hipMemcpyDefault, stream));
   if (pick_scores) HIPCHK(hipMemcpyAsync(pick_scores, dval.p, (size_t)n_batch * sizeof(double), hipMemcpyDefault, stream));
@@ -146,6 +181,24 @@ int bobe_gp::select_batch(const double* cand, int64_t C, const double* Z, int64_
     HIPCHK(hipMemcpyAsync(stage_scores, scores.p, (size_t)n_batch * C * sizeof(double), hipMemcpyDeviceToHost, stream));
   sync();
   return BOBE_OK;
+}
+
+// bobe_debug_batch_terms: select_batch itself with n_stage + 1 stages, routed as the three shipped entries route it (the
+// equal-weight scorer for criterion 0 / 1 without log-weights, else the weighted one; 4: the evidence variance).
+int bobe_gp::debug_batch_terms(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                               int criterion, int n_stage, const int64_t* forced, double* crossT, double* sc_out,
+                               double* basez_out, double* UC, double* UZ, int64_t* picks, double* stage_scores) {
+  if (n_stage < 0 || n_stage > BATCH_MAX - 1) throw Err(BOBE_ERR_ARG, "n_stage must be in [0, 63]");
+  if (criterion < 0 || criterion > 4) throw Err(BOBE_ERR_ARG, "criterion must be 0 .. 4");
+  BatchDebug dbg;
+  dbg.forced = forced; dbg.crossT = crossT; dbg.sc = sc_out; dbg.basez = basez_out; dbg.UC = UC; dbg.UZ = UZ;
+  int64_t own[BATCH_MAX];
+  if (!picks) picks = own;
+  if (!logw && criterion < 2)
+    return select_batch(cand, C, Z, M, y_std, n_stage + 1, criterion, picks, nullptr, stage_scores, nullptr, &dbg);
+  SweepW w;
+  w.logw = logw;
+  return select_batch(cand, C, Z, M, y_std, n_stage + 1, criterion, picks, nullptr, stage_scores, &w, &dbg);
 }
 
 // bobe_debug_sweep_terms: the sweep of stage 0 above - bobe_gp_wip_sweep's launches in their order, a WIPV row as the scorer's

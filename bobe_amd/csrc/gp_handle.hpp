@@ -292,6 +292,17 @@ struct SweepW {
   double* log_ez() const { return log_s() + 1; }
 };
 
+// What bobe_debug_batch_terms adds to a batch selection (bobe_gp::select_batch, gp_batch.hip): picks applied in place of the
+// argmins and the downdated state copied out.  Host pointers, every one may be NULL; the outputs are written without padding.
+struct BatchDebug {
+  const int64_t* forced = nullptr;  // n_batch - 1 picks: forced[j] replaces stage j's argmin before stage j + 1 reads it
+  double* crossT = nullptr;         // M x C
+  double* sc = nullptr;             // C
+  double* basez = nullptr;          // M, the call's copy
+  double* UC = nullptr;             // (n_batch - 1) x C
+  double* UZ = nullptr;             // (n_batch - 1) x M
+};
+
 // What bobe_gp::sweep is asked for: C candidates, optionally scored against M integration points Z (Z = NULL: prediction
 // only).  Every output may be NULL (host or device memory otherwise; the argmin / min ones are host scalars).
 struct SweepReq {
@@ -756,7 +767,12 @@ struct bobe_gp {
                        int64_t* picks, double* pick_scores, double* stage_scores);
   // the batch selection itself; w: score with the weighted scorer (criterion 0 .. 3) instead of wip_score (0 / 1)
   int select_batch(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, int n_batch, int criterion,
-                   int64_t* picks, double* pick_scores, double* stage_scores, bobe::SweepW* w);
+                   int64_t* picks, double* pick_scores, double* stage_scores, bobe::SweepW* w,
+                   const bobe::BatchDebug* dbg = nullptr);
+  // select_batch with n_stage downdates, forced picks and the downdated state copied out (bobe_debug_batch_terms)
+  int debug_batch_terms(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                        int criterion, int n_stage, const int64_t* forced, double* crossT, double* sc_out, double* basez_out,
+                        double* UC, double* UZ, int64_t* picks, double* stage_scores);
   // what the sweep forms on the way to its scores (bobe_debug_sweep_terms): the sweep with a SweepKeep, copied out unpadded
   int debug_sweep_terms(const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ_out, double* crossT,
                         double* sc_out, double* basez_out);

@@ -634,6 +634,23 @@ int bobe_debug_linv(bobe_gp_t* gp, double* Linv);
  * or Z, or a C over which the call's buffers, (Np + Mp + d + 1) x Cp + C doubles, pass bobe_gp_wip_select_batch's 16 GiB. */
 int bobe_debug_sweep_terms(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double* V, double* VZ,
                            double* crossT, double* sc, double* basez);
+/* The batch selection's downdated state, for the tests of its later stages: runs bobe_gp_wip_select_batch's own code (the same
+ * launches in the same order, no kernel of its own) with n_stage + 1 stages, n_stage in [0, 63], that is n_stage rank-one
+ * downdates, and copies out row-major and without padding what the last stage scored from: crossT [M x C], sc [C], basez [M]
+ * (the call's downdated copy; the handle's stays) and the u rows UC [n_stage x C], UZ [n_stage x M] of the downdates.
+ * criterion 0 wipv, 1 wipstd, 2 imiqr, 3 eiv, 4 zvar, routed as the shipped entries route them: 0 / 1 with logw NULL through
+ * bobe_gp_wip_select_batch's scorer, 0 .. 3 otherwise through bobe_gp_wip_select_batch_w's, 4 through
+ * bobe_gp_wip_select_batch_zvar's.  forced (n_stage, host, may be NULL): forced[j] is written over the pick record on the
+ * device after stage j's argmin and before stage j + 1 reads it, so stage j + 1 downdates by forced[j]; the argmins of the
+ * later stages mask the forced picks.  picks (n_stage + 1, may be NULL): the n_stage picks applied, then the last stage's
+ * argmin; stage_scores ((n_stage + 1) x C, may be NULL) as bobe_gp_wip_select_batch's.  With forced equal to the shipped
+ * entry's own picks, or NULL, stage_scores are the shipped entry's bits; n_stage = 0 hands out bobe_debug_sweep_terms' bits.
+ * The state outputs and forced are host pointers, every output may be NULL.  Refusals and the 16 GiB cap are
+ * bobe_gp_wip_select_batch's at n_batch = n_stage + 1; BOBE_ERR_ARG too for n_stage outside [0, 63], a forced index outside
+ * [0, C) or a repeated one, before anything is launched or written. */
+int bobe_debug_batch_terms(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                           const double* logw, int criterion, int n_stage, const int64_t* forced, double* crossT, double* sc,
+                           double* basez, double* UC, double* UZ, int64_t* picks, double* stage_scores);
 /* run only the Cholesky factorisation of the current K `reps` times after ONE untimed pass (first touch of the
  * workspace, clocks) and return the mean device time per factorisation in milliseconds (HIP events on the handle's
  * stream).  The two batch forms below time the same way. */

@@ -29,6 +29,7 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
     acc, ins = np.zeros(8, np.int32), np.zeros(8, np.int32)
     state, adapt = np.zeros((8, 3 * d + 2)), np.tile(np.array([0.1, 0.0, 0.0, 0.0, 0.0]), (8, 1))
     L, al = np.empty((n, n)), np.empty(n)
+    f_outside, f_twice = np.array([0, 8], dtype=np.int64), np.array([3, 3], dtype=np.int64)
 
     def calls(h):
         """Every entry point that takes a handle, with otherwise valid arguments."""
@@ -62,6 +63,8 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
             "debug_linv": lambda: lib.bobe_debug_linv(h, _p(L)),
             "debug_sweep_terms": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 8, _p(Z), 16, None, None, _p(np.empty((16, 8))),
                                                                     _p(o8), None),
+            "debug_batch_terms": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, _p(Z), 16, 1.0, None, 1, 2, None, None, _p(o8),
+                                                                    None, None, None, None, None),
             "time_potrf": lambda: lib.bobe_debug_time_potrf(h, 1, C.byref(val)),
         }
 
@@ -98,7 +101,7 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
     assert lib.bobe_gp_set_data(h, _p(X), _p(y), n) == 0
     assert lib.bobe_gp_set_hyper(h, _p(ls), 1.0, 1e-6) == 0
     needs_factor = {"predict", "wip_sweep", "fantasy_var", "wip_grad", "acq_ei", "predict_grad", "hmc_leapfrog", "hmc_run",
-                    "rwalk", "get_chol", "append", "debug_kinv", "debug_linv", "debug_sweep_terms"}
+                    "rwalk", "get_chol", "append", "debug_kinv", "debug_linv", "debug_sweep_terms", "debug_batch_terms"}
     c = calls(h)
     for name in sorted(needs_factor):
         rc = c[name]()
@@ -120,6 +123,22 @@ def test_every_entry_point_refuses_a_null_handle_and_the_wrong_state():
         "sweep_terms M=0": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 8, _p(Z), 0, None, None, None, _p(o8b), None),
         "sweep_terms cand NULL": lambda: lib.bobe_debug_sweep_terms(h, None, 8, _p(Z), 16, None, None, None, _p(o8b), None),
         "sweep_terms Z NULL": lambda: lib.bobe_debug_sweep_terms(h, _p(q), 8, None, 16, None, None, None, _p(o8b), None),
+        "batch_terms C=0": lambda: lib.bobe_debug_batch_terms(h, _p(q), 0, _p(Z), 16, 1.0, None, 1, 2, None, None, _p(o8b), None,
+                                                              None, None, None, None),
+        "batch_terms Z NULL": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, None, 16, 1.0, None, 1, 2, None, None, _p(o8b),
+                                                                 None, None, None, None, None),
+        "batch_terms n_stage=64": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, _p(Z), 16, 1.0, None, 1, 64, None, None,
+                                                                     _p(o8b), None, None, None, None, None),
+        "batch_terms n_stage=C": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, _p(Z), 16, 1.0, None, 1, 8, None, None,
+                                                                    _p(o8b), None, None, None, None, None),
+        "batch_terms criterion 5": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, _p(Z), 16, 1.0, None, 5, 2, None, None,
+                                                                      _p(o8b), None, None, None, None, None),
+        "batch_terms forced outside": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, _p(Z), 16, 1.0, None, 1, 2,
+                                                                         _p(f_outside), None, _p(o8b), None, None, None,
+                                                                         None, None),
+        "batch_terms forced twice": lambda: lib.bobe_debug_batch_terms(h, _p(q), 8, _p(Z), 16, 1.0, None, 1, 2,
+                                                                       _p(f_twice), None, _p(o8b), None, None, None, None,
+                                                                       None),
         "wip_grad C=0": lambda: lib.bobe_gp_wip_grad(h, _p(q), 0, _p(Z), 16, 1.0, _p(o8b), None, None, None),
         "acq_ei out NULL": lambda: lib.bobe_gp_acq_ei(h, _p(q), 8, 0.0, 0.0, 0, None),
         "predict_grad var without dvar": lambda: lib.bobe_gp_predict_grad(h, _p(q), 8, _p(o8b), _p(o8b), _p(g8), None),

@@ -34,12 +34,19 @@ CASES = [
 ]
 
 
-def make_case(case, kernel="rbf"):
-    from bobe_amd import GP
-    seed, n, d, c, m, b, noise, ell, kvar = case
+def case_arrays(case):
+    """(X, y, cand, Z) of a case."""
+    seed, n, d, c, m = case[:5]
     rng = np.random.default_rng(seed)
     X, cand, Z = rng.uniform(size=(n, d)), rng.uniform(size=(c, d)), rng.uniform(size=(m, d))
     y = np.sin(3.0 * X[:, 0]) + X[:, 1] ** 2 - X[:, 2 % d] * X[:, 3 % d] + 0.1 * rng.normal(size=n)
+    return X, y, cand, Z
+
+
+def make_case(case, kernel="rbf"):
+    from bobe_amd import GP
+    seed, n, d, c, m, b, noise, ell, kvar = case
+    X, y, cand, Z = case_arrays(case)
     gp = GP(X, y, noise=noise, kernel=kernel, lengthscales=np.full(d, ell), kernel_variance=kvar)
     return gp, cand, Z
 
@@ -275,9 +282,30 @@ def test_accepts_the_largest_batch(small):
     gp, cand, Z = small
     r = gp.wip_select_batch(cand, Z, 40, criterion="wipv")                     # min(C, 64) = C: every candidate, once
     assert sorted(r["indices"].tolist()) == list(range(40))
-    gp2, cand2, Z2 = make_case((62, 64, 3, 100, 16, 2, 1e-6, 0.5, 1.0))
-    r = gp2.wip_select_batch(cand2, Z2, 64)
+    case = (62, 64, 3, 100, 16, 2, 1e-6, 0.5, 1.0)
+    gp2, cand2, Z2 = make_case(case)
+    r = gp2.wip_select_batch(cand2, Z2, 64, return_stage_scores=True)
     assert len(set(r["indices"].tolist())) == 64
+    # all 63 downdates against the literal refit of the (N + j)-point believer surrogate in long double, under the rule of
+    # tests/test_gpu_batch_terms.py: the truth's pick at every stage (its two best more than GAP_MIN apart: asserted) and
+    # |device - truth| <= 4 |float64 literal refit - truth| + 1e-7 |truth| for every candidate
+    import batch_terms_restatement as BT
+    X, y, _, _ = case_arrays(case)
+    d = case[2]
+    ys, std = (y - np.mean(y)) / np.std(y), float(np.std(y))
+    assert abs(gp2.y_std / std - 1) < 1e-12
+    args = ("rbf", X, ys, cand2, Z2, np.full(d, case[7]), case[8], case[6], std, None, 64, "wipstd")
+    picks, truth, gaps, _ = BT.append_batch(*args)
+    f64 = BT.literal_batch(*args, dtype=np.float64, follow=picks)[1]
+    assert np.all(gaps > GAP_MIN), gaps.min()
+    assert r["indices"].tolist() == picks.tolist()
+    worst = 0.0
+    for j in range(64):
+        ok, err, ref_err = BT.rule(r["stage_scores"][j], f64[j], truth[j], "wipstd")
+        worst = max(worst, err)
+        assert ok, (j, err, ref_err)
+    print("\nthe largest batch: worst relative error of a stage score against the long-double literal refit %.2e, smallest gap "
+          "%.2e" % (worst, gaps.min()))
 
 
 @pytest.mark.parametrize("criterion", [-1, 2])
