@@ -264,27 +264,33 @@ class WeightedIntegratedPosteriorBase(AcquisitionFunction):
                                  optimizer_options=dict(self.optimizer_options), maxiter=maxiter,
                                  n_restarts=n_restarts, verbose=verbose)
 
+    _grad_entry = "bobe_gp_wip_grad_w"
+
+    def _score_and_grad(self, gp, x, mc_points, log_weights):
+        """(scores (C,), gradients (C, d)) of this criterion alone at the rows of x: what ``_polished_point`` minimises."""
+        r = gp.wip_grad_w(x, mc_points, log_weights=log_weights, criteria=(self._key,))
+        return r[self._key], r["d" + self._key]
+
     def _polished_point(self, gp, mc_points, log_weights, vals, idx, n_starts, maxiter):
-        """``weighted_polish`` = R > 0: SciPy's L-BFGS-B on the score over the unit cube from the R pool rows with the lowest
+        """``weighted_polish`` (ZVar: ``zvar_polish``) = R > 0: SciPy's L-BFGS-B on the score over the unit cube from the R pool rows with the lowest
         score (ties: the lower index), all runs in lock step (the drivers of optim.py) - every round ONE ``GP.wip_grad_w``
-        call on the points still waiting, this criterion alone.  Returns the lowest value among the restarts that finished and
+        (ZVar: ``GP.wip_grad_zvar``) call on the points still waiting, this criterion alone.  Returns the lowest value among the restarts that finished and
         the pool pick itself; ties go to the pool pick, then to the lower restart; a restart that raised or ended non-finite is
         skipped - never worse than the pool pick.  Nothing is drawn from a generator.  A design above the entry's limit on N
         keeps the pool pick (one log line).  Not gated (nor is the equal-weight polish)."""
         from .optim import _minimize_concurrently
         best_x, best_val = np.array(mc_points[idx]), float(vals[idx])
         if gp.train_x.shape[0] > WIP_GRAD_W_MAX_N:
-            log.info(f"{self.name}: {gp.train_x.shape[0]} training points exceed bobe_gp_wip_grad_w's limit of "
+            log.info(f"{self.name}: {gp.train_x.shape[0]} training points exceed {self._grad_entry}'s limit of "
                      f"{WIP_GRAD_W_MAX_N}; the pick stays on the candidate pool")
             return best_x, best_val
-        d, key = mc_points.shape[1], self._key
+        d = mc_points.shape[1]
         order = np.argsort(vals, kind="stable")[:min(int(n_starts), len(vals))]
         starts = np.clip(np.asarray(mc_points[order], dtype=np.float64), 0.0, 1.0)
 
         def batch(ids, xs):
-            r = gp.wip_grad_w(np.array(xs, dtype=np.float64).reshape(len(ids), d), mc_points, log_weights=log_weights,
-                              criteria=(key,))
-            return [(float(f), np.array(g, dtype=np.float64)) for f, g in zip(r[key], r["d" + key])]
+            fs, gs = self._score_and_grad(gp, np.array(xs, dtype=np.float64).reshape(len(ids), d), mc_points, log_weights)
+            return [(float(f), np.array(g, dtype=np.float64)) for f, g in zip(fs, gs)]
 
         results = _minimize_concurrently(batch, starts, True, with_ids=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * d,
                                          options={"maxiter": int(maxiter)})
@@ -329,17 +335,33 @@ class ZVar(WeightedIntegratedPosteriorBase):
     Bayesian-quadrature criterion for the lognormal estimate exp(f), which counts the correlation of the surrogate's errors
     between integration points where WIPV / WIPStd / IMIQR / EIV integrate a pointwise variance (no counterpart in the
     reference).  The score is ``zvar`` = -log T(c) of ``GP.wip_sweep(criteria=('zvar',))``: the expected reduction of Var Z is
-    ``exp(2 log_ez - zvar)``.  Picks from the candidate pool; no gradient form is built, so ``acq_kwargs['weighted_polish']``
-    > 0 is a ValueError."""
+    ``exp(2 log_ez - zvar)``.  Picks from the candidate pool; ``acq_kwargs['zvar_polish'] = R`` (1 ... 16; default 0: the
+    pool pick, as ever) refines the pick as ``_polished_point`` does for the weighted scores - L-BFGS-B on the unit cube from
+    the R best pool rows in lock step, one ``GP.wip_grad_zvar`` call per round (M^2 work per point: a cost of another order
+    than the weighted scores', hence a key of its own), at most ``acq_kwargs['zvar_polish_maxiter']`` (100) iterations; a
+    restart that meets a +inf score ends non-finite and is skipped.  ``acq_kwargs['weighted_polish']`` > 0 stays a
+    ValueError: it names the weighted scores' polish."""
     name: str = "ZVar"
     _key = "zvar"
+    _grad_entry = "bobe_gp_wip_grad_zvar"
+
+    def _score_and_grad(self, gp, x, mc_points, log_weights):
+        r = gp.wip_grad_zvar(x, mc_points, log_weights=log_weights)
+        return r["zvar"], r["dzvar"]
 
     def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 100, n_restarts: int = 1, verbose: bool = True,
                        early_stop_patience: int = 25, rng=None):
-        if _weighted_polish(acq_kwargs if acq_kwargs is not None else {}) > 0:
-            raise ValueError("ZVar has no input-gradient form: weighted_polish must be 0")
-        return super().get_next_point(gp, acq_kwargs=acq_kwargs, maxiter=maxiter, n_restarts=n_restarts, verbose=verbose,
-                                      early_stop_patience=early_stop_patience, rng=rng)
+        kw = acq_kwargs if acq_kwargs is not None else {}
+        if _weighted_polish(kw) > 0:
+            raise ValueError("ZVar's polish is acq_kwargs['zvar_polish']: weighted_polish must be 0")
+        polish = _zvar_polish(kw)
+        if polish == 0:
+            return super().get_next_point(gp, acq_kwargs=acq_kwargs, maxiter=maxiter, n_restarts=n_restarts, verbose=verbose,
+                                          early_stop_patience=early_stop_patience, rng=rng)
+        mc_points, log_weights = self._integration_points(kw, rng)
+        vals, idx = self.sweep(gp, mc_points, mc_points, log_weights=log_weights)          # every score: the starts come from them
+        return self._polished_point(gp, np.asarray(mc_points), log_weights, np.asarray(vals), int(idx), polish,
+                                    int(kw.get("zvar_polish_maxiter", 100)))
 
 
 class PathwiseTS(AcquisitionFunction):
@@ -498,7 +520,7 @@ def _ts_polish(acq_kwargs, mode) -> int:
     return int(r)
 
 
-WIP_GRAD_W_MAX_N = 4096         # bobe_gp_wip_grad_w's limit on the training points (its matrix-vector chain has no tile path)
+WIP_GRAD_W_MAX_N = 4096         # bobe_gp_wip_grad_w's / bobe_gp_wip_grad_zvar's limit on the training points (its matrix-vector chain has no tile path)
 
 
 def _weighted_polish(acq_kwargs) -> int:
@@ -506,6 +528,14 @@ def _weighted_polish(acq_kwargs) -> int:
     r = acq_kwargs.get("weighted_polish", 0)
     if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= 16:
         raise ValueError(f"weighted_polish must be an integer between 0 and 16, not {r!r}")
+    return int(r)
+
+
+def _zvar_polish(acq_kwargs) -> int:
+    """``acq_kwargs['zvar_polish']``: starts of the L-BFGS-B polish of a ZVar pick, an integer 0 (default: none) ... 16"""
+    r = acq_kwargs.get("zvar_polish", 0)
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= 16:
+        raise ValueError(f"zvar_polish must be an integer between 0 and 16, not {r!r}")
     return int(r)
 
 

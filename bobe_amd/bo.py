@@ -220,6 +220,7 @@ class BOBE:
         self.mc_weighted = False
         self.ts_polish = 0
         self.weighted_polish = 0
+        self.zvar_polish = 0
         self.ts_chain_steps, self.ts_chain_warmup = 0, 50
         self.min_delta_seen = np.inf
         self.current_iteration = 0
@@ -592,7 +593,7 @@ class BOBE:
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
             mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
             ts_polish: int = 0, ts_chain_steps: int = 0, ts_chain_warmup: int = 50, path_posterior: int = 0,
-            weighted_polish: int = 0, wip_batch_mode: str = "believer") -> dict:
+            weighted_polish: int = 0, zvar_polish: int = 0, wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
@@ -619,11 +620,14 @@ class BOBE:
         and ``weighted_polish`` - for ``acq`` 'imiqr' / 'eiv' and for ``mc_weighted=True``: R in 1 .. 16 hands
         ``acq_kwargs['weighted_polish'] = R`` to the acquisition, which then refines its pool pick by L-BFGS-B on the score from
         the R best pool rows (``GP.wip_grad_w``; never worse than the pool pick, nothing drawn from the run's generator); 0
-        (default): the pool pick, and an ``acq_kwargs`` without the key.
+        (default): the pool pick, and an ``acq_kwargs`` without the key, and ``zvar_polish`` - for ``acq`` 'zvar' stages
+        only (a ValueError when no stage is 'zvar'): R in 1 .. 16 hands ``acq_kwargs['zvar_polish'] = R`` to ``acquisition.ZVar``,
+        the same refinement on the evidence-variance score (``GP.wip_grad_zvar``, M^2 work per point and round); 0 (default):
+        the pool pick, and an ``acq_kwargs`` without the key.
         ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
         samples; ``acq`` 'zvar' (``acquisition.ZVar``) runs it with the expected posterior variance of the evidence estimate as the
-        criterion (pool picks only: ``weighted_polish`` > 0 with it is a ValueError).  ``acq`` may be a tuple of stages, run one after the other on the
+        criterion (its polish is ``zvar_polish``: ``weighted_polish`` > 0 with it is a ValueError).  ``acq`` may be a tuple of stages, run one after the other on the
         same surrogate (the evident intent of bo.py:1143-1156, whose tuple branch never binds ``acqs``).
 
         WIPV / WIPStd (``run_weighted_integrated_posterior``, bo.py:1226-1385): integration samples once before the
@@ -662,6 +666,9 @@ class BOBE:
                 or not 0 <= int(weighted_polish) <= 16:
             raise ValueError(f"weighted_polish must be an integer between 0 and 16, not {weighted_polish!r}")
         self.weighted_polish = int(weighted_polish)
+        if isinstance(zvar_polish, bool) or not isinstance(zvar_polish, (int, np.integer)) or not 0 <= int(zvar_polish) <= 16:
+            raise ValueError(f"zvar_polish must be an integer between 0 and 16, not {zvar_polish!r}")
+        self.zvar_polish = int(zvar_polish)
         for name, v in (("ts_chain_steps", ts_chain_steps), ("ts_chain_warmup", ts_chain_warmup),
                         ("path_posterior", path_posterior)):
             if isinstance(v, bool) or int(v) != v or int(v) < 0:
@@ -690,7 +697,9 @@ class BOBE:
             if _acq_class(a) is None:
                 raise ValueError(f"Invalid acquisition function '{a}'. Valid options are: {list(_ACQ) + list(_ACQ_MORE)}")
             if a.lower() == "zvar" and self.weighted_polish > 0:
-                raise ValueError("acq='zvar' has no input-gradient form: weighted_polish must be 0")
+                raise ValueError("acq='zvar' is polished by zvar_polish: weighted_polish must be 0")
+        if self.zvar_polish > 0 and not any(a.lower() == "zvar" for a in acqs):
+            raise ValueError(f"zvar_polish polishes acq='zvar' stages, and there is none in {acqs!r}")
         self.current_iteration = self.start_iteration
         rs, self._resume_state = self._resume_state, None        # (a second run() on this object starts from its current state)
         # A tuple of acquisition functions runs as stages, one after the other (bo.py:1149-1158); a saved run state names the
@@ -828,6 +837,8 @@ class BOBE:
                 acq_kwargs["ts_polish"] = self.ts_polish
             if self.weighted_polish > 0:
                 acq_kwargs["weighted_polish"] = self.weighted_polish
+            if self.zvar_polish > 0 and getattr(self.acquisition, "_key", None) == "zvar":
+                acq_kwargs["zvar_polish"] = self.zvar_polish
             if self.ts_chain_steps > 0:
                 acq_kwargs.update(ts_mode="posterior", ts_chain_steps=self.ts_chain_steps,
                                   ts_chain_warmup=self.ts_chain_warmup)

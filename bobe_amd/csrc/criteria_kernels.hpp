@@ -707,4 +707,193 @@ __global__ __launch_bounds__(256) void k_wg_final_w(const double* __restrict__ z
   }
 }
 
+// ---- input gradient of the evidence-variance score for a HANDFUL of candidates (bobe_gp_wip_grad_zvar) --------------------
+// zvar = -log T(c) (k_wip_score_zz above) is a function of the r_z alone: with h_c, p_z, E_z and the scaled pair sum T_s as
+// there (zvar = -(2 h_c + log T_s)) and
+//   G_z = sum_z' r_z' exp(p_z + p_z' + r_z r_z')        (the diagonal included; every exponent <= 0, nothing subtracted)
+//   d zvar / dx_j = sum_z rho_z d r_z / dx_j,   rho_z = -2 G_z / T_s,   d r_z / dx_j = w1 d cross_z / dx_j + w2_z d s / dx_j,
+//   w1 = y_std / sqrt(s),   w2_z = -r_z / (2 s)
+// - the chain above with other weights: wg_front and k_wg_cross_w (mask 1: cross_z and s_c, no log-sum-exp pairs) in front,
+// k_wg_rows_w<., ., 1> and k_wg_final_w (criterion slot 0) behind, and three stages in place of k_wg_weights_w:
+//   k_wg_zv_r     per candidate: r_z under k_wip_score_zz::r_of's rules with the "constant" flag, h_c, p_z, E_z
+//   k_wg_zv_pair  the hot one, M^2 pairs per candidate: G_z and z's row t_z = sum_z' pair(z, z') of the pair sum
+//   k_wg_zv_fold  per candidate: T_s, the score, rho_z, rho w1 into wv and sum rho w2, D_z[j] into zs (k_wg_weights_w's layout)
+// "Gradient of where": a z whose r_z was cut to its cap, whose cross_z is not finite, or whose candidate has s_c not > 0, is a
+// constant - it keeps its value in T and G and has rho_z = 0.  T_s <= 0 (or NaN): the score is k_wip_score_zz's (+inf, NaN)
+// and every rho_z is 0.  No atomics; every sum runs in a fixed order that depends on the candidate and M alone.
+constexpr int ZV_T = 256;                   // z' per LDS tile of k_wg_zv_pair (one per thread to load)
+
+// One workgroup of 256 per candidate, thread t owning z = t, t + 256, ... (padding: r = 0, constant, p = 0, E = 0).
+__global__ __launch_bounds__(256) void k_wg_zv_r(const double* __restrict__ crossA, int64_t lda,
+                                                 const double* __restrict__ sA, const double* __restrict__ basez,
+                                                 const double* __restrict__ zt, int64_t ldt, int64_t m, int64_t mp,
+                                                 double ystd, double* __restrict__ rA, double* __restrict__ pA,
+                                                 double* __restrict__ eA, double* __restrict__ constA,
+                                                 double* __restrict__ hA) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  const int64_t c = blockIdx.x;
+  crossA += c * lda;
+  rA += c * lda;
+  pA += c * lda;
+  eA += c * lda;
+  constA += c * lda;
+  const double* lam = zt + 5 * ldt;
+  const double s = sA[c];
+  const double scale = (s > 0.0) ? ystd / sqrt(s) : 0.0;
+  const bool dead = !(s > 0.0);
+  const double ystd2 = ystd * ystd;
+  double hm = -INFINITY;
+  for (int64_t z = t; z < mp; z += 256) {
+    if (z >= m) {
+      rA[z] = 0.0;
+      constA[z] = 1.0;
+      continue;
+    }
+    const double cross = crossA[z];
+    double b = basez[z];
+    if (!(b >= NOISE_FLOOR) || b > 1.79769313486231571e308) b = NOISE_FLOOR;
+    const double cap = sqrt(b * ystd2);
+    double r = cross * scale;
+    bool cst = dead || !(fabs(cross) <= 1.79769313486231571e308);
+    if (cst) r = 0.0;
+    if (r > cap) { r = cap; cst = true; }
+    if (r < -cap) { r = -cap; cst = true; }
+    rA[z] = r;
+    constA[z] = cst ? 1.0 : 0.0;
+    const double q = lam[z] + 0.5 * (r * r);
+    hm = (q > hm || q != q) ? q : hm;
+  }
+  hm = block_fold256<true>(red, hm);
+  for (int64_t z = t; z < mp; z += 256) {
+    const double p = (z < m) ? lam[z] - hm : 0.0;
+    pA[z] = p;
+    eA[z] = (z < m) ? exp(p) : 0.0;
+  }
+  if (t == 0) hA[c] = hm;
+}
+
+// The pair pass: one workgroup = 64 integration points z (lane) x 4 interleaved quarters of the z' (wave: z' = wave, wave + 4,
+// ...), grid (mp / 64, candidates) - a handful of candidates still fills the chip.  The z' pass through LDS in tiles of ZV_T
+// (r, p, E of the tile; every lane of a wave reads the same z': a broadcast, no bank conflict), so M is not capped.  A pair
+// costs one transcendental: |x| < 1 (x = r_z r_z') takes u = E E' expm1(x) for the pair sum and E E' + u = E E' e^x for G,
+// any other pair v = exp(p + p' + x) for G and v - E E' for the pair sum (k_wip_score_zz's pair()).  Every quarter sums its
+// z' in ascending order; the quarters are combined as (0 + 1) + (2 + 3).  Padding lanes write 0.
+__global__ __launch_bounds__(256) void k_wg_zv_pair(const double* __restrict__ rA, const double* __restrict__ pA,
+                                                    const double* __restrict__ eA, int64_t lda, int64_t m,
+                                                    double* __restrict__ tA, double* __restrict__ gA) {
+  __shared__ double rs[ZV_T], ps[ZV_T], es[ZV_T], redt[4][64], redg[4][64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t c = blockIdx.y, z = (int64_t)blockIdx.x * 64 + lane;
+  rA += c * lda;
+  pA += c * lda;
+  eA += c * lda;
+  const bool in = z < m;
+  const double r = in ? rA[z] : 0.0, p = in ? pA[z] : 0.0, e = in ? eA[z] : 0.0;
+  double tz = 0.0, gz = 0.0;
+  for (int64_t j0 = 0; j0 < m; j0 += ZV_T) {
+    __syncthreads();
+    const int zn = (m - j0 < ZV_T) ? (int)(m - j0) : ZV_T;
+    if (t < zn) {
+      rs[t] = rA[j0 + t];
+      ps[t] = pA[j0 + t];
+      es[t] = eA[j0 + t];
+    }
+    __syncthreads();
+    for (int k = wave; k < zn; k += 4) {            // (ZV_T is a multiple of 4: k and j0 + k fall into the same quarter)
+      const double rp = rs[k], x = r * rp, ee = e * es[k];
+      double pr, ex;
+      if (fabs(x) < 1.0) {
+        pr = ee * expm1(x);
+        ex = ee + pr;
+      } else {
+        ex = exp((p + ps[k]) + x);
+        pr = ex - ee;
+      }
+      tz += pr;
+      gz = __builtin_fma(rp, ex, gz);
+    }
+  }
+  redt[wave][lane] = tz;
+  redg[wave][lane] = gz;
+  __syncthreads();
+  if (wave == 0) {
+    tA[c * lda + z] = in ? (redt[0][lane] + redt[1][lane]) + (redt[2][lane] + redt[3][lane]) : 0.0;
+    gA[c * lda + z] = in ? (redg[0][lane] + redg[1][lane]) + (redg[2][lane] + redg[3][lane]) : 0.0;
+  }
+}
+
+// One workgroup of 256 per candidate, thread t owning z = t, t + 256, ... as in k_wg_weights_w, whose sums' order (the
+// thread's own z ascending, lanes by chain_wave_sum, then the four waves) and whose outputs it keeps: T_s = sum_z t_z, the
+// score (k_wip_score_zz's last line), rho_z, the weight vector rho w1 into wv[c * lda + z] (constants and padding: 0) and sum
+// rho w2, the score, Dz[j] = sum rho w1 G_z (s_zj - s_xj) into zs[(c * 4 + 0) * WGW_ZS + ...]: criterion slot 0 of k_wg_final_w.
+template <int KERN, int DCAP>
+__global__ __launch_bounds__(256) void k_wg_zv_fold(const double* __restrict__ ZsT, int64_t ldz, int64_t m, int64_t mp,
+                                                    const double* __restrict__ cand, Hyper h, double ystd,
+                                                    const double* __restrict__ rA, const double* __restrict__ constA,
+                                                    const double* __restrict__ tA, const double* __restrict__ gA,
+                                                    int64_t lda, const double* __restrict__ sA,
+                                                    const double* __restrict__ hA, double* __restrict__ wv,
+                                                    double* __restrict__ zs) {
+  __shared__ double red[4][WGW_ZS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t c = blockIdx.x;
+  rA += c * lda;
+  constA += c * lda;
+  tA += c * lda;
+  gA += c * lda;
+  double* wk = wv + c * lda;
+  double tot = 0.0;
+  for (int64_t z = t; z < m; z += 256) tot += tA[z];
+  tot = chain_wave_sum(tot);
+  if (lane == 0) red[wave][0] = tot;
+  __syncthreads();
+  tot = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+  const bool ok = tot > 0.0;
+  const double s = sA[c];
+  const double w1 = (s > 0.0) ? ystd / sqrt(s) : 0.0;
+  double xc[DCAP];
+#pragma unroll
+  for (int j = 0; j < DCAP; ++j) xc[j] = (j < h.d) ? cand[c * h.d + j] / h.ls[j] : 0.0;
+  double s2 = 0.0, dzs[DCAP];
+#pragma unroll
+  for (int j = 0; j < DCAP; ++j) dzs[j] = 0.0;
+  for (int64_t z = t; z < mp; z += 256) {
+    if (z >= m || !ok || constA[z] != 0.0) {
+      wk[z] = 0.0;
+      continue;
+    }
+    const double rho = -2.0 * gA[z] / tot;
+    const double a = rho * w1;
+    wk[z] = a;
+    s2 += rho * (-rA[z] / (2.0 * s));
+    double dz[DCAP];
+    double r2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) {
+      dz[j] = (j < h.d) ? ZsT[j * ldz + z] - xc[j] : 0.0;
+      r2 += dz[j] * dz[j];
+    }
+    const double kz = kern_eval<KERN>(r2, h.kvar);
+    const double ag = a * kern_grad_factor<KERN>(r2, h.kvar, kz);
+#pragma unroll
+    for (int j = 0; j < DCAP; ++j) dzs[j] = __builtin_fma(ag, dz[j], dzs[j]);
+  }
+  __syncthreads();                                 // (the readers of red[.][0] are through)
+  {
+    const double a = chain_wave_sum(s2);
+    if (lane == 0) red[wave][0] = a;
+  }
+#pragma unroll
+  for (int j = 0; j < DCAP; ++j) {
+    if (j < h.d) {                                 // uniform
+      const double a = chain_wave_sum(dzs[j]);
+      if (lane == 0) red[wave][2 + j] = a;
+    }
+  }
+  __syncthreads();
+  if (t < 2 + h.d && t != 1) zs[c * 4 * WGW_ZS + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+  if (t == 1) zs[c * 4 * WGW_ZS + 1] = ok ? -(2.0 * hA[c] + log(tot)) : ((tot <= 0.0) ? INFINITY : tot);
+}
+
 }  // namespace bobe

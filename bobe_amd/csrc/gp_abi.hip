@@ -498,6 +498,14 @@ int bobe_gp_wip_grad_w(bobe_gp_t* g, const double* cand, int64_t C, const double
   API_END
 }
 
+int bobe_gp_wip_grad_zvar(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                          const double* logw, double* zvar, double* dzvar, double* log_ez) {
+  API_BEGIN
+  NEED(g && cand && Z, "NULL argument");
+  return g->wip_grad_zvar(cand, C, Z, M, y_std, logw, zvar, dzvar, log_ez);
+  API_END
+}
+
 int bobe_gp_acq_ei(bobe_gp_t* g, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out) {
   API_BEGIN
   NEED(g && Xq && out, "NULL argument");

@@ -6,9 +6,9 @@
 // before it returns.  One buffer of the handle is written: kXZ, the sweep workspace's K(X, Z), which prepare_z fills and
 // nothing reads once prepare_z is through (the substitution path overwrites it there) - scratch, rewritten here with its
 // own bits; the handle's Z-side STATE (ZsT, V_Z, base_z and prepare_z's cache of them) is read, never written.
-// bobe_gp_wip_grad_w (values and input gradients of the four scores through bobe_gp_wip_grad's few-candidate chain) is the one
-// entry here that goes through prepare_z itself and keeps something between calls: the per-z table beside prepare_z's cache
-// (bobe_gp::zw), its workspace and its staged outputs.
+// bobe_gp_wip_grad_w (values and input gradients of the four scores through bobe_gp_wip_grad's few-candidate chain) and
+// bobe_gp_wip_grad_zvar (the same for the evidence-variance score) are the entries here that go through prepare_z themselves
+// and keep something between calls: the per-z table beside prepare_z's cache (bobe_gp::zw), their workspace and staged outputs.
 #include "gp_handle.hpp"
 
 #include "batch_kernels.hpp"
@@ -16,7 +16,7 @@
 
 using namespace bobe;
 
-void bobe_gp::wip_zterms(SweepW& w, int64_t M, int64_t Mp, double y_std, const double* bz, bool first) {
+void bobe_gp::wip_zterms(SweepW& w, int64_t M, int64_t Mp, double y_std, const double* bz, bool first, bool lam) {
   const double* lw = nullptr;
   if (first) {
     w.ldt = Mp;
@@ -30,7 +30,7 @@ void bobe_gp::wip_zterms(SweepW& w, int64_t M, int64_t Mp, double y_std, const d
     kernel_matrix_cross(XsT.d(), Np, N, Np, ZsT.d(), Mp, M, Mp, hyp, kXZ.d(), Mp, (const double*)alpha.d(), w.zpart.d(), Mp);
   }
   hipLaunchKernelGGL(k_wip_zterms, dim3(1), dim3(256), 0, stream, (const double*)w.zpart.d(), Mp, nb, M, y_std, lw, bz,
-                     w.zt.d(), Mp, first ? 1 : 0, w.log_s(), w.zz ? 1 : 0, w.log_ez());
+                     w.zt.d(), Mp, first ? 1 : 0, w.log_s(), (w.zz || lam) ? 1 : 0, w.log_ez());
   LAUNCH_CHECK();
 }
 
@@ -115,17 +115,64 @@ int bobe_gp::wip_sweep_w(const double* cand, int64_t C, const double* Z, int64_t
 // to 16 candidates: wg_front (bobe_gp_wip_grad's first stages) -> k_wg_cross_w -> k_wg_weights_w -> k_wg_rows_w -> k_wg_final_w.
 int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                         double* const scores[4], double* const grads[4]) {
+  int mask = 0;
+  for (int k = 0; k < 4; ++k)
+    if (scores[k] || grads[k]) mask |= 1 << k;
+  return wip_grad_chain("bobe_gp_wip_grad_w", cand, C, Z, M, y_std, logw, scores, grads, mask, false, nullptr);
+}
+
+// Value and input gradient of the evidence-variance score (criteria_kernels.hpp, "input gradient of the evidence-variance
+// score"): the same chain with k_wg_zv_r -> k_wg_zv_pair -> k_wg_zv_fold in k_wg_weights_w's place, criterion slot 0.
+int bobe_gp::wip_grad_zvar(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
+                           double* zvar, double* dzvar, double* log_ez) {
+  double* const scores[4] = {zvar, nullptr, nullptr, nullptr};
+  double* const grads[4] = {dzvar, nullptr, nullptr, nullptr};
+  return wip_grad_chain("bobe_gp_wip_grad_zvar", cand, C, Z, M, y_std, logw, scores, grads, (zvar || dzvar) ? 1 : 0, true,
+                        log_ez);
+}
+
+// The per-z table of the few-candidate chains: the handle's copy (bobe_gp::zw) while Z, the log-weights and y_std are the ones
+// it was made for.  lam: the lambda row and log E[Z] as well (bobe_gp_wip_grad_zvar) - added to a kept table that lacks them
+// by the table's second half alone (k_wip_zterms with first = 0: the e row and log S are rewritten with their own bits).
+void bobe_gp::wip_grad_table(int64_t M, int64_t Mp, double y_std, const double* logw, bool lam) {
+  const bool host_lw = logw && !is_device_ptr(logw);
+  const bool hit = zw_valid && zw_m == M && zw_ystd == y_std && zw_has_logw == (logw != nullptr) && (!logw || host_lw) &&
+                   (!logw || std::memcmp(zw_logw.data(), logw, (size_t)M * sizeof(double)) == 0);
+  if (hit) {
+    if (lam && !zw_lam) {
+      wip_zterms(zw, M, Mp, y_std, basez.d(), false, true);
+      zw_lam = true;
+    }
+    return;
+  }
+  zw_valid = false;
+  zw.logw = logw;
+  wip_zterms(zw, M, Mp, y_std, basez.d(), true, lam);
+  zw.logw = nullptr;
+  zw_lam = lam;
+  // (a device Z leaves prepare_z without a cache - z_seen_m < 0 - and device log-weights cannot be compared: no table kept)
+  if (z_seen_m == M && (!logw || host_lw)) {
+    zw_valid = true;
+    zw_m = M;
+    zw_ystd = y_std;
+    zw_has_logw = logw != nullptr;
+    if (logw) zw_logw.assign(logw, logw + M);
+  }
+}
+
+// mask: the criteria of k_wg_weights_w asked for; zv: the evidence-variance stages instead (mask 1: their slot).
+int bobe_gp::wip_grad_chain(const char* entry, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                            const double* logw, double* const scores[4], double* const grads[4], int mask, bool zv,
+                            double* log_ez) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
   if (C <= 0 || M <= 0) throw Err(BOBE_ERR_ARG, "C and M must be positive");
-  int mask = 0, nv = 0;
-  for (int k = 0; k < 4; ++k)
-    if (scores[k] || grads[k]) {
-      mask |= 1 << k;
-      ++nv;
-    }
-  if (!mask) throw Err(BOBE_ERR_ARG, "bobe_gp_wip_grad_w: no criterion requested (every scores[k] and grads[k] is NULL)");
+  int nv = 0;
+  for (int k = 0; k < 4; ++k) nv += (mask >> k) & 1;
+  if (!mask)
+    throw Err(BOBE_ERR_ARG, std::string(entry) + (zv ? ": no output requested (zvar and dzvar are NULL)"
+                                                     : ": no criterion requested (every scores[k] and grads[k] is NULL)"));
   if (N > WGW_MAX_N)
-    throw Err(BOBE_ERR_ARG, "bobe_gp_wip_grad_w: " + std::to_string(N) + " training points exceed the matrix-vector chain's " +
+    throw Err(BOBE_ERR_ARG, std::string(entry) + ": " + std::to_string(N) + " training points exceed the matrix-vector chain's " +
                                 "limit of " + std::to_string(WGW_MAX_N) + " (there is no tile path)");
   use();
   const int64_t Mp = round_up(M, TILE), G = std::min<int64_t>(C, 16);
@@ -133,28 +180,12 @@ int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t 
   const bool cand_pinned = C <= 16 && !is_device_ptr(cand);
   const double* cin = cand_pinned ? nullptr : fetch(cand, (size_t)C * d, in_stage);
   prepare_z(Z, M, Mp, true);                             // ZsT, V_Z, W_Z, base_z (forget_z on a miss drops the table too)
-  // the per-z table: the handle's copy while Z, the log-weights and y_std are the ones it was made for
-  const bool host_lw = logw && !is_device_ptr(logw);
-  const bool hit = zw_valid && zw_m == M && zw_ystd == y_std && zw_has_logw == (logw != nullptr) && (!logw || host_lw) &&
-                   (!logw || std::memcmp(zw_logw.data(), logw, (size_t)M * sizeof(double)) == 0);
-  if (!hit) {
-    zw_valid = false;
-    zw.logw = logw;
-    wip_zterms(zw, M, Mp, y_std, basez.d(), true);
-    zw.logw = nullptr;
-    // (a device Z leaves prepare_z without a cache - z_seen_m < 0 - and device log-weights cannot be compared: no table kept)
-    if (z_seen_m == M && (!logw || host_lw)) {
-      zw_valid = true;
-      zw_m = M;
-      zw_ystd = y_std;
-      zw_has_logw = logw != nullptr;
-      if (logw) zw_logw.assign(logw, logw + M);
-    }
-  }
+  wip_grad_table(M, Mp, y_std, logw, zv);
   const int nzw = (int)(Mp / 64), nnw = (int)((N + WGW_ROWS - 1) / WGW_ROWS);
   const size_t n_vec = (size_t)G * Np, n_a = (size_t)G * Mp;
   const size_t n_pn = (size_t)G * nnw * (nv + 1) * MAX_D;
-  wgw_ws.ensure((6 * n_vec + (3 + 4) * n_a + 16 + (size_t)G * nzw * 4 + (size_t)G * 4 * WGW_ZS + n_pn) * sizeof(double));
+  wgw_ws.ensure((6 * n_vec + (3 + 4) * n_a + 16 + (size_t)G * nzw * 4 + (size_t)G * 4 * WGW_ZS + n_pn +
+                 (zv ? 6 * n_a + 16 : 0)) * sizeof(double));
   double* kc = wgw_ws.d();
   double* vv = kc + n_vec;
   double* uu = vv + n_vec;
@@ -169,6 +200,13 @@ int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t 
   double* pairs = sA + 16;
   double* zs = pairs + (size_t)G * nzw * 4;
   double* pn = zs + (size_t)G * 4 * WGW_ZS;
+  double* rA = pn + n_pn;                           // zv: r, p, E, the constant flag, t, G [G][Mp] each, and h_c
+  double* pA = rA + n_a;
+  double* eA = pA + n_a;
+  double* constA = eA + n_a;
+  double* tA = constA + n_a;
+  double* gA = tA + n_a;
+  double* hA = gA + n_a;
   // outputs: a device pointer is written directly; the host ones share one block, requested arrays back to back - the pinned
   // result block (128 doubles, written by the last stage itself: no copy command) when there is no device output, one group
   // and they fit, else a staged block that ONE copy brings back
@@ -213,10 +251,20 @@ int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t 
                          stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)vv, clater,
                          h, kself, (const double*)basez.d(), y_std * y_std, (const double*)zw.zt.d(), zw.ldt, mask, crossA,
                          vplusA, flagA, Mp, sA, pairs);
-      hipLaunchKernelGGL((k_wg_weights_w<KE, DC>), dim3((unsigned)g), dim3(256), 0, stream, (const double*)ZsT.d(), Mp, M,
-                         Mp, clater, h, y_std * y_std, (const double*)zw.zt.d(), zw.ldt, mask, logw ? 0 : 1,
-                         (const double*)crossA, (const double*)vplusA, (const double*)flagA, Mp, (const double*)sA,
-                         (const double*)pairs, nzw, G, wv, zs);
+      if (zv) {
+        hipLaunchKernelGGL(k_wg_zv_r, dim3((unsigned)g), dim3(256), 0, stream, (const double*)crossA, Mp, (const double*)sA,
+                           (const double*)basez.d(), (const double*)zw.zt.d(), zw.ldt, M, Mp, y_std, rA, pA, eA, constA, hA);
+        hipLaunchKernelGGL(k_wg_zv_pair, dim3((unsigned)nzw, (unsigned)g), dim3(256), 0, stream, (const double*)rA,
+                           (const double*)pA, (const double*)eA, Mp, M, tA, gA);
+        hipLaunchKernelGGL((k_wg_zv_fold<KE, DC>), dim3((unsigned)g), dim3(256), 0, stream, (const double*)ZsT.d(), Mp, M,
+                           Mp, clater, h, y_std, (const double*)rA, (const double*)constA, (const double*)tA,
+                           (const double*)gA, Mp, (const double*)sA, (const double*)hA, wv, zs);
+      } else {
+        hipLaunchKernelGGL((k_wg_weights_w<KE, DC>), dim3((unsigned)g), dim3(256), 0, stream, (const double*)ZsT.d(), Mp, M,
+                           Mp, clater, h, y_std * y_std, (const double*)zw.zt.d(), zw.ldt, mask, logw ? 0 : 1,
+                           (const double*)crossA, (const double*)vplusA, (const double*)flagA, Mp, (const double*)sA,
+                           (const double*)pairs, nzw, G, wv, zs);
+      }
       auto rows = [&](auto NV) {
         // (KE, DC are captured: their types carry the values)
         hipLaunchKernelGGL((k_wg_rows_w<decltype(KE)::value, decltype(DC)::value, decltype(NV)::value>),
@@ -240,6 +288,7 @@ int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t 
     HIPCHK(hipMemcpyAsync(wgw_host.data(), wgw_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, stream));
     hb = wgw_host.data();
   }
+  if (log_ez) HIPCHK(hipMemcpyAsync(log_ez, zw.log_ez(), sizeof(double), hipMemcpyDefault, stream));
   sync();
   for (int k = 0; k < 4; ++k) {
     if (scores[k] && !is_device_ptr(scores[k])) std::memcpy(scores[k], hb + off_s[k], (size_t)C * sizeof(double));

@@ -407,11 +407,12 @@ struct bobe_gp {
   int64_t z_seen_m = -1;
   bool wz_ready = false;        // W_Z = K^-1 K(X,Z) (the score GRADIENTS need it; the sweep itself does not)
   void forget_z() { z_seen_m = -1; wz_ready = false; zw_valid = false; }
-  // bobe_gp_wip_grad_w keeps the weighted scorer's per-z table (mu, a, omega, e, l) beside them: valid while prepare_z's cache
+  // bobe_gp_wip_grad_w and bobe_gp_wip_grad_zvar keep the weighted scorer's per-z table (mu, a, omega, e, l) beside them: valid while prepare_z's cache
   // is valid AND the log-weights (host memory; device ones are never taken as seen) have the same bytes, or are absent
   // again, and y_std is the same.  A hit launches neither wip_zterms' K(X,Z) assembly nor k_wip_zterms.
   bobe::SweepW zw;              // (its buffers are released with the handle)
   bool zw_valid = false, zw_has_logw = false;
+  bool zw_lam = false;          // the table holds the lambda row and log E[Z] as well (bobe_gp_wip_grad_zvar asked for them)
   std::vector<double> zw_logw;
   double zw_ystd = 0.0;
   int64_t zw_m = -1;
@@ -424,7 +425,7 @@ struct bobe_gp {
   int num_cus = 0;
   // sweep / predict workspace
   DBuf wg_ws;     // workspace of bobe_gp_wip_grad's few-candidates path
-  DBuf wgw_ws, wgw_out;   // workspace and staged outputs of bobe_gp_wip_grad_w
+  DBuf wgw_ws, wgw_out;   // workspace and staged outputs of bobe_gp_wip_grad_w / bobe_gp_wip_grad_zvar
   std::vector<double> wgw_host;   // where the one copy of the staged outputs lands before they go to the caller's arrays
   DBuf in_stage, z_stage, CsT, ZsT, kXC, kXZ, VZ, WZ, basez, sc, qpart, pv, ps, o_mean, o_var, o_wipv, o_wipstd,
       o_misc, kin_a, kin_b, kout, vxc, vxc2;
@@ -779,7 +780,8 @@ struct bobe_gp {
 
   // ---- gp_criteria.hip: the importance-weighted scoring pass (criteria_kernels.hpp)
   // the per-z table of w for the base_z in bz (first: mu, a, omega as well; else only the terms that follow base_z)
-  void wip_zterms(bobe::SweepW& w, int64_t M, int64_t Mp, double y_std, const double* bz, bool first);
+  // lam: the lambda row and log E[Z] too, as for a w with zz set
+  void wip_zterms(bobe::SweepW& w, int64_t M, int64_t Mp, double y_std, const double* bz, bool first, bool lam = false);
   // k_wip_score_w on ns candidates (wip_score's arguments); writes w.out[k] + off
   void wip_score_w(const bobe::SweepW& w, const double* crossT, int64_t ldx, const double* cst, const double* scs,
                    const double* bz, int64_t ns, int64_t M, int64_t Mp, double y_std, int64_t off);
@@ -798,6 +800,13 @@ struct bobe_gp {
   static constexpr int64_t WGW_MAX_N = 4096;      // (k_wg_cross_w keeps v in N doubles of LDS)
   int wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                  double* const scores[4], double* const grads[4]);
+  // value and input gradient of the evidence-variance score through the same chain, the same limit on N
+  int wip_grad_zvar(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw, double* zvar,
+                    double* dzvar, double* log_ez);
+  // what the two share: the kept per-z table, and the chain itself (entry: the name in front of its refusals)
+  void wip_grad_table(int64_t M, int64_t Mp, double y_std, const double* logw, bool lam);
+  int wip_grad_chain(const char* entry, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                     const double* logw, double* const scores[4], double* const grads[4], int mask, bool zv, double* log_ez);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

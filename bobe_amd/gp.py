@@ -1050,6 +1050,22 @@ class GP:
                 out["d" + k] = grads[i]
         return out
 
+    def wip_grad_zvar(self, candidates, mc_points, *, log_weights=None):
+        """Value and input gradient of the evidence-variance score (``bobe_gp_wip_grad_zvar``): ``{"zvar": (C,), "dzvar":
+        (C, d), "log_ez": float}``.  ``candidates`` / ``mc_points``: NumPy arrays or torch CUDA tensors.  ``log_weights`` and
+        the units are those of ``wip_sweep(criteria=('zvar',))``: physical, y_mean added to ``log_ez``, no shift in the score.
+        A candidate whose score is +inf (it teaches nothing) has a zero gradient.  Matrix-vector work in groups of 16
+        candidates, for at most 4096 training points; the pair stage grows with M^2 per candidate."""
+        cand = candidates if hasattr(candidates, "data_ptr") else _lib.as_f64(np.atleast_2d(candidates))
+        z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
+        c, m = int(cand.shape[0]), int(z.shape[0])
+        lw = self._log_weights(log_weights, m)
+        zv, dz = np.empty(c), np.empty((c, self.ndim))
+        lez = C.c_double(0.0)
+        _lib.check(self._lib.bobe_gp_wip_grad_zvar(self._h, _lib.ptr(cand), c, _lib.ptr(z), m, float(self.y_std), _lib.ptr(lw),
+                                                   _lib.ptr(zv), _lib.ptr(dz), C.byref(lez)), "bobe_gp_wip_grad_zvar")
+        return {"zvar": zv, "dzvar": dz, "log_ez": lez.value + float(self.y_mean)}
+
     def predict_grad(self, x, mean_only=False):
         """Standardised (mean, var, dmean/dx, dvar/dx) of ``predict_single`` (gp.py:476-489) for C points: what the
         reference gets by JAX autodiff through the GP (acquisition.py:246-253, samplers.py:268-276).

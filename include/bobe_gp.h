@@ -309,6 +309,32 @@ int bobe_gp_wip_grad(bobe_gp_t* gp, const double* cand, int64_t C, const double*
 int bobe_gp_wip_grad_w(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                        const double* logw, double* const scores[4], double* const grads[4]);
 
+/* bobe_gp_wip_grad_w for bobe_gp_wip_sweep_zvar's score (a build addition): zvar[c] = -log T(c) and its gradient with respect
+ * to the candidate's coordinates, dzvar (C x d).  With omega_z = exp(lambda_z), b_z, r_z(c) = y_std cross_z / sqrt(s_c) as
+ * there, h_c = max_z (lambda_z + r_z^2 / 2), p_z = lambda_z - h_c and the scaled pair sum T_s (zvar = -(2 h_c + log T_s)):
+ *   G_z = sum_z' r_z' exp(p_z + p_z' + r_z r_z')     (the diagonal included; every exponent <= 0, nothing is subtracted),
+ *   d zvar/dx_j = sum_z rho_z d r_z/dx_j,   rho_z = -2 G_z / T_s,
+ *   d r_z/dx_j = w1 d cross_z/dx_j + w2_z d s/dx_j,   w1 = y_std / sqrt(s),   w2_z = -r_z / (2 s);
+ * d cross_z/dx_j and d s/dx_j are bobe_gp_wip_grad_w's.  The pair sum is formed as the sweep forms it (a pair with
+ * |r_z r_z'| < 1 through expm1, any other as a difference of two exponentials), over all M^2 ordered pairs.
+ * Rules, "gradient of where": a z whose r_z sits at its cap +-sqrt(b_z), or whose cross_z is not finite, is a constant - it
+ * keeps its value in T and in G and has rho_z = 0; a candidate whose s_c is not > 0, or whose T <= 0, has zvar = +inf and a
+ * zero gradient (on a finite state).
+ * Summation order: z's row of the pair sum and G_z over z' in four interleaved quarters (z' = q, q + 4, ...), each ascending,
+ * combined (0 + 1) + (2 + 3); T_s, sum_z rho_z w2_z and the z-side sums as bobe_gp_wip_grad_w sums over z (z = t, t + 256, ...
+ * per thread, the 64 lanes of a wave, the four waves); the rest is bobe_gp_wip_grad_w's chain.  No atomics.
+ * cand, Z, logw (M, NULL: l_z = -mu_z), zvar (C, may be NULL), dzvar (C x d, may be NULL): host or device; log_ez (host, one
+ * value, may be NULL): bobe_gp_wip_sweep_zvar's.  Units as there: physical, no y_mean.  Matrix-vector work in groups of 16
+ * candidates - there is no tile path - for at most 4096 training points; the pair stage costs C M^2 transcendental terms.
+ * A candidate's bits depend on the state, Z, logw, y_std and the candidate alone: not on C, its neighbours, the pointer kinds,
+ * which outputs are NULL, or the handle's caches - it shares bobe_gp_wip_grad_w's (Z's quantities and the per-z table, kept
+ * while the same host Z, host logw and y_std arrive again; the table gains its lambda row here and keeps the bits of the
+ * rows bobe_gp_wip_grad_w reads).  NOT gated.  The handle's state is left as it was.
+ * BOBE_ERR_ARG: NULL cand / Z, C or M < 1, zvar and dzvar both NULL, more than 4096 training points; BOBE_ERR_STATE without a
+ * factorised state - no output is touched then; a NaN state behaves as in bobe_gp_wip_sweep_zvar (BOBE_OK). */
+int bobe_gp_wip_grad_zvar(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
+                          const double* logw, double* zvar, double* dzvar, double* log_ez);
+
 /* The JOINT posterior of the latent-plus-noise process at C query points Xq (C x d), 1 <= C <= 16384 - what scikit-learn's
  * GaussianProcessRegressor.predict(return_cov=True) (plus noise I) and sample_y return; the reference has no counterpart.
  * Standardised units.  Every work buffer (V: N x C, Sigma and its factor: C x C each) belongs to the call and is freed before
