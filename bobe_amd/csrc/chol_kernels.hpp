@@ -792,15 +792,14 @@ __global__ __launch_bounds__(256) void k_copy_diag(double* __restrict__ A, int64
 // colk0 / far_col (optional, 64x64 tiles only): block columns >= far_col read their first pending panel from colk0[column]
 // (deferred columns: the K range [colk0[c], k1) differs from column to column; colk0[c] >= k1 skips the column); columns
 // before far_col take the scalar k0 without touching memory.
-// GLDS (T = 64, BK = 16 only): the direct-to-LDS tile core instead of the register-staged one (tile_gemm) - same bits
-// (BOBE_GEMM64_GLDS, gp_handle.hpp).  Its occupancy bound of two workgroups per CU caps the registers at 256, so the
-// MFMAs accumulate in VGPRs: with room for 512 the compiler takes the AGPR form and copies all 32 accumulator registers
-// out and back in every K-step of this loop.
-template <int T, int BK, bool GLDS = false>
-__global__ __launch_bounds__(256, GLDS ? 2 : 1) void k_syrk_trail(double* __restrict__ A, int64_t lda, int k0, int k1, int first,
-                                                    int colmode, int n, int64_t bsA = 0, int per = 0,
-                                                    const int* __restrict__ colk0 = nullptr, int far_col = 0, int ncol = 0) {
-  static_assert(!GLDS || has_glds_core<T, BK>, "no direct-to-LDS core for this tile and K-step");
+// Tile core (tile_gemm): direct-to-LDS where the tile and K-step have one (<64, 16>), else register-staged (<32, SYRK32_BK>).
+// On the direct-to-LDS core an occupancy bound of two workgroups per CU caps the registers at 256, so the MFMAs accumulate
+// in VGPRs: with room for 512 the compiler takes the AGPR form and copies all 32 accumulator registers out and back in
+// every K-step of this loop.
+template <int T, int BK>
+__global__ __launch_bounds__(256, (has_glds_core<T, BK> ? 2 : 1)) void k_syrk_trail(
+    double* __restrict__ A, int64_t lda, int k0, int k1, int first, int colmode, int n, int64_t bsA = 0, int per = 0,
+    const int* __restrict__ colk0 = nullptr, int far_col = 0, int ncol = 0) {
   extern __shared__ double smem[];
   A += blockIdx.y * bsA;
   int a, b;
@@ -831,7 +830,7 @@ __global__ __launch_bounds__(256, GLDS ? 2 : 1) void k_syrk_trail(double* __rest
   const int64_t base = (int64_t)first * TILE;
   v4d acc[T / 32][T / 32];
   load_tile<T, T>(acc, A, lda, base + (int64_t)a * T, base + (int64_t)b * T);   // acc = C, then acc -= A B^T
-  tile_gemm<GLDS, KC, KC, T, true, false, BK>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T,
+  tile_gemm<true, KC, KC, T, true, false, BK>(acc, A, lda, base + (int64_t)a * T, A, lda, base + (int64_t)b * T,
                                               (int64_t)k0 * TILE, (int64_t)k1 * TILE, smem);
   store_tile<T, T>(acc, A, lda, base + (int64_t)a * T, base + (int64_t)b * T, 1.0, 0.0);
 }
@@ -861,8 +860,8 @@ __device__ __forceinline__ bool tri_find(const TriProb* __restrict__ probs, int 
   return false;
 }
 
-// GLDS: the tile core as in k_syrk_trail (k_trtri_R likewise); the host asks for it on 64 x 64 tiles only
-template <int T, bool GLDS = false>
+// Tile core (k_trtri_R likewise): direct-to-LDS on 64 x 64 tiles only; 128 and 32 are register-staged
+template <int T>
 __global__ __launch_bounds__(256, 2) void k_trtri_T(const double* __restrict__ L, int64_t ldl,
                                                     const double* __restrict__ Linv, int64_t ldi,
                                                     double* __restrict__ Tmp, int64_t ldt,
@@ -887,12 +886,12 @@ __global__ __launch_bounds__(256, 2) void k_trtri_T(const double* __restrict__ L
     const int64_t m0 = (int64_t)p.mid * TILE + (int64_t)ti * T, n0 = (int64_t)p.lo * TILE + (int64_t)tj * T;
     v4d acc[T / 32][T / 32];
     acc_zero(acc);
-    tile_gemm<GLDS, KC, RC, T>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
+    tile_gemm<T == 64, KC, RC, T>(acc, L, ldl, m0, Linv, ldi, n0, n0, (int64_t)p.mid * TILE, smem);
     store_tile<T, T>(acc, Tmp, ldt, m0, n0, 1.0, 0.0);
   }
 }
 
-template <int T, bool GLDS = false>
+template <int T>
 __global__ __launch_bounds__(256, 2) void k_trtri_R(double* __restrict__ Linv, int64_t ldi,
                                                     const double* __restrict__ Tmp, int64_t ldt,
                                                     const TriProb* __restrict__ probs, int nprob, int64_t bsL = 0,
@@ -916,7 +915,7 @@ __global__ __launch_bounds__(256, 2) void k_trtri_R(double* __restrict__ Linv, i
     const int64_t m0 = (int64_t)p.mid * TILE + (int64_t)ti * T, n0 = (int64_t)p.lo * TILE + (int64_t)tj * T;
     v4d acc[T / 32][T / 32];
     acc_zero(acc);
-    tile_gemm<GLDS, KC, RC, T>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
+    tile_gemm<T == 64, KC, RC, T>(acc, Linv, ldi, m0, Tmp, ldt, n0, (int64_t)p.mid * TILE, m0 + T, smem);
     store_tile<T, T>(acc, Linv, ldi, m0, n0, -1.0, 0.0);
   }
 }
@@ -950,8 +949,8 @@ __global__ __launch_bounds__(256, 2) void k_lauum_tiles32(const double* __restri
 // off-diagonal tiles weighted x2.  Optionally stores Kinv (lower tiles, slot stride bsK): tests, and the LOO objective.
 // from_kinv: the tiles of K^-1 are already in Kinv (k_lauum_tiles, slot stride bsK): only the gradient epilogue runs, each
 // thread on the elements it would own after the GEMM - the partial sums are the fused kernel's, bit for bit.
-// GLDS: the tile core as in k_syrk_trail; the host asks for it on 64 x 64 tiles only.
-template <int KERN, int DCAP, int T, bool GLDS = false>
+// Tile core: direct-to-LDS on 64 x 64 tiles, register-staged on 128 x 128.
+template <int KERN, int DCAP, int T>
 __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict__ Linv, int64_t ldi, int64_t np,
                                                        int64_t n, const double* __restrict__ alpha,
                                                        const double* __restrict__ XsT, int64_t ldx, Hyper h,
@@ -977,7 +976,7 @@ __global__ __launch_bounds__(256, 2) void k_lauum_grad(const double* __restrict_
     load_tile<T, T>(acc, Kinv + slot * bsK, ldk, (int64_t)ti * T, (int64_t)tj * T);
   } else {
     acc_zero(acc);
-    tile_gemm<GLDS, RC, RC, T>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np, smem);
+    tile_gemm<T == 64, RC, RC, T>(acc, Linv, ldi, (int64_t)ti * T, Linv, ldi, (int64_t)tj * T, (int64_t)ti * T, np, smem);
     if (Kinv) store_tile<T, T>(acc, Kinv + slot * bsK, ldk, (int64_t)ti * T, (int64_t)tj * T, 1.0, 0.0);
   }
   // stage coordinates and alpha in the (now free) GEMM LDS

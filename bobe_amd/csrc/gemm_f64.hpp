@@ -446,7 +446,8 @@ __device__ __forceinline__ void gemm_tile_glds(v4d (&acc)[T / 32][T / 32], const
 }
 
 // ---- the one way to ask for a tile product: acc += A(m0.., k) * B(n0.., k), k in [kbeg, kend) ---------------------------
-// GLDS: take the direct-to-LDS core where the tile has one (has_glds_core), else - and with GLDS = false always - the
+// GLDS, a constant written at every call site (a kernel's tile core is a property of the kernel; nothing picks it at run
+// time): take the direct-to-LDS core where the tile has one (has_glds_core), else - and with GLDS = false always - the
 // register-staged gemm_tile; the bits are the same either way.  smem: the launch's GEMM_SMEM_BYTES / GEMM64_SMEM_BYTES /
 // GEMM32_SMEM_BYTES serve both cores.
 template <bool GLDS, int LA, int LB, int T, bool NEGA = false, bool TRIL = false, int BK = TileCfg<T>::bk>

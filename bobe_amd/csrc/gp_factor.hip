@@ -26,25 +26,21 @@ void configure_factor_kernels() {
   allow_big_lds(k_trtri_T<128>, GEMM_SMEM_BYTES);
   allow_big_lds(k_trtri_R<128>, GEMM_SMEM_BYTES);
   allow_big_lds(k_syrk_trail<64, SYRK64_BK>, SYRK64_SMEM);
-  allow_big_lds(k_syrk_trail<64, SYRK64_BK, true>, SYRK64_SMEM);
   allow_big_lds(k_syrk_trail<32, SYRK32_BK>, SYRK32_SMEM);
   allow_big_lds(k_trtri_T<64>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_trtri_R<64>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_trtri_T<64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_trtri_R<64, true>, GEMM64_SMEM_BYTES);
   allow_big_lds(k_trtri_T<32>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_trtri_R<32>, GEMM32_SMEM_BYTES);
   allow_big_lds(k_lauum_tiles32, GEMM32_SMEM_BYTES);
   for_each_kern_dcap([](auto KE, auto DC) {
     allow_big_lds((k_lauum_grad<KE, DC, 64>), GEMM64_SMEM_BYTES);
-    allow_big_lds((k_lauum_grad<KE, DC, 64, true>), GEMM64_SMEM_BYTES);
     allow_big_lds((k_lauum_grad<KE, DC, 128>), GEMM_SMEM_BYTES);
   });
 }
 
 const Tuning& tuning() {
   static Tuning t = [] {
-    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, 1, false, false, true, true, true};
+    Tuning v{512, 600, 300, 1, BOBE_MAX_MLL_SLOTS, 2048, 1, 1, 1, false, false, true};
     auto geti = [](const char* name, int& dst) {
       const char* e = std::getenv(name);
       if (e) dst = std::atoi(e);
@@ -63,12 +59,6 @@ const Tuning& tuning() {
     int reuse = 1;
     geti("BOBE_FACTOR_REUSE", reuse);
     v.factor_reuse = reuse != 0;
-    int glds = 1;
-    geti("BOBE_GEMM_GLDS", glds);
-    v.gemm_glds = glds != 0;
-    int glds64 = 1;
-    geti("BOBE_GEMM64_GLDS", glds64);
-    v.gemm64_glds = glds64 != 0;
     return v;
   }();
   return t;
@@ -266,10 +256,8 @@ void bobe_gp::syrk(const FactorBufs& f, int k0, int k1, int first, int colmode, 
     return;
   }
   const TileGrid tg = colmode ? TileGrid{t64, 0} : tile_grid(t64);
-  // (the tile core BOBE_GEMM64_GLDS selects, through a function pointer: every argument is passed)
-  const auto k64 = tu.gemm64_glds ? k_syrk_trail<64, SYRK64_BK, true> : k_syrk_trail<64, SYRK64_BK, false>;
-  hipLaunchKernelGGL(k64, dim3(tg.grid, B), dim3(256), SYRK64_SMEM, stream, f.a, Np, k0, k1, first, colmode, n64, f.mat,
-                     tg.per, colk0, far_col, nc64);
+  hipLaunchKernelGGL((k_syrk_trail<64, SYRK64_BK>), dim3(tg.grid, B), dim3(256), SYRK64_SMEM, stream, f.a, Np, k0, k1, first,
+                     colmode, n64, f.mat, tg.per, colk0, far_col, nc64);
 }
 
 int bobe_gp::panel_strips(int B, int rr) const {
@@ -534,14 +522,12 @@ void bobe_gp::trtri_level(const FactorBufs& f, const Depth& part, int level_bloc
                          (const double*)f.tmp, Np, pr, part.count, f.mat, f.mat, tg.per);
   } else if (level_blocks < tu.trtri64_below) {
     const TileGrid tg = tile_grid(2 * part.nblocks);             // (tile pairs of complementary K: equal work)
-    const auto kT = tu.gemm64_glds ? k_trtri_T<64, true> : k_trtri_T<64, false>;
-    const auto kR = tu.gemm64_glds ? k_trtri_R<64, true> : k_trtri_R<64, false>;
     if (do_t)
-      hipLaunchKernelGGL(kT, dim3(tg.grid, f.B), dim3(256), GEMM64_SMEM_BYTES, st, f.a, Np, (const double*)f.linv, Np,
-                         f.tmp, Np, pr, part.count, f.mat, f.mat, f.mat, tg.per);
+      hipLaunchKernelGGL(k_trtri_T<64>, dim3(tg.grid, f.B), dim3(256), GEMM64_SMEM_BYTES, st, f.a, Np,
+                         (const double*)f.linv, Np, f.tmp, Np, pr, part.count, f.mat, f.mat, f.mat, tg.per);
     if (do_r)
-      hipLaunchKernelGGL(kR, dim3(tg.grid, f.B), dim3(256), GEMM64_SMEM_BYTES, st, f.linv, Np, (const double*)f.tmp, Np,
-                         pr, part.count, f.mat, f.mat, tg.per);
+      hipLaunchKernelGGL(k_trtri_R<64>, dim3(tg.grid, f.B), dim3(256), GEMM64_SMEM_BYTES, st, f.linv, Np,
+                         (const double*)f.tmp, Np, pr, part.count, f.mat, f.mat, tg.per);
   } else {
     if (do_t)
       hipLaunchKernelGGL(k_trtri_T<128>, dim3(part.nblocks, f.B), dim3(256), GEMM_SMEM_BYTES, st, f.a, Np,
@@ -596,8 +582,8 @@ int bobe_gp::lauum(const Hyper& h, const FactorBufs& f, const Hyper* hdev, bool 
     hipLaunchKernelGGL(k_lauum_tiles32, dim3(4 * ntiles * B), dim3(256), GEMM32_SMEM_BYTES, stream, (const double*)f.linv, Np,
                        Np, f.tmp, Np, f.mat, f.mat, B);
   }
-  with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT, auto GL) {
-    hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT, GL>), dim3(ntiles * B), dim3(256),
+  with_lauum_variant(h.kern, h.d, t, [&](auto KE, auto DC, auto TT) {
+    hipLaunchKernelGGL((k_lauum_grad<KE, DC, TT>), dim3(ntiles * B), dim3(256),
                        (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)f.linv, Np, Np, N,
                        (const double*)f.alpha, (const double*)f.xst, Np, h, f.gpart, kio, Np, hdev, f.mat, f.vec, f.xs, f.gps,
                        B, split ? 1 : 0, kio ? f.mat : (int64_t)0);

@@ -174,13 +174,9 @@ void allow_big_lds(K kernel, int bytes) {
 //                       (inv_side_pays), 2 wherever there are two block columns or more
 //   BOBE_TRACE          print launch plans and batch timings to stderr
 //   BOBE_FACTOR_REUSE   0: bobe_gp_factor always factorises, never adopts an evaluation's factor (1; for A/B runs)
-//   BOBE_GEMM_GLDS      0: the sweep's 128-tile GEMMs (k_trimul, k_cross_vv<128>) take the register-staged tile core
-//                       instead of the direct-to-LDS one (tile_gemm's GLDS, gemm_f64.hpp; 1; for A/B runs)
-//   BOBE_GEMM64_GLDS    0: the 64-tile GEMMs (k_syrk_trail<64, 16>, k_trtri_T/R<64>, k_lauum_grad<., ., 64>, k_cross_vv<64>,
-//                       k_trimul_v64, k_trimul_t64, k_loo_grad<., ., 64>) likewise (1; A/B)
 struct Tuning {
   int syrk32_below, trtri64_below, pair_min, lockstep_min_n, mll_slots, graph_max_n, xcd_shares, fill, inv_side;
-  bool mll_slots_set, trace, factor_reuse, gemm_glds, gemm64_glds;
+  bool mll_slots_set, trace, factor_reuse;
 };
 const Tuning& tuning();
 
@@ -220,14 +216,12 @@ inline LauumTiling lauum_tiling(int nb) {
   const int nt = small ? 2 * nb : nb;
   return {small, nt, nt * (nt + 1) / 2};
 }
-// with_kern_dcap extended by the tile size TT and its core GL: f(KE, DC, TT, GL).  BOBE_GEMM64_GLDS selects the core of the
-// 64 x 64 tiles; the 128 x 128 ones are register-staged.
+// with_kern_dcap extended by the tile size TT: f(KE, DC, TT)
 template <typename F>
 inline void with_lauum_variant(int kern, int d, const LauumTiling& t, F&& f) {
   with_kern_dcap(kern, d, [&](auto KE, auto DC) {
-    if (!t.small) f(KE, DC, std::integral_constant<int, 128>{}, std::false_type{});
-    else if (tuning().gemm64_glds) f(KE, DC, std::integral_constant<int, 64>{}, std::true_type{});
-    else f(KE, DC, std::integral_constant<int, 64>{}, std::false_type{});
+    if (t.small) f(KE, DC, std::integral_constant<int, 64>{});
+    else f(KE, DC, std::integral_constant<int, 128>{});
   });
 }
 

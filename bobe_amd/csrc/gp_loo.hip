@@ -16,7 +16,6 @@ void configure_loo_kernels() {
   if (!first_use_on_device(done)) return;
   for_each_kern_dcap([](auto KE, auto DC) {
     allow_big_lds((k_loo_grad<KE, DC, 64>), GEMM64_SMEM_BYTES);
-    allow_big_lds((k_loo_grad<KE, DC, 64, true>), GEMM64_SMEM_BYTES);
     allow_big_lds((k_loo_grad<KE, DC, 128>), GEMM_SMEM_BYTES);
   });
 }
@@ -119,8 +118,8 @@ void bobe_gp::loo_enqueue(EvalWs& ws, int B, const Hyper* hs, bool want_grad, co
                        nb, 0, Np, lw + 6 * Np, f.prt, f.lvs);
     const LauumTiling t = lauum_tiling(nb);       // (the dense B^T B on the tiles and the tile core K^-1 was formed on)
     prof_begin(BOBE_PROF_LAUUM);
-    with_lauum_variant(hs[0].kern, hs[0].d, t, [&](auto KE, auto DC, auto TT, auto GL) {
-      hipLaunchKernelGGL((k_loo_grad<KE, DC, TT, GL>), dim3(t.ntiles * B), dim3(256),
+    with_lauum_variant(hs[0].kern, hs[0].d, t, [&](auto KE, auto DC, auto TT) {
+      hipLaunchKernelGGL((k_loo_grad<KE, DC, TT>), dim3(t.ntiles * B), dim3(256),
                          (TT == 128 ? GEMM_SMEM_BYTES : GEMM64_SMEM_BYTES), stream, (const double*)f.a, Np, Np, N,
                          (const double*)f.alpha, (const double*)(lw + 6 * Np), (const double*)f.xst, Np, hs[0], f.gpart,
                          hdev, f.mat, f.vec, f.lvs, f.xs, f.gps, B);

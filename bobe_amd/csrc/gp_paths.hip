@@ -35,16 +35,12 @@ void configure_paths_kernels() {
   static bool done[64] = {false};
   if (!first_use_on_device(done)) return;
   allow_big_lds(k_paths_rhs, GEMM_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<128, true, false>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<128, false, false>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<128, true, true>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<128, false, true>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<64, true, false>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<64, false, false>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<64, true, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<64, false, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<32, false, false>, GEMM32_SMEM_BYTES);
-  allow_big_lds(k_paths_tiles<32, false, true>, GEMM32_SMEM_BYTES);
+  allow_big_lds(k_paths_tiles<128, false>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_paths_tiles<128, true>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_paths_tiles<64, false>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_paths_tiles<64, true>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_paths_tiles<32, false>, GEMM32_SMEM_BYTES);
+  allow_big_lds(k_paths_tiles<32, true>, GEMM32_SMEM_BYTES);
   // (the chain kernel keeps training rows in up to 148 KB of LDS, like k_hmc_run)
   for_each_kern_dcap([](auto KE, auto DC) { allow_big_lds((k_paths_hmc_run<KE, DC>), CHAIN_LDS_BYTES); });
 }
@@ -84,21 +80,18 @@ void features(bobe_paths& p, const double* xst, int64_t ldx, int64_t n, int64_t 
   LAUNCH_CHECK();
 }
 
-// the evaluation product of one chunk (k_paths_tiles) on the tile the set was given and the core the tuning switches select
+// the evaluation product of one chunk (k_paths_tiles) on the tile the set was given
 template <bool ARGMAX, typename... Args>
 void launch_tiles(bobe_paths& p, int64_t ncp, Args... args) {
   const int T = p.T;
   const dim3 grid((unsigned)(ncp / T), (unsigned)(round_up(p.S, T) / T));
   hipStream_t st = p.g->stream;
-  if (T == 128) {
-    auto k = tuning().gemm_glds ? k_paths_tiles<128, true, ARGMAX> : k_paths_tiles<128, false, ARGMAX>;
-    hipLaunchKernelGGL(k, grid, dim3(256), GEMM_SMEM_BYTES, st, args...);
-  } else if (T == 64) {
-    auto k = tuning().gemm64_glds ? k_paths_tiles<64, true, ARGMAX> : k_paths_tiles<64, false, ARGMAX>;
-    hipLaunchKernelGGL(k, grid, dim3(256), GEMM64_SMEM_BYTES, st, args...);
-  } else {
-    hipLaunchKernelGGL((k_paths_tiles<32, false, ARGMAX>), grid, dim3(256), GEMM32_SMEM_BYTES, st, args...);
-  }
+  if (T == 128)
+    hipLaunchKernelGGL((k_paths_tiles<128, ARGMAX>), grid, dim3(256), GEMM_SMEM_BYTES, st, args...);
+  else if (T == 64)
+    hipLaunchKernelGGL((k_paths_tiles<64, ARGMAX>), grid, dim3(256), GEMM64_SMEM_BYTES, st, args...);
+  else
+    hipLaunchKernelGGL((k_paths_tiles<32, ARGMAX>), grid, dim3(256), GEMM32_SMEM_BYTES, st, args...);
   LAUNCH_CHECK();
 }
 

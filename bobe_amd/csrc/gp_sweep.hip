@@ -10,27 +10,14 @@ namespace bobe {
 void configure_sweep_kernels() {
   static bool done[64] = {false};
   if (!first_use_on_device(done)) return;
-  allow_big_lds(k_trimul<true>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_trimul<false>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_trimul, GEMM_SMEM_BYTES);
   allow_big_lds(k_trimul_t, GEMM_SMEM_BYTES);
-  allow_big_lds(k_trimul_v64<true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_trimul_v64<false>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_trimul_t64<true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_trimul_t64<false>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trimul_v64, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_trimul_t64, GEMM64_SMEM_BYTES);
   allow_big_lds(k_blk_step, GEMM_SMEM_BYTES);
-  allow_big_lds(k_cross_vv<128, true>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_cross_vv<128, false>, GEMM_SMEM_BYTES);
-  allow_big_lds(k_cross_vv<64, true>, GEMM64_SMEM_BYTES);
-  allow_big_lds(k_cross_vv<64, false>, GEMM64_SMEM_BYTES);
+  allow_big_lds(k_cross_vv<128>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_cross_vv<64>, GEMM64_SMEM_BYTES);
 }
-
-// the sweep's 128-tile GEMM kernels on the tile core BOBE_GEMM_GLDS selects (a function pointer: pass every argument)
-static auto trimul_kernel() { return tuning().gemm_glds ? k_trimul<true> : k_trimul<false>; }
-static auto cross_vv128_kernel() { return tuning().gemm_glds ? k_cross_vv<128, true> : k_cross_vv<128, false>; }
-// and the 64-tile ones on the core BOBE_GEMM64_GLDS selects
-static auto cross_vv64_kernel() { return tuning().gemm64_glds ? k_cross_vv<64, true> : k_cross_vv<64, false>; }
-static auto trimul_v64_kernel() { return tuning().gemm64_glds ? k_trimul_v64<true> : k_trimul_v64<false>; }
-static auto trimul_t64_kernel() { return tuning().gemm64_glds ? k_trimul_t64<true> : k_trimul_t64<false>; }
 }  // namespace bobe
 
 void bobe_gp::decide_refinement(double min_diag) {
@@ -40,9 +27,9 @@ void bobe_gp::decide_refinement(double min_diag) {
 
 void bobe_gp::solve_v(double* B, int64_t ldb, int64_t ncp, double* V, int64_t ldv, double* qp, int64_t ldq) {
   if (!refine_v) {
-    hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)(ncp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
+    hipLaunchKernelGGL(k_trimul, dim3((unsigned)(ncp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nb, (const double*)B, ldb, V, ldv, qp, ldq, (const double*)nullptr,
-                       (int64_t)0, 0, (double*)nullptr, (int64_t)0, (const double*)nullptr, (int64_t)0, 0, 1 << 30);
+                       (int64_t)0, 0, (double*)nullptr, (int64_t)0);
     return;
   }
   if (!V) throw Err(BOBE_ERR_STATE, "solve_v: the blocked substitution needs a buffer for V");
@@ -83,7 +70,7 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
   const bool few = (Mp / TILE) * nb < 2 * std::max(num_cus, 1);
   auto make_w = [&]() {
     if (few)
-      hipLaunchKernelGGL(trimul_t64_kernel(), dim3((unsigned)(Mp / 64), (unsigned)(2 * nb)), dim3(256), GEMM64_SMEM_BYTES, stream,
+      hipLaunchKernelGGL(k_trimul_t64, dim3((unsigned)(Mp / 64), (unsigned)(2 * nb)), dim3(256), GEMM64_SMEM_BYTES, stream,
                          (const double*)Linv.d(), Np, 2 * nb, (const double*)VZ.d(), Mp, WZ.d(), Mp);
     else
       hipLaunchKernelGGL(k_trimul_t, dim3((unsigned)(Mp / TILE), (unsigned)nb), dim3(256), GEMM_SMEM_BYTES, stream,
@@ -111,7 +98,7 @@ void bobe_gp::prepare_z(const double* Z, int64_t M, int64_t Mp, bool need_w) {
   int nt = nb;                                     // row tiles whose column sums of squares qpart holds
   if (few && !refine_v) {
     nt = 2 * nb;
-    hipLaunchKernelGGL(trimul_v64_kernel(), dim3((unsigned)(Mp / 64), (unsigned)nt), dim3(256), GEMM64_SMEM_BYTES, stream,
+    hipLaunchKernelGGL(k_trimul_v64, dim3((unsigned)(Mp / 64), (unsigned)nt), dim3(256), GEMM64_SMEM_BYTES, stream,
                        (const double*)Linv.d(), Np, nt, (const double*)kXZ.d(), Mp, VZ.d(), Mp, qpart.d(), Mp);
   } else {
     solve_v(kXZ.d(), Mp, Mp, VZ.d(), Mp, qpart.d(), Mp);
@@ -204,10 +191,10 @@ void bobe_gp::sweep(const SweepReq& r) {
     // cross-covariances from the two solved factors (sweep_kernels.hpp, k_cross_vv): crossT[z][c] = VZ[:, z] . V[:, c]
     prof_begin(BOBE_PROF_CROSSVV);
     if ((int64_t)nzt * (ncp_ / TILE) >= 2 * std::max(num_cus, 1))
-      hipLaunchKernelGGL(cross_vv128_kernel(), dim3((unsigned)(ncp_ / TILE), (unsigned)nzt), dim3(256), GEMM_SMEM_BYTES, stream,
+      hipLaunchKernelGGL(k_cross_vv<128>, dim3((unsigned)(ncp_ / TILE), (unsigned)nzt), dim3(256), GEMM_SMEM_BYTES, stream,
                          (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, ldC);
     else
-      hipLaunchKernelGGL(cross_vv64_kernel(), dim3((unsigned)(ncp_ / 64), (unsigned)(Mp / 64)), dim3(256), GEMM64_SMEM_BYTES,
+      hipLaunchKernelGGL(k_cross_vv<64>, dim3((unsigned)(ncp_ / 64), (unsigned)(Mp / 64)), dim3(256), GEMM64_SMEM_BYTES,
                          stream, (const double*)VZ.d(), Mp, Vc, ldvc, Np, cross_out, ldC);
     prof_end(BOBE_PROF_CROSSVV);
   };
@@ -263,7 +250,7 @@ void bobe_gp::sweep(const SweepReq& r) {
         if (fuse_cross) {
           const int ncv = (int)(ncp / TILE), ncx = pend.valid ? (int)(pend.ncp / TILE) : 0;
           const int nz = pend.valid ? nzt : 0;
-          hipLaunchKernelGGL(trimul_kernel(), dim3((unsigned)std::max(ncv, ncx), (unsigned)(nb + nz)), dim3(256), GEMM_SMEM_BYTES,
+          hipLaunchKernelGGL(k_trimul, dim3((unsigned)std::max(ncv, ncx), (unsigned)(nb + nz)), dim3(256), GEMM_SMEM_BYTES,
                              stream, (const double*)Linv.d(), Np, nb, (const double*)kXC.d(), CH, vcur, ldV, qpart.d(), CH,
                              (const double*)VZ.d(), Mp, nz, pend.cross, ldC, pend.V, ldV, ncx, ncv);
           pend = {true, vcur, ncp, xT + c0};

@@ -10,7 +10,9 @@ using namespace bobe;
 namespace {
 
 // One row per instantiation the library ships (plus the two remaining layouts of k_debug_gemm); a new tile_gemm
-// instantiation gets a row here and in the test's table.  Columns:
+// instantiation gets a row here and in the test's table.  Three register-staged rows - (64, 16, RC, RC), (64, 16, KC, RC)
+// and (64, SYRK64_BK, KC, KC, NEGA) - belong to no shipped launch any more (those kernels run the direct-to-LDS core): they
+// stay as the reference their direct-to-LDS twins are compared with, bit for bit.  Columns:
 //   T, BK, GLDS, LA, LB, NEGA, TRIL, groups (256-thread tile groups per workgroup), single_buffer, dynamic LDS of the
 //   shipped launch in bytes (for groups = 2: of both groups together; group g takes the g-th half)
 // single_buffer: the launch has LDS for ONE pair of operand images, so the K range is one K-step.

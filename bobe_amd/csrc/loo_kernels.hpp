@@ -138,11 +138,11 @@ static __global__ __launch_bounds__(256) void k_loo_make_b(const double* __restr
 // operand of k_lauum_grad);  W = 2 M = -2 G - (w alpha^T + alpha w^T) on the tile.
 // partial[tile * (DCAP + 1) + j] = sum_ab W_ab dK_ab / dlog ls_j (j < d), [DCAP] = sum_ab W_ab Kt_ab (Kt: without noise),
 // off-diagonal tiles weighted x2: the layout and the epilogue arithmetic of k_lauum_grad, reduced by k_mll_grad_reduce
-// (x 1/2).  One tile per workgroup; GLDS: the tile core, as in k_lauum_grad.
+// (x 1/2).  One tile per workgroup; the tile core as in k_lauum_grad (direct-to-LDS for T = 64).
 // Batch: one grid dimension, tile-major - workgroup id = tile * nbatch + member, the order k_lauum_grad takes (here every
 // tile has the same K length, so the order is a convention, not a schedule).  hp: the members' hyper-parameters on the
 // device (NULL: h by value); B strides by bsB, alpha by bsV, w by bsW, XsT by bsX, partial by bsP.
-template <int KERN, int DCAP, int T, bool GLDS = false>
+template <int KERN, int DCAP, int T>
 __global__ __launch_bounds__(256, 2) void k_loo_grad(const double* __restrict__ B, int64_t ldb, int64_t np, int64_t n,
                                                      const double* __restrict__ alpha, const double* __restrict__ wv,
                                                      const double* __restrict__ XsT, int64_t ldx, Hyper h,
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void k_loo_grad(const double* __restrict__ 
   tri_decode(tile, ti, tj);
   v4d acc[T / 32][T / 32];
   acc_zero(acc);
-  tile_gemm<GLDS, RC, RC, T>(acc, B, ldb, (int64_t)ti * T, B, ldb, (int64_t)tj * T, (int64_t)0, np, smem);
+  tile_gemm<T == 64, RC, RC, T>(acc, B, ldb, (int64_t)ti * T, B, ldb, (int64_t)tj * T, (int64_t)0, np, smem);
   __syncthreads();                    // (every wave is through with the GEMM's LDS images)
   double* xa = smem;                  // [d][T]
   double* xb = smem + MAX_D * T;      // [d][T]

@@ -148,8 +148,8 @@ __global__ __launch_bounds__(256, 2) void k_paths_rhs(const double* __restrict__
 // and its column land in pmax / pidx[s * npt + tile] (ties: the lower column; NaN never wins; no valid entry: -inf, column 0),
 // k_paths_argmax_merge folds them.  The reduction: every lane keeps the best of its four fragments per row, the 32 lane
 // candidates of a row (16 lanes x the two column halves) meet in LDS - smem is free once the product is done - and one thread
-// per row scans them.
-template <int T, bool GLDS, bool ARGMAX>
+// per row scans them.  Tile core: direct-to-LDS where the tile has one (T = 128 and 64; T = 32: register-staged).
+template <int T, bool ARGMAX>
 __global__ __launch_bounds__(256, 2) void k_paths_tiles(const double* __restrict__ VW, int64_t ldv,
                                                         const double* __restrict__ OP, int64_t ldo, int64_t kend,
                                                         const double* __restrict__ mean, int64_t S, int64_t nc,
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void k_paths_tiles(const double* __restrict
   const int tq = blockIdx.x, ts = blockIdx.y;
   v4d acc[FR][FR];
   acc_zero(acc);
-  tile_gemm<GLDS, RC, RC, T>(acc, VW, ldv, (int64_t)ts * T, OP, ldo, (int64_t)tq * T, 0, kend, smem);
+  tile_gemm<true, RC, RC, T>(acc, VW, ldv, (int64_t)ts * T, OP, ldo, (int64_t)tq * T, 0, kend, smem);
   if (!ARGMAX) {
 #pragma unroll
     for (int i = 0; i < FR; ++i)

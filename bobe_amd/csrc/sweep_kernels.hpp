@@ -37,9 +37,7 @@ __device__ __forceinline__ void tile_colsq(const v4d (&acc)[T / 32][T / 32], dou
 // solves the next chunk, where their full-K tiles fill the tails of the triangular ones, instead of a launch of their own
 // (2.62 ms per chunk of 8192 candidates at N = 4096, M = 512 against 2.17 + 0.59).  ncv / ncx: column tiles of the two
 // parts (the grid spans the larger; a chunk's last tiles may be missing in one of them).
-// GLDS: the tile core (gemm_f64.hpp, tile_gemm): direct-to-LDS (true, the default) or register-staged - same bits
-// (BOBE_GEMM_GLDS, gp_handle.hpp).
-template <bool GLDS>
+// Tile core (gemm_f64.hpp, tile_gemm): direct-to-LDS.
 __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Linv, int64_t ldi, int nb,
                                                    const double* __restrict__ B, int64_t ldb, double* __restrict__ V,
                                                    int64_t ldv, double* __restrict__ qpart, int64_t ldq,
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Li
   if ((int)blockIdx.y < nzt) {
     if (tc >= ncx) return;
     const int tz = blockIdx.y;
-    tile_gemm<GLDS, RC, RC, TILE>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
+    tile_gemm<true, RC, RC, TILE>(acc, VZ, ldw, (int64_t)tz * TILE, Bx, ldbx, (int64_t)tc * TILE, 0, (int64_t)nb * TILE, smem);
     store_tile(acc, crossT, ldx, (int64_t)tz * TILE, (int64_t)tc * TILE, 1.0, 0.0);
     return;
   }
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(256, 2) void k_trimul(const double* __restrict__ Li
   const int ti = nb - 1 - ((int)blockIdx.y - nzt);
   // (the K range of a row tile ends with its diagonal block of the lower-triangular Linv: the zeros above the diagonal are
   // skipped, 1.2 % of the launch)
-  tile_gemm<GLDS, KC, RC, TILE, false, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE, 0,
+  tile_gemm<true, KC, RC, TILE, false, true>(acc, Linv, ldi, (int64_t)ti * TILE, B, ldb, (int64_t)tc * TILE, 0,
                                              (int64_t)(ti + 1) * TILE, smem);
   if (V) store_tile(acc, V, ldv, (int64_t)ti * TILE, (int64_t)tc * TILE, 1.0, 0.0);
   if (qpart) tile_colsq<TILE>(acc, smem, qpart + (int64_t)ti * ldq + (int64_t)tc * TILE);
@@ -164,8 +162,8 @@ __global__ __launch_bounds__(256) void k_colsq_tile_parts(const double* __restri
 // scores came out 1e-2 ... 1 (relative) off an extended-precision evaluation where the triangular-solve form is 1e-4 ...
 // 1e-1 off (profiles/r05_conditioning.txt, tests/test_gpu_conditioning.py).  Same 2 N M flops per candidate.
 // T = 128: grid (ncols / 128, Mp / 128); T = 64: grid (ncols / 64, Mp / 64) - few integration points fill the chip only
-// with the small tile.  GLDS: the tile core as in k_trimul (T = 128: BOBE_GEMM_GLDS, T = 64: BOBE_GEMM64_GLDS).
-template <int T, bool GLDS = false>
+// with the small tile.  Tile core: direct-to-LDS, as in k_trimul (both tile sizes have one).
+template <int T>
 __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ VZ, int64_t ldz,
                                                      const double* __restrict__ V, int64_t ldv, int64_t kend,
                                                      double* __restrict__ crossT, int64_t ldx) {
@@ -173,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void k_cross_vv(const double* __restrict__ 
   const int tc = blockIdx.x, tz = blockIdx.y;
   v4d acc[T / 32][T / 32];
   acc_zero(acc);
-  tile_gemm<GLDS, RC, RC, T>(acc, VZ, ldz, (int64_t)tz * T, V, ldv, (int64_t)tc * T, 0, kend, smem);
+  tile_gemm<true, RC, RC, T>(acc, VZ, ldz, (int64_t)tz * T, V, ldv, (int64_t)tc * T, 0, kend, smem);
   store_tile<T, T>(acc, crossT, ldx, (int64_t)tz * T, (int64_t)tc * T, 1.0, 0.0);
 }
 
@@ -194,8 +192,7 @@ __global__ __launch_bounds__(256, 2) void k_trimul_t(const double* __restrict__ 
 // ---- the same two products on 64 x 64 tiles, for right-hand sides with FEW columns (the M = 512 integration points of a
 // sweep: 4 x nb tiles of 128 x 128 leave half the chip idle for two launches of ~0.57 ms each at N = 4096; 8 x 2nb tiles
 // of 64 x 64 fill it).  V = Linv B with the column sums of squares per 64-row tile (qpart[2 nb][.]), W = Linv^T V.
-// GLDS: the tile core, direct-to-LDS or register-staged (BOBE_GEMM64_GLDS).
-template <bool GLDS>
+// Tile core of both: direct-to-LDS.
 __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict__ Linv, int64_t ldi, int nt,
                                                        const double* __restrict__ B, int64_t ldb, double* __restrict__ V,
                                                        int64_t ldv, double* __restrict__ qpart, int64_t ldq) {
@@ -204,12 +201,11 @@ __global__ __launch_bounds__(256, 2) void k_trimul_v64(const double* __restrict_
   const int ti = nt - 1 - (int)blockIdx.y;                      // long K first
   v4d acc[2][2];
   acc_zero(acc);
-  tile_gemm<GLDS, KC, RC, 64>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64, smem);
+  tile_gemm<true, KC, RC, 64>(acc, Linv, ldi, (int64_t)ti * 64, B, ldb, (int64_t)tc * 64, 0, (int64_t)(ti + 1) * 64, smem);
   store_tile<64, 64>(acc, V, ldv, (int64_t)ti * 64, (int64_t)tc * 64, 1.0, 0.0);
   tile_colsq<64>(acc, smem, qpart + (int64_t)ti * ldq + (int64_t)tc * 64);
 }
 
-template <bool GLDS>
 __global__ __launch_bounds__(256, 2) void k_trimul_t64(const double* __restrict__ Linv, int64_t ldi, int nt,
                                                        const double* __restrict__ V, int64_t ldv, double* __restrict__ W,
                                                        int64_t ldw) {
@@ -218,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void k_trimul_t64(const double* __restrict_
   const int tc = blockIdx.x;
   v4d acc[2][2];
   acc_zero(acc);
-  tile_gemm<GLDS, RC, RC, 64>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64, (int64_t)nt * 64,
+  tile_gemm<true, RC, RC, 64>(acc, Linv, ldi, (int64_t)ti * 64, V, ldv, (int64_t)tc * 64, (int64_t)ti * 64, (int64_t)nt * 64,
                               smem);
   store_tile<64, 64>(acc, W, ldw, (int64_t)ti * 64, (int64_t)tc * 64, 1.0, 0.0);
 }

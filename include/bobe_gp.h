@@ -629,7 +629,8 @@ int64_t bobe_gp_npoints(bobe_gp_t* gp);
 int bobe_debug_gemm(int device, int layoutA, int layoutB, int64_t M, int64_t N, int64_t K, const double* A,
                     int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc);
 /* One instantiation ("variant") of the tile core tile_gemm<GLDS, LA, LB, T, NEGA, TRIL, BK> on the caller's operands, with
- * the dynamic LDS of the launch that ships it.  bobe_debug_tile_gemm_count: the number of variants compiled in.
+ * the dynamic LDS of the launch that ships it (a register-staged variant on 64 x 64 tiles with BK = 16, which no launch
+ * ships: of the launch that ships its direct-to-LDS twin).  bobe_debug_tile_gemm_count: the number of variants compiled in.
  * bobe_debug_tile_gemm_info: info9 = {T, BK, glds, layoutA, layoutB, nega, tril, groups, single_buffer} (layouts as in
  * bobe_debug_gemm; groups = 2: two 256-thread tile groups per workgroup, side by side in n; single_buffer: LDS for one
  * K-step only).

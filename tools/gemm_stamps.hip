@@ -2,11 +2,12 @@
 // a K-step's cycles go.  BOBE_GEMM_STAMPS switches the stamps on in gemm_f64.hpp; the product never defines it.
 //
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -o tools/bin/gemm_stamps tools/gemm_stamps.hip
-//   tools/bin/gemm_stamps [glds 0|1] [seconds] > profiles/<name>.json
+//   tools/bin/gemm_stamps [seconds] > profiles/<name>.json
 //
 // k_trimul at the headline shape (N = 4096: nb = 32 row tiles, a chunk of 8192 candidates, no cross tiles) on random data,
 // launched back to back for `seconds` (default 3), then one more launch whose stamps are read.  Per wave: clock =
-// d(s_memtime) / d(s_memrealtime) x 100 MHz around the loop; segment cycles per K-step (see gemm_f64.hpp).
+// d(s_memtime) / d(s_memrealtime) x 100 MHz around the loop; segment cycles per K-step (see gemm_f64.hpp).  The kernel
+// runs the direct-to-LDS tile core, the one it ships with; the register-staged core can no longer be stamped through it.
 #define BOBE_GEMM_STAMPS 1
 #include "../bobe_amd/csrc/sweep_kernels.hpp"
 
@@ -28,17 +29,15 @@
 
 using namespace bobe;
 
-template <bool G>
 static double run(int nb, int64_t ncols, const double* Li, const double* B, double* V, double* qp, double secs,
                   unsigned long long* st, std::vector<unsigned long long>& host) {
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trimul<G>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trimul), hipFuncAttributeMaxDynamicSharedMemorySize,
                          GEMM_SMEM_BYTES));
   const int64_t Np = (int64_t)nb * TILE;
   const dim3 grid((unsigned)(ncols / TILE), (unsigned)nb);
   auto launch = [&] {
-    hipLaunchKernelGGL(k_trimul<G>, grid, dim3(256), GEMM_SMEM_BYTES, 0, Li, Np, nb, B, ncols, V, ncols, qp, ncols,
-                       (const double*)nullptr, (int64_t)0, 0, (double*)nullptr, (int64_t)0, (const double*)nullptr,
-                       (int64_t)0, 0, 1 << 30);
+    hipLaunchKernelGGL(k_trimul, grid, dim3(256), GEMM_SMEM_BYTES, 0, Li, Np, nb, B, ncols, V, ncols, qp, ncols,
+                       (const double*)nullptr, (int64_t)0, 0, (double*)nullptr, (int64_t)0);
   };
   launch();
   CK(hipDeviceSynchronize());
@@ -65,8 +64,7 @@ static double run(int nb, int64_t ncols, const double* Li, const double* B, doub
 }
 
 int main(int argc, char** argv) {
-  const bool glds = argc > 1 ? std::atoi(argv[1]) != 0 : true;
-  const double secs = argc > 2 ? std::atof(argv[2]) : 3.0;
+  const double secs = argc > 1 ? std::atof(argv[1]) : 3.0;
   const int nb = 32;
   const int64_t ncols = 8192, Np = (int64_t)nb * TILE;
   std::mt19937_64 rng(1);
@@ -87,7 +85,7 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(B, hB.data(), hB.size() * 8, hipMemcpyHostToDevice));
   CK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &st, sizeof(st)));
   std::vector<unsigned long long> h(nst);
-  const double ms = glds ? run<true>(nb, ncols, Li, B, V, qp, secs, st, h) : run<false>(nb, ncols, Li, B, V, qp, secs, st, h);
+  const double ms = run(nb, ncols, Li, B, V, qp, secs, st, h);
   std::vector<double> clk;
   double seg[4] = {0, 0, 0, 0}, loop = 0, steps = 0;
   for (size_t w = 0; w < nst / 8; ++w) {
@@ -100,11 +98,11 @@ int main(int argc, char** argv) {
   }
   std::sort(clk.begin(), clk.end());
   const double med = clk.empty() ? 0.0 : clk[clk.size() / 2];
-  std::printf("{\"loop\": \"%s\", \"stamped_ms_per_launch\": %.4f, \"waves\": %zu, \"clock_ghz_median\": %.4f, "
-              "\"clock_ghz_p10\": %.4f, \"clock_ghz_p90\": %.4f, \"cycles_per_kstep\": {\"first_fragment_wait\": %.1f, "
-              "\"mfma_body\": %.1f, \"staging_wait\": %.1f, \"barrier\": %.1f, \"loop_total\": %.1f}}\n",
-              glds ? "gemm_tile_glds<128>" : "gemm_tile (register-staged)", ms, clk.size(), med,
-              clk.empty() ? 0.0 : clk[clk.size() / 10], clk.empty() ? 0.0 : clk[clk.size() * 9 / 10], seg[0] / steps,
-              seg[1] / steps, seg[2] / steps, seg[3] / steps, loop / steps);
+  std::printf("{\"loop\": \"gemm_tile_glds<128>\", \"stamped_ms_per_launch\": %.4f, \"waves\": %zu, "
+              "\"clock_ghz_median\": %.4f, \"clock_ghz_p10\": %.4f, \"clock_ghz_p90\": %.4f, \"cycles_per_kstep\": "
+              "{\"first_fragment_wait\": %.1f, \"mfma_body\": %.1f, \"staging_wait\": %.1f, \"barrier\": %.1f, "
+              "\"loop_total\": %.1f}}\n",
+              ms, clk.size(), med, clk.empty() ? 0.0 : clk[clk.size() / 10], clk.empty() ? 0.0 : clk[clk.size() * 9 / 10],
+              seg[0] / steps, seg[1] / steps, seg[2] / steps, seg[3] / steps, loop / steps);
   return 0;
 }
