@@ -66,6 +66,7 @@ SIGNATURES = [
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("bobe_gp_wip_sweep_zvar", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                          C.c_void_p, c_double_p, c_int64_p, c_double_p]),
+    ("bobe_gp_evidence_moments", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, c_double_p, c_double_p]),
     ("bobe_gp_wip_select_batch_zvar", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("bobe_gp_fantasy_var", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),

@@ -221,6 +221,7 @@ class BOBE:
         self.ts_polish = 0
         self.weighted_polish = 0
         self.zvar_polish = 0
+        self.logz_moments = False
         self.ts_chain_steps, self.ts_chain_warmup = 0, 50
         self.min_delta_seen = np.inf
         self.current_iteration = 0
@@ -569,8 +570,12 @@ class BOBE:
         self.prev_samples = {"x": eq, "logl": np.asarray(equal_logl)}
         self.convergence_history.append({"iteration": int(step), "delta": float(delta), "converged": bool(below),
                                          "threshold": float(self.logz_threshold)})
+        moments = self.logz_moments and "moments_std" in logz_dict       # (reported only: the rule below does not read it)
+        if moments:
+            self.convergence_history[-1]["moments_std"] = float(logz_dict["moments_std"])
         if verbose:
-            log.info(f"Convergence check: delta = {delta:.4f}, step = {step}, threshold = {self.logz_threshold}")
+            log.info(f"Convergence check: delta = {delta:.4f}, step = {step}, threshold = {self.logz_threshold}" +
+                     (f", moments_std = {float(logz_dict['moments_std']):.4f}" if moments else ""))
         if below:
             self.convergence_counter += 1
             converged = self.convergence_counter >= self.convergence_n_iters
@@ -584,6 +589,10 @@ class BOBE:
                 self.gp.save(self.save_path + "_checkpoint_gp")
         return converged
 
+    def _ns_extras(self) -> dict:
+        """Keywords the loop adds to its ``nested_sampling`` calls: none unless ``run(logz_moments=True)``."""
+        return {"logz_moments": True} if self.logz_moments else {}
+
     # ------------------------------------------------------------------ main run methods (bo.py:963-1397)
     def run(self, acq="wipstd", min_evals: int = 200, max_evals: int = 1500, max_gp_size: int = 1200,
             logz_threshold: float = 0.01, convergence_n_iters: int = 1, ei_goal: float = 1e-10,
@@ -593,7 +602,8 @@ class BOBE:
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
             mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
             ts_polish: int = 0, ts_chain_steps: int = 0, ts_chain_warmup: int = 50, path_posterior: int = 0,
-            weighted_polish: int = 0, zvar_polish: int = 0, wip_batch_mode: str = "believer") -> dict:
+            weighted_polish: int = 0, logz_moments: bool = False, zvar_polish: int = 0,
+            wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
         optional ``acq_threshold`` stop, ``verbose``, and ``mc_sampler`` - the chains behind every ``method="NUTS"`` draw:
@@ -623,7 +633,11 @@ class BOBE:
         (default): the pool pick, and an ``acq_kwargs`` without the key, and ``zvar_polish`` - for ``acq`` 'zvar' stages
         only (a ValueError when no stage is 'zvar'): R in 1 .. 16 hands ``acq_kwargs['zvar_polish'] = R`` to ``acquisition.ZVar``,
         the same refinement on the evidence-variance score (``GP.wip_grad_zvar``, M^2 work per point and round); 0 (default):
-        the pool pick, and an ``acq_kwargs`` without the key.
+        the pool pick, and an ``acq_kwargs`` without the key, and ``logz_moments`` - True: every nested-sampling run of the
+        loop also forms the closed-form standard deviation of log Z under the surrogate's joint posterior at its samples
+        (``nested_sampling(logz_moments=True)``, ``GP.evidence_moments``), and every convergence check logs ``moments_std``
+        beside ``delta`` and records it in ``convergence_history``; reported only - the stopping rule, the checkpoints and the
+        run's generator are as without it; False (default): no such key, no device call.
         ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
         samples; ``acq`` 'zvar' (``acquisition.ZVar``) runs it with the expected posterior variance of the evidence estimate as the
@@ -669,6 +683,7 @@ class BOBE:
         if isinstance(zvar_polish, bool) or not isinstance(zvar_polish, (int, np.integer)) or not 0 <= int(zvar_polish) <= 16:
             raise ValueError(f"zvar_polish must be an integer between 0 and 16, not {zvar_polish!r}")
         self.zvar_polish = int(zvar_polish)
+        self.logz_moments = bool(logz_moments)
         for name, v in (("ts_chain_steps", ts_chain_steps), ("ts_chain_warmup", ts_chain_warmup),
                         ("path_posterior", path_posterior)):
             if isinstance(v, bool) or int(v) != v or int(v) < 0:
@@ -859,7 +874,7 @@ class BOBE:
             if ns_flag and float(acq_vals[-1]) <= self.logz_threshold:        # bo.py:1283-1311
                 t0 = time.time()
                 ns_samples, logz_dict, ns_success = nested_sampling(self.gp, mode="convergence", dlogz=0.01,
-                                                                    equal_weights=False, rng=self.np_rng)
+                                                                    equal_weights=False, rng=self.np_rng, **self._ns_extras())
                 self.timing["Nested Sampling"] += time.time() - t0
                 self.ns_samples, self._ns_success = ns_samples, ns_success
                 if ns_success:
@@ -902,7 +917,7 @@ class BOBE:
             self.timing["GP Training"] += time.time() - t0
             t0 = time.time()
             self.ns_samples, logz_dict, ns_success = nested_sampling(self.gp, mode="convergence", dlogz=0.01,
-                                                                     rng=self.np_rng)
+                                                                     rng=self.np_rng, **self._ns_extras())
             self.timing["Nested Sampling"] += time.time() - t0
             if ns_success:
                 equal_samples, equal_logl = resample_equal(self.ns_samples["x"], self.ns_samples["logl"],

@@ -375,6 +375,15 @@ int bobe_gp_wip_sweep_zvar(bobe_gp_t* g, const double* cand, int64_t C, const do
   API_END
 }
 
+int bobe_gp_evidence_moments(bobe_gp_t* g, const double* Z, int64_t M, double y_std, const double* logw, double* log_ez,
+                             double* log_t0) {
+  API_BEGIN
+  NEED(g && Z, "NULL argument");
+  NEED(log_ez || log_t0, "no output requested (log_ez and log_t0 are NULL)");
+  return g->evidence_moments(Z, M, y_std, logw, log_ez, log_t0);
+  API_END
+}
+
 int bobe_gp_wip_select_batch_zvar(bobe_gp_t* g, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                                   const double* logw, int n_batch, int64_t* picks, double* pick_scores,
                                   double* stage_scores) {

@@ -9,10 +9,13 @@
 // bobe_gp_wip_grad_w (values and input gradients of the four scores through bobe_gp_wip_grad's few-candidate chain) and
 // bobe_gp_wip_grad_zvar (the same for the evidence-variance score) are the entries here that go through prepare_z themselves
 // and keep something between calls: the per-z table beside prepare_z's cache (bobe_gp::zw), their workspace and staged outputs.
+// bobe_gp_evidence_moments (the total variance of the evidence estimate; kernels: evidence_kernels.hpp) goes through
+// prepare_z too and keeps nothing of its own: its table, rows, tile sums and staged weights are freed before it returns.
 #include "gp_handle.hpp"
 
 #include "batch_kernels.hpp"
 #include "criteria_kernels.hpp"
+#include "evidence_kernels.hpp"
 
 using namespace bobe;
 
@@ -345,4 +348,59 @@ int bobe_gp::wip_select_batch_w(const double* cand, int64_t C, const double* Z, 
   SweepW w;
   w.logw = logw;
   return select_batch(cand, C, Z, M, y_std, n_batch, criterion, picks, pick_scores, stage_scores, &w);
+}
+
+// bobe_gp_evidence_moments: log E[Z] (bobe_gp_wip_sweep_zvar's bits: the same table launch) and log T0 = log (Var Z / E[Z]^2).
+// prepare_z (the sweep's, with its cache of a repeated host Z), the per-z table with its lambda row, then k_evid_h ->
+// k_evid_pairs over the lower tile pairs -> k_evid_fold, and one copy home.
+namespace {
+void configure_evidence_kernels() {
+  static bool done[64] = {false};
+  if (!first_use_on_device(done)) return;
+  allow_big_lds(k_evid_pairs<0>, GEMM_SMEM_BYTES);
+  allow_big_lds(k_evid_pairs<1>, GEMM_SMEM_BYTES);
+}
+constexpr int64_t EVID_CAP_DOUBLES = int64_t(1) << 31;   // the batch selection's cap (gp_batch.hip): 16 GiB
+}  // namespace
+
+int bobe_gp::evidence_moments(const double* Z, int64_t M, double y_std, const double* logw, double* log_ez, double* log_t0) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  if (M <= 0) throw Err(BOBE_ERR_ARG, "M must be positive");
+  const int64_t Mp = round_up(M, TILE);
+  // prepare_z keeps K(X,Z), V_Z and W_Z on the handle, Np x Mp each; the call adds one double per tile pair (nothing is read
+  // or allocated before this test)
+  const bool over = Mp > EVID_CAP_DOUBLES / (3 * Np);
+  if (over || 3 * Np * Mp + (Mp / TILE) * (Mp / TILE + 1) / 2 > EVID_CAP_DOUBLES)
+    throw Err(BOBE_ERR_ARG, "too many integration points: the handle's Z-side buffers, 3 x Np x Mp doubles, and the tile pairs' "
+                            "sums exceed 16 GiB");
+  use();
+  configure_evidence_kernels();
+  prepare_z(Z, M, Mp, false);
+  SweepW w;
+  w.logw = logw;
+  wip_zterms(w, M, Mp, y_std, basez.d(), true, true);
+  const int64_t nt = Mp / TILE, ntiles = nt * (nt + 1) / 2;
+  CallBuf ev, parts, res;
+  ev.ensure((size_t)(EVID_ROWS * Mp + 8) * sizeof(double));
+  parts.ensure((size_t)ntiles * sizeof(double));
+  res.ensure(8 * sizeof(double));
+  hipLaunchKernelGGL(k_evid_h, dim3(1), dim3(256), 0, stream, (const double*)(w.zt.d() + 5 * w.ldt), (const double*)basez.d(), M,
+                     Mp, y_std, ev.d());
+  prof_begin(BOBE_PROF_CROSSVV);              // (the class of the tile products V^T V: k_cross_vv, k_sigma_tiles, the paths' product)
+  if (kern == BOBE_KERNEL_RBF)
+    hipLaunchKernelGGL(k_evid_pairs<0>, dim3((unsigned)ntiles), dim3(256), GEMM_SMEM_BYTES, stream, (const double*)VZ.d(), Mp,
+                       Np, (const double*)ZsT.d(), Mp, (const double*)ev.d(), Mp, M, hyp, y_std, parts.d());
+  else
+    hipLaunchKernelGGL(k_evid_pairs<1>, dim3((unsigned)ntiles), dim3(256), GEMM_SMEM_BYTES, stream, (const double*)VZ.d(), Mp,
+                       Np, (const double*)ZsT.d(), Mp, (const double*)ev.d(), Mp, M, hyp, y_std, parts.d());
+  prof_end(BOBE_PROF_CROSSVV);
+  hipLaunchKernelGGL(k_evid_fold, dim3(1), dim3(256), 0, stream, (const double*)parts.d(), ntiles,
+                     (const double*)(ev.d() + EVID_ROWS * Mp), (const double*)w.log_ez(), res.d());   // log E[Z] rides home with it
+  LAUNCH_CHECK();
+  double hb[2] = {0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(hb, res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
+  if (log_t0) *log_t0 = hb[0];
+  if (log_ez) *log_ez = hb[1];
+  return BOBE_OK;
 }

@@ -11,7 +11,8 @@
 //   gp_loo.hip        leave-one-out predictive terms of the state, the LOO objective and its gradient
 //   gp_batch.hip      one-sweep batch selection for WIPV / WIPStd (the sweep's intermediates kept, rank-one downdates)
 //   gp_criteria.hip   importance-weighted integration points, IMIQR / EIV: the weighted scoring pass of the sweep and the batch,
-//                     the input gradients of the four scores (few-candidate chain)
+//                     the input gradients of the four scores (few-candidate chain); the total variance of the evidence estimate
+//                     over the integration points (the pair sum on the 128-tile core)
 //   gp_paths.hip      pathwise posterior draws of the latent surrogate (random Fourier features + Matheron's rule): path
 //                     sets, their evaluation at query points and per-path argmax, input gradients, whole HMC chains on a path
 //   gp_abi.hip        the extern "C" layer, the RCCL exchange step, test / bench hooks
@@ -801,6 +802,10 @@ struct bobe_gp {
   void wip_grad_table(int64_t M, int64_t Mp, double y_std, const double* logw, bool lam);
   int wip_grad_chain(const char* entry, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                      const double* logw, double* const scores[4], double* const grads[4], int mask, bool zv, double* log_ez);
+
+  // ---- gp_criteria.hip: log E[Z] and log T0 = log (Var Z / E[Z]^2) of the evidence estimate over Z (evidence_kernels.hpp);
+  // prepare_z, the per-z table with its lambda row, then k_evid_h -> k_evid_pairs -> k_evid_fold and one copy home
+  int evidence_moments(const double* Z, int64_t M, double y_std, const double* logw, double* log_ez, double* log_t0);
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);

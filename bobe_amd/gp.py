@@ -79,6 +79,15 @@ class _scratch_handle:
         return False
 
 
+def std_from_log_t0(log_t0: float) -> float:
+    """sqrt(log1p(exp(log_t0))): the standard deviation of log Z of the lognormal whose squared coefficient of variation is
+    exp(log_t0).  Formed from the log where the exponential would overflow: log1p(e^t) = t + log1p(e^-t)."""
+    t = float(log_t0)
+    if t != t:
+        return t
+    return math.sqrt(t + math.log1p(math.exp(-t))) if t > 30.0 else math.sqrt(math.log1p(math.exp(t)))
+
+
 def dist_sq(x, y):
     """gp.py:80-96: squared Euclidean distances (n1, n2) of the rows of ``x`` and ``y``, on the GPU (bobe_gp_dist_sq)."""
     x = _lib.as_f64(np.atleast_2d(x))
@@ -944,6 +953,26 @@ class GP:
         if want_mean_var:
             out["mean"], out["var"] = mean, var
         return out
+
+    def evidence_moments(self, mc_points, *, log_weights=None):
+        """Mean and TOTAL variance of the evidence estimate Z = sum_z e^{l_z} e^{f(z)} over the integration points under the
+        surrogate's joint posterior (``bobe_gp_evidence_moments``): the closed form of the lognormal estimate, with the
+        posterior covariance of every pair of points formed on the fly - nothing is stored, factorised or drawn, so M is
+        bounded by what ``wip_sweep`` holds for the same points, not by M^2.
+
+        ``mc_points``: NumPy array or torch CUDA tensor; ``log_weights`` as in ``wip_sweep`` (None: l_z = -mu_z).  Returns
+        ``log_ez`` = log E[Z] (physical: y_mean added; ``wip_sweep(criteria=('zvar',))``'s), ``log_t0`` = log (Var Z /
+        E[Z]^2), ``log_var_z`` = log_t0 + 2 log_ez and ``std_logz`` = sqrt(log1p(exp(log_t0))), the standard deviation of
+        log Z of the lognormal with these two moments.  ``exp(-zvar[c] - log_t0)`` is the share of the evidence variance that an
+        evaluation at candidate c is expected to remove (``zvar`` of ``wip_sweep`` on the same points and weights)."""
+        z = mc_points if hasattr(mc_points, "data_ptr") else _lib.as_f64(np.atleast_2d(mc_points))
+        m = int(z.shape[0])
+        lw = self._log_weights(log_weights, m)
+        lez, lt0 = C.c_double(0.0), C.c_double(0.0)
+        _lib.check(self._lib.bobe_gp_evidence_moments(self._h, _lib.ptr(z), m, float(self.y_std), _lib.ptr(lw), C.byref(lez),
+                                                      C.byref(lt0)), "bobe_gp_evidence_moments")
+        log_ez, log_t0 = lez.value + float(self.y_mean), lt0.value
+        return {"log_ez": log_ez, "log_t0": log_t0, "log_var_z": log_t0 + 2.0 * log_ez, "std_logz": std_from_log_t0(log_t0)}
 
     def wip_select_batch(self, candidates, mc_points, n_batch, criterion="wipstd", return_stage_scores=False):
         """A kriging-believer batch of ``n_batch`` WIPV / WIPStd picks out of ``candidates`` from ONE sweep

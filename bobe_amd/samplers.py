@@ -77,7 +77,8 @@ def _draw_in_ellipsoid(mu, A, n, rng):
 
 def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float, *, n_draws: int = 0,
                       draws_seed: int = 0, draws_max_points: int = 16384, draws_method: str = "joint",
-                      draws_features: int = 2048, draws_arrays: Optional[Dict] = None) -> Dict:
+                      draws_features: int = 2048, draws_arrays: Optional[Dict] = None, moments: bool = False,
+                      moments_max_points: int = 65536) -> Dict:
     """The logZ dictionary of a finished run (samplers.py:172-183): the GP's predictive variance at every sample —
     ONE batched ``bobe_gp_predict`` call instead of the reference's ``lax.map`` over points — turns into
     logl +- std for the upper / lower evidence integrals and into the variance estimate of logZ.
@@ -91,7 +92,13 @@ def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float,
     covariance (``GP.sample_posterior``, at most 16384 points); 'paths' perturbs EVERY sample with a finite, ungated logl by a
     centred pathwise draw of the surrogate (``GP.sample_paths`` with ``draws_features`` random Fourier features, cost linear
     in the number of samples, no cap) and reports ``draws_features`` in the place of ``draws_jitter``.  ``draws_arrays``
-    ('paths' only): the caller's ``u`` / ``phase`` / ``w`` / ``eps`` for ``GP.sample_paths`` instead of the seeded ones."""
+    ('paths' only): the caller's ``u`` / ``phase`` / ``w`` / ``eps`` for ``GP.sample_paths`` instead of the seeded ones.
+
+    ``moments=True`` adds the GP's own answer in closed form (``_logz_moments``, ``GP.evidence_moments``: the exact mean and
+    variance of the lognormal evidence estimate under the JOINT posterior of the surrogate at the samples, nothing drawn, no
+    cap of 16384): ``moments_log_ez``, ``moments_log_var``, ``moments_std`` (of log Z) and ``moments_points``, the number of
+    samples that enter as random (``draws_points`` with ``moments_max_points``; the rest are constants).  The other keys do
+    not depend on it either."""
     if draws_method not in ("joint", "paths"):
         raise ValueError(f"draws_method must be 'joint' or 'paths', not {draws_method!r}")
     logl = np.asarray(logl, dtype=np.float64)
@@ -109,6 +116,8 @@ def logz_from_samples(gp, samples_x, logl, logvol, mean: float, logz_err: float,
                                      draws_arrays))
     elif n_draws > 0:
         out.update(_logz_draws(gp, samples_x, logl, logvol, int(n_draws), int(draws_seed), int(draws_max_points)))
+    if moments:
+        out.update(_logz_moments(gp, samples_x, logl, logvol, int(moments_max_points)))
     return out
 
 
@@ -133,6 +142,32 @@ def draws_points(gp, logl, logvol, max_points: int = 16384) -> np.ndarray:
         logwt = _log_weights(logl, np.asarray(logvol, dtype=np.float64))
         idx = np.sort(idx[np.argsort(-logwt[idx], kind="stable")[:max_points]])
     return idx
+
+
+def _logz_moments(gp, samples_x, logl, logvol, max_points: int) -> Dict:
+    """Mean and variance of Z = sum_z e^{logwt_z} e^{f(z) - logl_z} over the free samples (``draws_points``: finite, ungated,
+    the ``max_points`` heaviest; a sample whose weight logwt is not finite - two equal log-volumes in a row - is held fixed like
+    the gated ones and adds nothing) plus the constants e^{logwt_z} of the others, from ``gp.evidence_moments`` with
+    l_z = logwt_z - logl_z (the convention of ``get_mc_points(weighted=True)``).  std: of log Z, lognormal-matched, from logs."""
+    from .gp import std_from_log_t0
+    logl = np.asarray(logl, dtype=np.float64)
+    logvol = np.asarray(logvol, dtype=np.float64)
+    logwt = _log_weights(logl, logvol)
+    idx = draws_points(gp, logl, logvol, max_points)
+    idx = idx[np.isfinite(logwt[idx])]
+    fixed = np.ones(len(logl), dtype=bool)
+    fixed[idx] = False
+    fw = logwt[fixed]
+    fw = fw[np.isfinite(fw)]
+    log_fixed = float(np.logaddexp.reduce(fw)) if len(fw) else -math.inf
+    if not len(idx):
+        return {"moments_log_ez": log_fixed, "moments_log_var": -math.inf, "moments_std": 0.0, "moments_points": 0}
+    m = gp.evidence_moments(np.asarray(samples_x)[idx], log_weights=logwt[idx] - logl[idx])
+    log_ez = float(np.logaddexp(m["log_ez"], log_fixed))
+    log_var = float(m["log_t0"] + 2.0 * m["log_ez"])
+    # log (Var Z / E[Z]^2) of the whole sum -> the standard deviation of log Z
+    return {"moments_log_ez": log_ez, "moments_log_var": log_var, "moments_std": float(std_from_log_t0(log_var - 2.0 * log_ez)),
+            "moments_points": int(len(idx))}
 
 
 def _logz_draws(gp, samples_x, logl, logvol, n_draws: int, seed: int, max_points: int) -> Dict:
@@ -212,7 +247,7 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
                     maxcall: int = int(5e6), equal_weights: bool = False, rng=None, batch: int = 8192,
                     enlarge: float = 1.25, nlive: Optional[int] = None, sample_method: str = "auto",
                     walks: Optional[int] = None, device_walks: bool = True, logz_draws: int = 0,
-                    logz_draws_seed: int = 0, *, keep_weights: bool = False,
+                    logz_draws_seed: int = 0, *, keep_weights: bool = False, logz_moments: bool = False,
                     logz_draws_method: str = "joint") -> Tuple[Dict, Dict, bool]:
     """Static nested sampling of exp(GP mean) over the unit cube -> (samples_dict, logz_dict, success).
 
@@ -225,7 +260,8 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     ``logz_draws`` > 0: the logZ dictionary also holds the evidence of that many joint posterior draws of the surrogate
     (``logz_from_samples``, seeded by ``logz_draws_seed``); reported only, nothing else depends on them.
     ``keep_weights``: mode 'acq' returns the weighted samples as they are instead of resampling them to equal weights.
-    ``logz_draws_method``: 'joint' (default) or 'paths' - how those draws are made (``logz_from_samples``, ``draws_method``)."""
+    ``logz_draws_method``: 'joint' (default) or 'paths' - how those draws are made (``logz_from_samples``, ``draws_method``).
+    ``logz_moments``: True adds the closed-form ``moments_*`` keys of ``logz_from_samples(moments=True)``; reported only."""
     if logz_draws_method not in ("joint", "paths"):
         raise ValueError(f"logz_draws_method must be 'joint' or 'paths', not {logz_draws_method!r}")
     rng = rng if rng is not None else get_numpy_rng()
@@ -248,6 +284,8 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
         if logz_draws > 0:
             logz_nan.update(draws=np.full(int(logz_draws), nan), draws_mean=nan, draws_std=nan, draws_points=0)
             logz_nan.update({"draws_features": 0} if logz_draws_method == "paths" else {"draws_jitter": nan})
+        if logz_moments:
+            logz_nan.update(moments_log_ez=nan, moments_log_var=nan, moments_std=nan, moments_points=0)
         return ({"x": live, "weights": np.ones(nlive), "logl": live_logl, "best": live[0], "method": "nested"},
                 logz_nan, False)
     use_rwalk = sample_method == "rwalk" or (sample_method == "auto" and ndim > 4)
@@ -366,7 +404,7 @@ def nested_sampling(gp, ndim: Optional[int] = None, mode: str = "convergence", d
     success = bool(~np.all(logl == logl[0])) and not gave_up
 
     logz_dict = logz_from_samples(gp, samples_x, logl, logvol, mean, logz_err, n_draws=logz_draws,
-                                  draws_seed=logz_draws_seed, draws_method=logz_draws_method)
+                                  draws_seed=logz_draws_seed, draws_method=logz_draws_method, moments=bool(logz_moments))
     logz_dict.update(ncall=int(ncall), niter=int(niter), truncated=bool(truncated))
     best_pt = samples_x[int(np.argmax(logl))]
     weights = renormalise_log_weights(logwt)
@@ -388,15 +426,15 @@ def prior_transform(x):
 def nested_sampling_Dy(gp, mode: str = "acq", ndim: int = 1, dlogz: float = 0.1, dynamic: bool = False,
                        maxcall: Optional[int] = int(5e6), print_progress: Optional[bool] = True,
                        equal_weights: bool = False, sample_method: str = "rwalk", rng=None, *, logz_draws: int = 0,
-                       logz_draws_seed: int = 0, logz_draws_method: str = "joint"):
+                       logz_draws_seed: int = 0, logz_moments: bool = False, logz_draws_method: str = "joint"):
     """The reference's entry point name and keywords (samplers.py:55-65) on ``nested_sampling`` above; ``dynamic``,
     ``print_progress`` are dynesty options without a counterpart here; ``sample_method='rwalk'`` (the reference's
     default) maps to 'auto': exact ellipsoid draws in up to 4 dimensions, batched random walks above.  ``logz_draws``,
-    ``logz_draws_seed``, ``logz_draws_method``: see ``nested_sampling``."""
+    ``logz_draws_seed``, ``logz_moments``, ``logz_draws_method``: see ``nested_sampling``."""
     return nested_sampling(gp, ndim=ndim if ndim and ndim > 1 else gp.ndim, mode=mode, dlogz=dlogz,
                            maxcall=maxcall if maxcall is not None else int(5e6), equal_weights=equal_weights, rng=rng,
                            sample_method="auto" if sample_method == "rwalk" else sample_method, logz_draws=logz_draws,
-                           logz_draws_seed=logz_draws_seed, logz_draws_method=logz_draws_method)
+                           logz_draws_seed=logz_draws_seed, logz_moments=logz_moments, logz_draws_method=logz_draws_method)
 
 
 def get_hmc_settings(ndim, warmup_steps=None, num_samples=None, thinning=None):

@@ -250,8 +250,9 @@ int bobe_gp_wip_select_batch_w(bobe_gp_t* gp, const double* cand, int64_t C, con
  * total variance
  *   E_xi[Var+ Z] = Var Z - E[Z]^2 T(c),   T(c) = sum_z sum_z' omega_z omega_z' expm1(r_z r_z'),
  *   omega = softmax(l_z + mu_z + b_z / 2),   E[Z] = exp(*log_ez),   *log_ez = LSE_z (l_z + mu_z + b_z / 2).
- * The posterior covariance among the integration points enters the c-independent Var Z only, which is not formed
- * (bobe_gp_predict_cov supplies it to a caller who wants the absolute figure).  T >= 0; for small r it tends to
+ * The posterior covariance among the integration points enters the c-independent Var Z only, which this entry does not
+ * form: bobe_gp_evidence_moments returns it (as log T0 = log (Var Z / E[Z]^2), the denominator of the share exp(-zvar[c] -
+ * log T0) of the evidence variance that an evaluation at c is expected to remove).  T >= 0; for small r it tends to
  * (sum_z omega_z r_z)^2.
  *   zvar[c] = -log T(c), to MINIMISE; the expected reduction of Var Z is exp(2 *log_ez - zvar[c]).  omega is normalised: the
  *   score carries no y_mean shift (a caller in physical units adds y_mean to *log_ez).
@@ -271,6 +272,38 @@ int bobe_gp_wip_select_batch_w(bobe_gp_t* gp, const double* cand, int64_t C, con
  * bobe_gp_wip_sweep (BOBE_OK; the scores are NaN where mu_z is, +inf where only the cross terms are). */
 int bobe_gp_wip_sweep_zvar(bobe_gp_t* gp, const double* cand, int64_t C, const double* Z, int64_t M, double y_std,
                            const double* logw, double* zvar, double* log_ez, int64_t* argmin, double* min);
+
+/* The TOTAL variance of the evidence estimate under the surrogate's joint posterior at the M integration points Z (a build
+ * addition; the closed form of the lognormal estimate, the c-independent term of bobe_gp_wip_sweep_zvar).  Notation and units
+ * are bobe_gp_wip_sweep_zvar's (physical, no y_mean): Z = sum_z e^{l_z} e^{f(z)}, l_z = logw[z] or -mu_z when logw is NULL,
+ *   mu_z = y_std (K(X,Z)^T alpha)_z,   b_z = y_std^2 base_z (non-finite or < 1e-12 -> 1e-12 before the scaling),
+ *   S_zz' = y_std^2 (k(z,z') - V_z . V_z') for z != z',   S_zz = b_z,
+ *   g_z = l_z + mu_z + b_z / 2,   *log_ez = LSE_z g_z,   lambda_z = g_z - *log_ez,   omega = e^lambda,
+ *   T0 = sum_z sum_z' omega_z omega_z' expm1(S_zz')  over all M^2 ordered pairs,   Var Z = e^{2 *log_ez} T0,
+ *   *log_t0 = log T0: the log of the squared coefficient of variation of Z.
+ * Rules: for z != z', |S_zz'| is capped at sqrt(b_z b_z') (Cauchy-Schwarz; it binds only where rounding or the floor left
+ * the diagonal small); a non-finite off-diagonal S counts as 0; T0 <= 0 (underflown or rounding-negative) gives
+ * *log_t0 = -inf.  No exponent above 0 is taken: with h = max_z (lambda_z + b_z / 2), p_z = lambda_z - h, E_z = e^{p_z}, a
+ * pair with |S| < 1 adds E_z E_z' expm1(S), any other exp(p_z + p_z' + S) - E_z E_z', and log T0 = 2 h + log sum - one
+ * transcendental per pair; y_std ~ 4e3 (log T0 ~ 1e7) stays finite.
+ * Consequences: exp(-zvar[c] - *log_t0) is the expected share of the evidence variance that an evaluation at c removes, in
+ * [0, 1]; the lognormal-matched standard deviation of log Z is sqrt(log1p(T0)).
+ * Sigma is never stored, nothing is factorised, no jitter is added, nothing is drawn: one launch over the M / 128 (M / 128 + 1)
+ * / 2 lower 128 x 128 tile pairs forms V_z . V_z' on the sweep's tile core and sums the pair terms in its epilogue (an
+ * off-diagonal pair counts twice, the diagonal once).  M is bounded by the Np x Mp buffers the sweep itself holds for Z:
+ * BOBE_ERR_ARG when the three of them (K(X,Z), V_Z, W_Z) and the call's one double per tile pair would pass
+ * bobe_gp_wip_select_batch's 16 GiB in all (the tile sums matter at small Np only: Mp^2 / 32768 doubles).
+ * Summation order: a lane adds its 64 (or fewer) elements of the tile in fragment order; the 64 lanes of a wave fold in one
+ * fixed tree, the four waves in order; the tiles' sums are added per thread t = tile mod 256 ascending, then pairwise.  No
+ * atomics.  The bits depend on the state, Z, logw and y_std alone - not on the pointer kinds, on a hit or miss of the
+ * handle's cache of Z's quantities (the sweep's: a repeated host Z is not prepared again, and a later bobe_gp_wip_sweep* on
+ * the same Z hits it too), or on which output is NULL.  *log_ez carries bobe_gp_wip_sweep_zvar's bits.
+ * Z (M x d) and logw (M, may be NULL): host or device.  log_ez, log_t0: host, one value each; either may be NULL, not both.
+ * NOT gated.  BOBE_ERR_ARG: NULL Z, M < 1, both outputs NULL, the cap; BOBE_ERR_STATE without a factorised state - no output
+ * is touched then; a NaN state (NaN mu_z) returns BOBE_OK with both outputs NaN, with or without logw (l_z + mu_z is NaN
+ * either way), as bobe_gp_wip_sweep_zvar does. */
+int bobe_gp_evidence_moments(bobe_gp_t* gp, const double* Z, int64_t M, double y_std, const double* logw, double* log_ez,
+                             double* log_t0);
 
 /* bobe_gp_wip_select_batch_w with bobe_gp_wip_sweep_zvar's scorer at every stage.  Row 0 of stage_scores and picks[0] are
  * bobe_gp_wip_sweep_zvar's bits and argmin.  Under the believer append mu_z does not change: omega's l_z + mu_z part is the
@@ -701,7 +734,9 @@ int bobe_debug_factor_source(bobe_gp_t* gp);
 #define BOBE_PROF_TRIMUL 6 /* sweep: V = Linv * K(X, C_chunk) with column sum of squares */
 #define BOBE_PROF_CROSS 7  /* sweep: WIPV / WIPStd scoring */
 #define BOBE_PROF_KXX 8    /* K(X,X) assembly */
-#define BOBE_PROF_CROSSVV 9 /* sweep: cross-covariance GEMM V_Z^T V of the two solved factors */
+#define BOBE_PROF_CROSSVV 9 /* sweep: cross-covariance GEMM V_Z^T V of the two solved factors; the class also brackets the other
+                             * tile products of solved factors - bobe_gp_predict_cov's Sigma pass, the paths' product and
+                             * bobe_gp_evidence_moments' pair launch - so a total mixes whichever of them ran while it was selected */
 #define BOBE_PROF_KXC 10   /* sweep: K(X, C_chunk) assembly */
 int bobe_gp_profile_select(bobe_gp_t* gp, int kernel_class);
 int bobe_gp_profile_read(bobe_gp_t* gp, double* total_ms, int64_t* launches);
