@@ -127,10 +127,28 @@ class EI(AcquisitionFunction):
             return -log_ei, -grad
         return vg
 
+    def _lockstep_value_and_grad(self, gp, best_y, zeta):
+        """(vg, batch_vg) on ``GP.acq_ei_grad``: the negated value and gradient of one point, and of every point handed
+        over in ONE device call - value and gradient from the same posterior, nothing assembled on the host."""
+        def batch_vg(xs):
+            val, grad = gp.acq_ei_grad(np.asarray(xs, dtype=np.float64), best_y, zeta, log_ei=self._log)
+            return [(-float(v), -g) for v, g in zip(val, grad)]
+
+        def vg(x):
+            return batch_vg([np.asarray(x, dtype=np.float64)])[0]
+        return vg, batch_vg
+
     def get_next_point(self, gp, acq_kwargs=None, maxiter: int = 250, n_restarts: int = 20, verbose: bool = True,
                        early_stop_patience: int = 25, rng=None):
+        """``acq_kwargs['ei_lockstep']`` (default off: the loop below as ever, one restart after the other on
+        ``predict_grad`` + ``acq_ei``): the same starts, drawn by the same calls on ``rng``, with all restarts advancing in
+        lock step on ``GP.acq_ei_grad`` - the screening and every L-BFGS-B round are one device call
+        (``optimize_scipy(batch_value_and_grad=)``); restart order, acceptance rule and return value are unchanged."""
         rng = rng if rng is not None else get_numpy_rng()
         acq_kwargs = acq_kwargs if acq_kwargs is not None else {}
+        lockstep = bool(acq_kwargs.get("ei_lockstep", False))
+        if lockstep and self.optimizer != "scipy":
+            raise ValueError(f"acq_kwargs['ei_lockstep'] needs optimizer='scipy', not {self.optimizer!r}")
         zeta = acq_kwargs.get("zeta", 0.0)
         best_y = acq_kwargs.get("best_y", float(np.max(gp.train_y)))
         best_x = gp.train_x[int(np.argmax(gp.train_y))]
@@ -141,6 +159,12 @@ class EI(AcquisitionFunction):
         else:
             x0 = np.atleast_2d(best_x)
         x0 = np.clip(x0 + rng.normal(0.0, 0.005, size=x0.shape), 0.0, 1.0)
+        if lockstep:
+            vg, batch_vg = self._lockstep_value_and_grad(gp, best_y, zeta)
+            pts, vals = optimize_scipy(vg, num_params=gp.ndim, x0=x0, bounds=[0, 1],
+                                       optimizer_options=dict(self.optimizer_options), maxiter=maxiter,
+                                       n_restarts=n_restarts, verbose=verbose, batch_value_and_grad=batch_vg)
+            return pts, -vals
         pts, vals = self.acq_optimize(self._value_and_grad(gp, best_y, zeta), num_params=gp.ndim, x0=x0,
                                       bounds=[0, 1], optimizer_options=dict(self.optimizer_options),
                                       maxiter=maxiter, n_restarts=n_restarts, verbose=verbose)

@@ -221,6 +221,7 @@ class BOBE:
         self.ts_polish = 0
         self.weighted_polish = 0
         self.zvar_polish = 0
+        self.ei_lockstep = False
         self.logz_moments = False
         self.ts_chain_steps, self.ts_chain_warmup = 0, 50
         self.min_delta_seen = np.inf
@@ -602,7 +603,7 @@ class BOBE:
             num_mc_samples: int = 1024, acq_threshold: Optional[float] = None, verbose: bool = False,
             mc_sampler: str = "hmc", loo_diagnostics: bool = False, mc_weighted: bool = False,
             ts_polish: int = 0, ts_chain_steps: int = 0, ts_chain_warmup: int = 50, path_posterior: int = 0,
-            weighted_polish: int = 0, logz_moments: bool = False, zvar_polish: int = 0,
+            weighted_polish: int = 0, logz_moments: bool = False, ei_lockstep: bool = False, zvar_polish: int = 0,
             wip_batch_mode: str = "believer") -> dict:
         """``BOBE.run`` (bo.py:967-1172): the reference's keywords in its order with its defaults (``acq='wipstd'``,
         batches of 4); keyword-only extras: ``num_mc_samples`` for the 'uniform' / 'NS' integration-point methods, an
@@ -637,7 +638,11 @@ class BOBE:
         loop also forms the closed-form standard deviation of log Z under the surrogate's joint posterior at its samples
         (``nested_sampling(logz_moments=True)``, ``GP.evidence_moments``), and every convergence check logs ``moments_std``
         beside ``delta`` and records it in ``convergence_history``; reported only - the stopping rule, the checkpoints and the
-        run's generator are as without it; False (default): no such key, no device call.
+        run's generator are as without it; False (default): no such key, no device call, and ``ei_lockstep`` - for ``acq``
+        'ei' / 'logei' stages only (a ValueError when there is none): True hands ``acq_kwargs['ei_lockstep'] = True`` to
+        ``EI`` / ``LogEI``, whose restarts then advance in lock step on ``GP.acq_ei_grad``, one device call per L-BFGS-B round
+        (same starts, same draws from the run's generator, same acceptance rule); False (default): the restarts one after
+        the other, and an ``acq_kwargs`` without the key; the checkpoints are the same either way.
         ``acq`` 'imiqr' / 'eiv' (``acquisition.IMIQR`` / ``EIV``) run the WIPV / WIPStd loop with
         those criteria, ``acq`` 'ts' (``acquisition.PathwiseTS``) the same loop with Thompson batches out of the integration
         samples; ``acq`` 'zvar' (``acquisition.ZVar``) runs it with the expected posterior variance of the evidence estimate as the
@@ -684,6 +689,9 @@ class BOBE:
             raise ValueError(f"zvar_polish must be an integer between 0 and 16, not {zvar_polish!r}")
         self.zvar_polish = int(zvar_polish)
         self.logz_moments = bool(logz_moments)
+        if not isinstance(ei_lockstep, (bool, np.bool_)):
+            raise ValueError(f"ei_lockstep must be True or False, not {ei_lockstep!r}")
+        self.ei_lockstep = bool(ei_lockstep)
         for name, v in (("ts_chain_steps", ts_chain_steps), ("ts_chain_warmup", ts_chain_warmup),
                         ("path_posterior", path_posterior)):
             if isinstance(v, bool) or int(v) != v or int(v) < 0:
@@ -715,6 +723,8 @@ class BOBE:
                 raise ValueError("acq='zvar' is polished by zvar_polish: weighted_polish must be 0")
         if self.zvar_polish > 0 and not any(a.lower() == "zvar" for a in acqs):
             raise ValueError(f"zvar_polish polishes acq='zvar' stages, and there is none in {acqs!r}")
+        if self.ei_lockstep and not any(a.lower() in ("ei", "logei") for a in acqs):
+            raise ValueError(f"ei_lockstep runs acq='ei' / 'logei' stages, and there is none in {acqs!r}")
         self.current_iteration = self.start_iteration
         rs, self._resume_state = self._resume_state, None        # (a second run() on this object starts from its current state)
         # A tuple of acquisition functions runs as stages, one after the other (bo.py:1149-1158); a saved run state names the
@@ -792,6 +802,8 @@ class BOBE:
                 log.info(f"Iteration {ii} of {self.acquisition.name}, objective evals {current_evals}/{self.max_evals}")
             acq_kwargs = {"zeta": self.zeta_ei,
                           "best_y": float(np.max(self.gp.train_y)) if self.gp.train_y.size > 0 else 0.0}
+            if self.ei_lockstep:
+                acq_kwargs["ei_lockstep"] = True
             n_batch = 1
             new_pts_u, acq_vals = self.get_next_batch(acq_kwargs, n_batch=n_batch, n_restarts=50, maxiter=1000,
                                                       early_stop_patience=50, step=ii, verbose=self.verbose)

@@ -807,6 +807,64 @@ __global__ void k_ei(const double* __restrict__ mu, const double* __restrict__ v
   out[i] = mode ? (log_ei_helper(u) + log(sigma)) : (ei_helper(u) * sigma);
 }
 
+// k_ei with its input gradient, from predict_grad's chain (mu, var: n; dmu, dvar: n x d, standardised units).  One thread per
+// point: the point's scalars once - the value by k_ei's statements on k_ei's device functions -, then its d coordinates.
+// sigma = sqrt(max(var, lo)), dsigma = dvar / (2 sigma), and 0 where var was clipped; u = (mu - zeta - best_y) / sigma.
+//   EI:    grad = Phi(u) dmu + phi(u) dsigma
+//   LogEI: grad = A dmu + B dsigma, A = Phi / (sigma h), B = phi / (sigma h), h = phi + u Phi; directly for u > -1.  At and
+//          below (log_ei_helper's own bound; Phi / h turns into 0 / 0 near u = -38) through the Mills ratio
+//          R = Phi / phi = sqrt(pi / 2) erfcx(-u / sqrt 2):  g = h / phi = 1 - |u| R,  B = 1 / (sigma g),  A = R B.
+//          1 - |u| R cancels to ~1 / u^2, so from |u| = 30 on g is its asymptotic series
+//          1/u^2 - 3/u^4 + 15/u^6 - ... (nine terms: the ninth is 8e-17 of the first at |u| = 30), and the difference itself
+//          only below, where it loses at most log10(900) ~ 3 of the 16 digits.  (log h is NOT taken from log_ei_helper here:
+//          its log1mexp(w), w -> -1 / u^2, carries an absolute error ~1e-16 u^2 - invisible beside the value's u^2 / 2,
+//          but 1e-9 of B at u = -4500 and 1e-4 at u = -1e6, where a floored point one unit below the target sits.)
+// A gated point (mu = -inf, k_gate's mark) has the value of (minus_inf, 1e-12) and a gradient of exactly 0.
+__global__ __launch_bounds__(256) void k_ei_grad(const double* __restrict__ mu, const double* __restrict__ var,
+                                                 const double* __restrict__ dmu, const double* __restrict__ dvar, int64_t n,
+                                                 int d, double best_y, double zeta, int mode, double minus_inf,
+                                                 double* __restrict__ val, double* __restrict__ grad) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  double v = var[c];
+  const double lo = mode ? 1e-18 : 1e-20;
+  const bool clipped = v < lo;
+  if (v < lo) v = lo;
+  const double sigma = sqrt(v);
+  double m = mu[c];
+  const bool gated = m == -INFINITY;
+  if (m == -INFINITY) m = minus_inf;
+  const double u = (m - zeta - best_y) / sigma;
+  val[c] = mode ? (log_ei_helper(u) + log(sigma)) : (ei_helper(u) * sigma);
+  double a = 0.0, b = 0.0;
+  if (gated) {
+    // (a = b = 0)
+  } else if (!mode) {
+    a = norm_cdf(u);
+    b = norm_pdf(u);
+  } else if (u > -1.0) {
+    const double sh = sigma * ei_helper(u);
+    a = norm_cdf(u) / sh;
+    b = norm_pdf(u) / sh;
+  } else {
+    const double x = -u, r = 1.25331413731550025121 * erfcx(0.70710678118654752440 * x);
+    double g;
+    if (x < 30.0) {
+      g = 1.0 - x * r;
+    } else {
+      const double t = 1.0 / (x * x);
+      g = t * (1.0 - t * (3.0 - t * (15.0 - t * (105.0 - t * (945.0 - t * (10395.0 - t * (135135.0 - t * (2027025.0 - t * 34459425.0))))))));
+    }
+    b = 1.0 / (sigma * g);
+    a = r * b;
+  }
+  for (int j = 0; j < d; ++j) {
+    const int64_t i = c * d + j;
+    const double ds = clipped ? 0.0 : dvar[i] / (2.0 * sigma);
+    grad[i] = gated ? 0.0 : a * dmu[i] + b * ds;
+  }
+}
+
 // ---- training of the ellipsoid classifier (clf.py:415-472): every restart's whole AdamW run in ONE launch ----------
 // One 256-thread workgroup = one restart (blockIdx.x).  Parameters theta = [flat_L (T = d(d+1)/2, tril_indices order:
 // (0,0), (1,0), (1,1), (2,0), ...), alpha, beta], P = T + 2 <= 530: thread t owns theta[t], theta[t + 256], theta[t + 512]

@@ -523,6 +523,15 @@ int bobe_gp_acq_ei(bobe_gp_t* g, const double* Xq, int64_t C, double best_y, dou
   API_END
 }
 
+int bobe_gp_acq_ei_grad(bobe_gp_t* g, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* val,
+                        double* grad) {
+  API_BEGIN
+  NEED(g && Xq && val && grad, "NULL argument");
+  g->acq_ei_grad(Xq, C, best_y, zeta, mode, val, grad);
+  return BOBE_OK;
+  API_END
+}
+
 int bobe_gp_predict_grad(bobe_gp_t* g, const double* Xq, int64_t C, double* mean, double* var, double* dmean,
                          double* dvar) {
   API_BEGIN

@@ -156,6 +156,33 @@ void bobe_gp::acq_ei(const double* Xq, int64_t C, double best_y, double zeta, in
   sync();
 }
 
+void bobe_gp::acq_ei_grad(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* val, double* grad) {
+  if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");
+  if (C <= 0) throw Err(BOBE_ERR_ARG, "C must be positive");
+  if (mode != 0 && mode != 1) throw Err(BOBE_ERR_ARG, "mode must be 0 (EI) or 1 (LogEI)");
+  use();
+  const size_t cd = (size_t)C * d;
+  const double* cin = fetch(Xq, cd, in_stage);
+  // the posterior and its gradients stay in the staging buffers predict_grad copies home from; host outputs are staged in
+  // o_misc, the value in front of the gradient
+  o_mean.ensure((size_t)C * sizeof(double));
+  o_var.ensure((size_t)C * sizeof(double));
+  o_wipv.ensure(cd * sizeof(double));
+  o_wipstd.ensure(cd * sizeof(double));
+  const bool val_dev = is_device_ptr(val), grad_dev = is_device_ptr(grad);
+  if (!val_dev || !grad_dev) o_misc.ensure(((size_t)C + cd) * sizeof(double));
+  predict_grad_chain(cin, C, o_mean.d(), o_var.d(), o_wipv.d(), o_wipstd.d());
+  double* d_val = val_dev ? val : o_misc.d();
+  double* d_grad = grad_dev ? grad : o_misc.d() + C;
+  hipLaunchKernelGGL(k_ei_grad, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, (const double*)o_mean.d(),
+                     (const double*)o_var.d(), (const double*)o_wipv.d(), (const double*)o_wipstd.d(), C, d, best_y, zeta,
+                     mode, gate.minus_inf, d_val, d_grad);
+  LAUNCH_CHECK();
+  if (!val_dev) HIPCHK(hipMemcpyAsync(val, d_val, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (!grad_dev) HIPCHK(hipMemcpyAsync(grad, d_grad, cd * sizeof(double), hipMemcpyDeviceToHost, stream));
+  sync();
+}
+
 void bobe_gp::hmc_leapfrog(int64_t P, double* U, double* Pm, const double* inv_mass, double eps, int L, double y_std,
                            double y_mean, double temp, double* logp, double* grad, double* mean, double* X) {
   if (!factored) throw Err(BOBE_ERR_STATE, "call bobe_gp_factor first");

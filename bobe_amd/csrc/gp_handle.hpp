@@ -733,6 +733,9 @@ struct bobe_gp {
   void wg_front(const double* cfirst, double* cdev, int64_t C, double* kc, double* vv, double* uu, double* t1, double* t2,
                 double* t3);
   void predict_grad(const double* Xq, int64_t C, double* mean, double* var, double* dmean, double* dvar);
+  // predict_grad's full-mode launches, the gate included, on device pointers (cin: C x d; d_mean may be null): nothing is
+  // copied home and nothing waits for the stream - what predict_grad and acq_ei_grad share
+  void predict_grad_chain(const double* cin, int64_t C, double* d_mean, double* d_var, double* d_dm, double* d_dv);
   int append(const double* X_new, int64_t b, const double* y_all);
 
   // ---- gp_posterior.hip (call-local buffers only; the factorisation of Sigma runs on a data-less child handle)
@@ -809,6 +812,8 @@ struct bobe_gp {
 
   // ---- gp_consumers.hip
   void acq_ei(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);
+  // +EI / +logEI and their input gradients: predict_grad_chain into the o_* staging buffers, then k_ei_grad; one sync
+  void acq_ei_grad(const double* Xq, int64_t C, double best_y, double zeta, int mode, double* val, double* grad);
   void hmc_leapfrog(int64_t P, double* U, double* Pm, const double* inv_mass, double eps, int L, double y_std,
                     double y_mean, double temp, double* logp, double* grad, double* mean, double* X);
   void hmc_run(int64_t P, double* state, double* adapt, const double* inv_mass, uint64_t seed, int64_t it0, int niter,

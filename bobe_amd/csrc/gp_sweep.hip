@@ -463,7 +463,6 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
   if (C <= 0) throw Err(BOBE_ERR_ARG, "C must be positive");
   use();
   const int64_t CH = std::min<int64_t>(chunk, 2048);
-  const double kself = hyp.kvar + hyp.noise;
   const double* cin = fetch(Xq, (size_t)C * d, in_stage);
   if (!dvar) {
     // mean-only mode (HMC on the surrogate): scale the queries, then one kernel that walks the training points
@@ -490,6 +489,21 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
     sync();
     return;
   }
+  double* d_mean = out_dev(mean, C, o_mean);
+  double* d_var = out_dev(var, C, o_var);
+  double* d_dm = out_dev(dmean, (size_t)C * d, o_wipv);
+  double* d_dv = out_dev(dvar, (size_t)C * d, o_wipstd);
+  predict_grad_chain(cin, C, d_mean, d_var, d_dm, d_dv);
+  out_finish(mean, C, o_mean);
+  out_finish(var, C, o_var);
+  out_finish(dmean, (size_t)C * d, o_wipv);
+  out_finish(dvar, (size_t)C * d, o_wipstd);
+  sync();
+}
+
+void bobe_gp::predict_grad_chain(const double* cin, int64_t C, double* d_mean, double* d_var, double* d_dm, double* d_dv) {
+  const int64_t CH = std::min<int64_t>(chunk, 2048);
+  const double kself = hyp.kvar + hyp.noise;
   CsT.ensure((size_t)d * std::max<int64_t>(CH, chunk) * sizeof(double));
   kXC.ensure((size_t)Np * std::max<int64_t>(CH, chunk) * sizeof(double));
   forget_z();                                      // (VZ / WZ double as this call's scratch)
@@ -498,10 +512,6 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
   qpart.ensure((size_t)nb * std::max<int64_t>(CH, chunk) * sizeof(double));
   part.ensure((size_t)nb * std::max<int64_t>(Np, std::max<int64_t>(CH, chunk)) * sizeof(double));
   sc.ensure((size_t)std::max<int64_t>(CH, chunk) * sizeof(double));
-  double* d_mean = out_dev(mean, C, o_mean);
-  double* d_var = out_dev(var, C, o_var);
-  double* d_dm = out_dev(dmean, (size_t)C * d, o_wipv);
-  double* d_dv = out_dev(dvar, (size_t)C * d, o_wipstd);
   for (int64_t c0 = 0; c0 < C; c0 += CH) {
     const int64_t nc = std::min<int64_t>(CH, C - c0), ncp = round_up(nc, TILE);
     scale(cin + c0 * d, nc, ncp, hyp, CsT.d(), CH);
@@ -526,11 +536,6 @@ void bobe_gp::predict_grad(const double* Xq, int64_t C, double* mean, double* va
     LAUNCH_CHECK();
   }
   if (gate_on(gate)) gate_apply(cin, C, nullptr, nullptr, d_mean, d_var, d_dm, d_dv);
-  out_finish(mean, C, o_mean);
-  out_finish(var, C, o_var);
-  out_finish(dmean, (size_t)C * d, o_wipv);
-  out_finish(dvar, (size_t)C * d, o_wipstd);
-  sync();
 }
 
 int bobe_gp::append(const double* X_new, int64_t b, const double* y_all) {

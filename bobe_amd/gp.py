@@ -1036,6 +1036,18 @@ class GP:
                                             1 if log_ei else 0, _lib.ptr(out)), "bobe_gp_acq_ei")
         return out
 
+    def acq_ei_grad(self, x, best_y, zeta=0.0, log_ei=False):
+        """(val (C,), grad (C, d)): +EI / +log EI at the rows of x with their input gradients, standardised units like
+        ``acq_ei`` - one device call (``bobe_gp_acq_ei_grad``: ``predict_grad``'s chain and one kernel behind it, value and
+        gradient from the same posterior).  A point's row does not depend on the rest of the batch; under a classifier gate
+        an infeasible point has ``acq_ei``'s value and a zero gradient."""
+        x = _lib.as_f64(np.atleast_2d(x))
+        c = x.shape[0]
+        val, grad = np.empty(c), np.empty((c, self.ndim))
+        _lib.check(self._lib.bobe_gp_acq_ei_grad(self._h, _lib.ptr(x), c, float(best_y), float(zeta), 1 if log_ei else 0,
+                                                 _lib.ptr(val), _lib.ptr(grad)), "bobe_gp_acq_ei_grad")
+        return val, grad
+
     def wip_grad(self, candidates, mc_points):
         """(wipv, wipstd, dwipv/dx, dwipstd/dx) of the candidates — values and input gradients of ``WIPV.fun`` /
         ``WIPStd.fun`` (acquisition.py:438-465), the gradient being what the reference takes with ``jax.grad`` in the

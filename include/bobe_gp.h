@@ -459,6 +459,23 @@ void bobe_gp_paths_destroy(bobe_paths_t* p);
  * +log EI (mode 1); best_y, zeta in standardised units. */
 int bobe_gp_acq_ei(bobe_gp_t* gp, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* out);
 
+/* The same scores with their input gradients, for C points in one call: val[c] = +EI (mode 0) or +log EI (mode 1) and
+ * grad (C x d) = d val / d x, standardised units like bobe_gp_acq_ei; Xq, val, grad: host or device pointers.  The call runs
+ * bobe_gp_predict_grad's full chain (mean m, variance v, dm, dv stay on the device) and one elementwise kernel behind it, with
+ * one stream synchronisation at the end; value and gradient come from the same (m, v).  Per point, with lo = 1e-18 (LogEI) /
+ * 1e-20 (EI): sigma = sqrt(max(v, lo)), dsigma = dv / (2 sigma) and exactly 0 where v < lo (dv arrives as 0 on the 1e-12
+ * floor), u = (m - zeta - best_y) / sigma, h = phi(u) + u Phi(u);
+ *   EI:    val = sigma h,                grad = Phi(u) dm + phi(u) dsigma
+ *   LogEI: val = log h + log sigma (the reference's _log_ei_helper, as bobe_gp_acq_ei), grad = A dm + B dsigma with
+ *          A = Phi / (sigma h), B = phi / (sigma h) for u > -1; for u <= -1, with the Mills ratio R = Phi / phi =
+ *          sqrt(pi / 2) erfcx(-u / sqrt 2) and g = h / phi = 1 - |u| R (its series 1/u^2 - 3/u^4 + ... from |u| = 30 on),
+ *          B = 1 / (sigma g) and A = R B, which stay finite where Phi / h is 0 / 0 (u < -38) and accurate at any |u|.
+ * Under a classifier gate an infeasible point has the value of (m = minus_inf, v = 1e-12), like bobe_gp_acq_ei, and a
+ * gradient of exactly 0.  A point's outputs do not depend on the rest of its batch.  C <= 0 or mode outside {0, 1}:
+ * BOBE_ERR_ARG; a handle that was not factorised: BOBE_ERR_STATE. */
+int bobe_gp_acq_ei_grad(bobe_gp_t* gp, const double* Xq, int64_t C, double best_y, double zeta, int mode, double* val,
+                        double* grad);
+
 /* Input gradients of GP.predict_single (gp.py:476-489) — what the reference obtains by differentiating through
  * the GP with JAX (EI restarts acquisition.py:246-253/281-290; NUTS on predict_mean_batched samplers.py:268-276).
  * mean, var (may be NULL): as bobe_gp_predict with nan_policy 1.  dmean, dvar: C x d, derivatives with respect
