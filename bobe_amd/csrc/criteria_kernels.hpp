@@ -1,5 +1,6 @@
 // Kernels of the importance-weighted scoring pass (bobe_gp_wip_sweep_w, bobe_gp_wip_select_batch_w) and of the scores' input
-// gradients (bobe_gp_wip_grad_w, at the end of the file); gfx950.  Included by gp_criteria.hip only.
+// gradients (bobe_gp_wip_grad_w, at the end of the file); gfx950.  Included by gp_criteria.hip only.  (The gradients' chain
+// takes its rows stage and its cross kernel's front from wg_kernels.hpp, as bobe_gp_wip_grad's does.)
 //
 // The sweep scores candidate c against integration point z through the fantasy variance v+(z|c) (k_wip_score,
 // sweep_kernels.hpp).  Here every z also carries a log-weight l_z (the log of its quadrature weight under the flat prior on
@@ -17,6 +18,7 @@
 // returns NaN (exp(-inf - (-inf))), as it does for two +inf terms - the NaN marks an input outside the contract.
 #pragma once
 #include "kernels_common.hpp"
+#include "wg_kernels.hpp"
 
 namespace bobe {
 
@@ -355,18 +357,18 @@ __global__ __launch_bounds__(256) void k_wip_score_w(const double* __restrict__ 
 }
 
 // ---- input gradients of the four scores for a HANDFUL of candidates (bobe_gp_wip_grad_w) ---------------------------------
-// The few-candidate chain of bobe_gp_wip_grad (sweep_kernels.hpp, "the same for a HANDFUL of candidates") with one stage more.
+// The few-candidate chain of bobe_gp_wip_grad (sweep_kernels.hpp, "the same for a HANDFUL of candidates") with one stage more;
+// the front of the cross kernel and the rows stage are that chain's own (wg_kernels.hpp).
 // Each score is a function of the v+_z alone, so d score_k / dx_j = sum_z rho^k_z d v+_z / dx_j with
 //   rho^0 = omega_z        rho^1 = omega_z / (2 sqrt(v+))        rho^3 = exp(e_z - v+ + eiv)
 //   rho^2 = exp(t_z - imiqr) coth(x) u / (2 sqrt(v+)),  t_z = a_z + x + log1p(-e^{-2x}),  x = u sqrt(v+)
 // The two softmax weights need the candidate's FINISHED log-sum-exp over all z (exponents reach 1e5 at y_std ~ 4e3: only
 // exp(t - LSE) <= 1 is ever formed), which the single pass of k_wg_cross cannot supply: it forms the weights while it forms v+.
 // So k_wg_cross_w stops at cross_z, v+_z, the floored flag and one (maximum, sum) pair per workgroup, k_wg_weights_w folds
-// the pairs, forms rho^k w1 (w1 = d v+ / d cross, w2 = d v+ / d s: k_wg_cross's) and the z-side sums, k_wg_rows_w contracts
+// the pairs, forms rho^k w1 (w1 = d v+ / d cross, w2 = d v+ / d s: k_wg_cross's) and the z-side sums, k_wg_rows contracts
 // q = W_Z (rho^k w1) with T[j][n] for every requested criterion in one read of W_Z, k_wg_final_w combines.  A floored z is a
 // constant: it contributes its value and no gradient.  No atomics, every sum in a fixed order that depends on the
 // candidate alone - not on C, its place in the group, the pointer kinds or the other criteria requested.
-constexpr int WGW_ROWS = 4;                 // training points per k_wg_rows_w workgroup (k_wg_rows' WG_ROWS)
 constexpr int WGW_ZS = 2 + MAX_D;           // doubles per (candidate, criterion) of k_wg_weights_w: sum rho w2, the score, Dz[j]
 
 struct WgwOut {
@@ -374,8 +376,7 @@ struct WgwOut {
   double* grad[4];
 };
 
-// k_wg_cross up to the per-z quantities: one workgroup = 64 integration points (lane) x 4 interleaved quarters of the
-// training points (wave), v in LDS, eight rows in flight.  Writes cross_z, v+_z (floored, times y_std^2) and the floored flag
+// k_wg_cross up to the per-z quantities (wg_cross_front, wg_vplus).  Writes cross_z, v+_z (floored, times y_std^2) and the floored flag
 // (padding: 0, 0, 1), s_c (workgroup 0), and - mask bits 2 / 3 - the workgroup's (maximum, sum of exp(t - maximum)) of the
 // IMIQR / EIV terms into pairs[(c * gridDim.x + blockIdx.x) * 4 + {0, 1} / {2, 3}]; a workgroup without a point: (-inf, 0).
 template <int KERN, int DCAP>
@@ -389,38 +390,12 @@ __global__ __launch_bounds__(256) void k_wg_cross_w(const double* __restrict__ Z
                                                     double* __restrict__ pairs) {
   extern __shared__ double kcs[];                 // [n]: v = L^-1 k_c
   __shared__ double red[4], redz[4][64], fold[256];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t c = blockIdx.y;
-  v += c * np;
-  double sq = 0.0;
-  for (int64_t i = t; i < n; i += 256) {
-    const double vi = v[i];
-    kcs[i] = vi;
-    sq += vi * vi;
-  }
-  sq = wave_sum(sq);
-  if (lane == 0) red[wave] = sq;
-  __syncthreads();
-  const double s = kself - ((red[0] + red[1]) + (red[2] + red[3]));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t c = blockIdx.y, z = (int64_t)blockIdx.x * 64 + lane;
+  double wk;
+  const double s = wg_cross_front(v + c * np, n, VZ, ldw, z, kself, kcs, red, redz, wk);
   const bool sbad = !(s >= 0.0);
-  const int64_t z = (int64_t)blockIdx.x * 64 + lane;
-  double acc = 0.0;
-  {
-    const double* wp = VZ + z;
-    int64_t i = wave;
-    for (; i + 28 < n; i += 32) {                 // eight rows in flight per thread
-      double w8[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) w8[q] = wp[(i + 4 * q) * ldw];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc = __builtin_fma(w8[q], kcs[i + 4 * q], acc);
-    }
-    for (; i < n; i += 4) acc = __builtin_fma(wp[i * ldw], kcs[i], acc);
-  }
-  redz[wave][lane] = acc;
-  __syncthreads();
   if (wave != 0 && !(mask & 12)) return;          // (uniform per wave; the two maxima below are folded by the whole workgroup)
-  const double wk = (redz[0][lane] + redz[1][lane]) + (redz[2][lane] + redz[3][lane]);
   double cross = 0.0, vs = 0.0, fl = 1.0, ti = -INFINITY, te = -INFINITY;
   if (wave == 0 && z < m) {
     double r2 = 0.0;
@@ -429,14 +404,10 @@ __global__ __launch_bounds__(256) void k_wg_cross_w(const double* __restrict__ Z
       const double dz = (j < h.d) ? ZsT[j * ldz + z] - cand[c * h.d + j] / h.ls[j] : 0.0;
       r2 += dz * dz;
     }
-    cross = kern_eval<KERN>(r2, h.kvar) - wk;
-    double vp = basez[z] - (cross * cross) / s;
-    bool floored = sbad;
-    if (vp != vp) floored = true;
-    if (vp < NOISE_FLOOR) floored = true;
-    if (floored) vp = NOISE_FLOOR;
-    vs = vp * ystd2;
-    fl = floored ? 1.0 : 0.0;
+    const WgVplus f = wg_vplus(kern_eval<KERN>(r2, h.kvar), wk, s, sbad, basez[z]);
+    cross = f.cross;
+    vs = f.vp * ystd2;
+    fl = f.floored ? 1.0 : 0.0;
     if (mask & 4) {
       const double x = IMIQR_U * sqrt(vs);
       ti = zt[ldt + z] + x + log1p(-exp(-2.0 * x));
@@ -597,64 +568,7 @@ __global__ __launch_bounds__(256) void k_wg_weights_w(const double* __restrict__
   }
 }
 
-// k_wg_rows for NV weight vectors (1 .. 4) instead of the fixed pair: one workgroup = WGW_ROWS training points, one per wave;
-// lanes run over the integration points, and W_Z's row is read once whatever NV is.  partN[(c * gridDim.x + blockIdx.x) *
-// (NV + 1) * MAX_D + r * MAX_D + j]: r < NV the n-side sum Q_r[j] = sum_n q_r[n] T[j][n], r = NV ds[j] = sum_n u_n T[j][n].
-template <int KERN, int DCAP, int NV>
-__global__ __launch_bounds__(256) void k_wg_rows_w(const double* __restrict__ XsT, int64_t ldx, int64_t n, int64_t np,
-                                                   const double* __restrict__ cand, Hyper h,
-                                                   const double* __restrict__ W, int64_t ldw, int64_t mp,
-                                                   const double* __restrict__ wv, int64_t lda, int64_t ctot,
-                                                   const double* __restrict__ u, double* __restrict__ partN) {
-  __shared__ double red[4][NV + 1][DCAP];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t c = blockIdx.y;
-  u += c * np;
-  const double xl = (lane < h.d) ? cand[c * h.d + lane] / h.ls[lane] : 0.0;      // this lane's coordinate (lane = j)
-  double xc[DCAP];
-#pragma unroll
-  for (int j = 0; j < DCAP; ++j) xc[j] = (j < h.d) ? cand[c * h.d + j] / h.ls[j] : 0.0;
-  double aq[NV], au = 0.0;
-#pragma unroll
-  for (int r = 0; r < NV; ++r) aq[r] = 0.0;
-  const int64_t i = (int64_t)blockIdx.x * WGW_ROWS + wave;
-  if (i < n) {                                    // uniform per wave
-    double q[NV];
-#pragma unroll
-    for (int r = 0; r < NV; ++r) q[r] = 0.0;
-    for (int64_t z = lane; z < mp; z += 64) {
-      const double w = W[i * ldw + z];
-#pragma unroll
-      for (int r = 0; r < NV; ++r) q[r] = __builtin_fma(wv[(r * ctot + c) * lda + z], w, q[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < NV; ++r) q[r] = chain_wave_sum(q[r]);
-    double r2 = 0.0;
-#pragma unroll
-    for (int j = 0; j < DCAP; ++j) {
-      const double df = (j < h.d) ? XsT[j * ldx + i] - xc[j] : 0.0;
-      r2 += df * df;
-    }
-    const double kv = kern_eval<KERN>(r2, h.kvar);
-    const double tj = (lane < h.d) ? kern_grad_factor<KERN>(r2, h.kvar, kv) * (XsT[lane * ldx + i] - xl) : 0.0;
-#pragma unroll
-    for (int r = 0; r < NV; ++r) aq[r] = __builtin_fma(q[r], tj, aq[r]);
-    au = __builtin_fma(u[i], tj, au);
-  }
-  if (lane < DCAP) {
-#pragma unroll
-    for (int r = 0; r < NV; ++r) red[wave][r][lane] = aq[r];
-    red[wave][NV][lane] = au;
-  }
-  __syncthreads();
-  if (t < (NV + 1) * DCAP) {
-    const int k = t / DCAP, j = t % DCAP;
-    partN[(c * gridDim.x + blockIdx.x) * (NV + 1) * MAX_D + k * MAX_D + j] =
-        (red[0][k][j] + red[1][k][j]) + (red[2][k][j] + red[3][k][j]);
-  }
-}
-
-// the n-side partials of k_wg_rows_w (nnw of them, nv + 1 rows each) and the z-side sums of k_wg_weights_w -> scores and
+// the n-side partials of k_wg_rows (nnw of them, nv + 1 rows each) and the z-side sums of k_wg_weights_w -> scores and
 // gradients of candidate blockIdx.x, in k_wg_final's order: thread (j = t & 31, part = t >> 5) adds the partials part,
 // part + 8, ... of coordinate j, the eight parts are combined in order.  The outputs of criterion k at out.score[k] + c0 + c,
 // out.grad[k] + (c0 + c) d (NULL: not written).
@@ -714,7 +628,7 @@ __global__ __launch_bounds__(256) void k_wg_final_w(const double* __restrict__ z
 //   d zvar / dx_j = sum_z rho_z d r_z / dx_j,   rho_z = -2 G_z / T_s,   d r_z / dx_j = w1 d cross_z / dx_j + w2_z d s / dx_j,
 //   w1 = y_std / sqrt(s),   w2_z = -r_z / (2 s)
 // - the chain above with other weights: wg_front and k_wg_cross_w (mask 1: cross_z and s_c, no log-sum-exp pairs) in front,
-// k_wg_rows_w<., ., 1> and k_wg_final_w (criterion slot 0) behind, and three stages in place of k_wg_weights_w:
+// k_wg_rows<., ., 1> and k_wg_final_w (criterion slot 0) behind, and three stages in place of k_wg_weights_w:
 //   k_wg_zv_r     per candidate: r_z under k_wip_score_zz::r_of's rules with the "constant" flag, h_c, p_z, E_z
 //   k_wg_zv_pair  the hot one, M^2 pairs per candidate: G_z and z's row t_z = sum_z' pair(z, z') of the pair sum
 //   k_wg_zv_fold  per candidate: T_s, the score, rho_z, rho w1 into wv and sum rho w2, D_z[j] into zs (k_wg_weights_w's layout)

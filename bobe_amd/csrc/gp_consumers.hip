@@ -440,7 +440,7 @@ void bobe_gp::release_all() {
   if (stream) (void)hipStreamSynchronize(stream);
   DBuf* bufs[] = {&X, &y, &XsT, &A, &Linv, &Tmp, &alpha, &w, &part, &gpart, &res, &info, &probs, &diag, &in_stage, &z_stage, &CsT, &ZsT, &kXC, &kXZ, &VZ, &WZ, &basez, &sc, &qpart, &pv,
                   &ps, &o_mean, &o_var, &o_wipv, &o_wipstd, &o_misc, &kin_a, &kin_b, &kout, &wg_ws, &gate_sv, &gate_dual, &gate_ell, &ell_ws, &ell_perm,
-                  &vxc, &vxc2, &loo_ws, &wgw_ws, &wgw_out, &zw.zt, &zw.zpart, &zw.lstage};
+                  &vxc, &vxc2, &loo_ws, &wg_out, &zw.zt, &zw.zpart, &zw.lstage};
   for (DBuf* b : bufs) b->release();
   for (auto& pr : prof_events) {
     (void)hipEventDestroy(pr.first);

@@ -115,7 +115,7 @@ int bobe_gp::wip_sweep_w(const double* cand, int64_t C, const double* Z, int64_t
 }
 
 // Values and input gradients of the four scores (criteria_kernels.hpp, "input gradients of the four scores").  Per group of up
-// to 16 candidates: wg_front (bobe_gp_wip_grad's first stages) -> k_wg_cross_w -> k_wg_weights_w -> k_wg_rows_w -> k_wg_final_w.
+// to 16 candidates: wg_front (bobe_gp_wip_grad's first stages) -> k_wg_cross_w -> k_wg_weights_w -> k_wg_rows -> k_wg_final_w.
 int bobe_gp::wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                         double* const scores[4], double* const grads[4]) {
   int mask = 0;
@@ -174,28 +174,22 @@ int bobe_gp::wip_grad_chain(const char* entry, const double* cand, int64_t C, co
   if (!mask)
     throw Err(BOBE_ERR_ARG, std::string(entry) + (zv ? ": no output requested (zvar and dzvar are NULL)"
                                                      : ": no criterion requested (every scores[k] and grads[k] is NULL)"));
-  if (N > WGW_MAX_N)
+  if (N > WG_MAX_N)
     throw Err(BOBE_ERR_ARG, std::string(entry) + ": " + std::to_string(N) + " training points exceed the matrix-vector chain's " +
-                                "limit of " + std::to_string(WGW_MAX_N) + " (there is no tile path)");
+                                "limit of " + std::to_string(WG_MAX_N) + " (there is no tile path)");
   use();
   const int64_t Mp = round_up(M, TILE), G = std::min<int64_t>(C, 16);
   const double kself = hyp.kvar + hyp.noise;
-  const bool cand_pinned = C <= 16 && !is_device_ptr(cand);
-  const double* cin = cand_pinned ? nullptr : fetch(cand, (size_t)C * d, in_stage);
+  const WgCand cc = wg_candidates(cand, C, C <= 16);
   prepare_z(Z, M, Mp, true);                             // ZsT, V_Z, W_Z, base_z (forget_z on a miss drops the table too)
   wip_grad_table(M, Mp, y_std, logw, zv);
-  const int nzw = (int)(Mp / 64), nnw = (int)((N + WGW_ROWS - 1) / WGW_ROWS);
+  const int nzw = (int)(Mp / 64), nnw = (int)((N + WG_ROWS - 1) / WG_ROWS);
   const size_t n_vec = (size_t)G * Np, n_a = (size_t)G * Mp;
   const size_t n_pn = (size_t)G * nnw * (nv + 1) * MAX_D;
-  wgw_ws.ensure((6 * n_vec + (3 + 4) * n_a + 16 + (size_t)G * nzw * 4 + (size_t)G * 4 * WGW_ZS + n_pn +
-                 (zv ? 6 * n_a + 16 : 0)) * sizeof(double));
-  double* kc = wgw_ws.d();
-  double* vv = kc + n_vec;
-  double* uu = vv + n_vec;
-  double* t1 = uu + n_vec;
-  double* t2 = t1 + n_vec;
-  double* t3 = t2 + n_vec;
-  double* crossA = t3 + n_vec;
+  wg_ws.ensure((6 * n_vec + (3 + 4) * n_a + 16 + (size_t)G * nzw * 4 + (size_t)G * 4 * WGW_ZS + n_pn +
+                (zv ? 6 * n_a + 16 : 0)) * sizeof(double));
+  const WgFront f(wg_ws.d(), n_vec);
+  double* crossA = f.end;
   double* vplusA = crossA + n_a;
   double* flagA = vplusA + n_a;
   double* wv = flagA + n_a;                         // [nv][G][Mp]
@@ -210,48 +204,21 @@ int bobe_gp::wip_grad_chain(const char* entry, const double* cand, int64_t C, co
   double* tA = constA + n_a;
   double* gA = tA + n_a;
   double* hA = gA + n_a;
-  // outputs: a device pointer is written directly; the host ones share one block, requested arrays back to back - the pinned
-  // result block (128 doubles, written by the last stage itself: no copy command) when there is no device output, one group
-  // and they fit, else a staged block that ONE copy brings back
-  size_t n_out = 0;
-  bool any_dev = false;
+  WgOut home(*this);
   WgwOut out;
-  size_t off_s[4] = {0, 0, 0, 0}, off_g[4] = {0, 0, 0, 0};
   for (int k = 0; k < 4; ++k) {
-    any_dev = any_dev || is_device_ptr(scores[k]) || is_device_ptr(grads[k]);
-    if (scores[k] && !is_device_ptr(scores[k])) { off_s[k] = n_out; n_out += (size_t)C; }
-    if (grads[k] && !is_device_ptr(grads[k])) { off_g[k] = n_out; n_out += (size_t)C * d; }
+    home.add(scores[k], (size_t)C, out.score[k]);
+    home.add(grads[k], (size_t)C * d, out.grad[k]);
   }
-  const bool packed = C <= 16 && n_out <= 128 && !any_dev;
-  double* base = h_res;
-  if (!packed && n_out) {
-    wgw_out.ensure(n_out * sizeof(double));
-    base = wgw_out.d();
-  }
-  for (int k = 0; k < 4; ++k) {
-    out.score[k] = !scores[k] ? nullptr : (is_device_ptr(scores[k]) ? scores[k] : base + off_s[k]);
-    out.grad[k] = !grads[k] ? nullptr : (is_device_ptr(grads[k]) ? grads[k] : base + off_g[k]);
-  }
+  home.place(C <= 16);
   const Hyper& h = hyp;
   for (int64_t c0 = 0; c0 < C; c0 += 16) {
     const int64_t g = std::min<int64_t>(16, C - c0);
-    double* cdev = nullptr;
-    const double* cfirst;
-    const double* clater;
-    if (cand_pinned) {                              // (one group: the pinned block is written once per call)
-      if (!h_in) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_in), 16 * MAX_D * sizeof(double), hipHostMallocDefault));
-      std::memcpy(h_in, cand, (size_t)C * d * sizeof(double));
-      in_stage.ensure((size_t)16 * MAX_D * sizeof(double));
-      cdev = in_stage.d();
-      cfirst = h_in;
-      clater = cdev;
-    } else {
-      cfirst = clater = cin + c0 * d;
-    }
-    wg_front(cfirst, cdev, g, kc, vv, uu, t1, t2, t3);
+    const double* clater = cc.later + c0 * d;
+    wg_front(cc, c0, g, f);
     with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
       hipLaunchKernelGGL((k_wg_cross_w<KE, DC>), dim3((unsigned)nzw, (unsigned)g), dim3(256), (size_t)N * sizeof(double),
-                         stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)vv, clater,
+                         stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)f.vv, clater,
                          h, kself, (const double*)basez.d(), y_std * y_std, (const double*)zw.zt.d(), zw.ldt, mask, crossA,
                          vplusA, flagA, Mp, sA, pairs);
       if (zv) {
@@ -270,9 +237,9 @@ int bobe_gp::wip_grad_chain(const char* entry, const double* cand, int64_t C, co
       }
       auto rows = [&](auto NV) {
         // (KE, DC are captured: their types carry the values)
-        hipLaunchKernelGGL((k_wg_rows_w<decltype(KE)::value, decltype(DC)::value, decltype(NV)::value>),
+        hipLaunchKernelGGL((k_wg_rows<decltype(KE)::value, decltype(DC)::value, decltype(NV)::value>),
                            dim3((unsigned)nnw, (unsigned)g), dim3(256), 0, stream, (const double*)XsT.d(), Np, N, Np, clater, h,
-                           (const double*)WZ.d(), Mp, Mp, (const double*)wv, Mp, G, (const double*)uu, pn);
+                           (const double*)WZ.d(), Mp, Mp, (const double*)wv, Mp, G, (const double*)f.uu, pn);
       };
       switch (nv) {
         case 1: rows(std::integral_constant<int, 1>{}); break;
@@ -285,18 +252,10 @@ int bobe_gp::wip_grad_chain(const char* entry, const double* cand, int64_t C, co
                        mask, h, c0, out);
     LAUNCH_CHECK();
   }
-  const double* hb = h_res;
-  if (!packed && n_out) {
-    wgw_host.resize(n_out);
-    HIPCHK(hipMemcpyAsync(wgw_host.data(), wgw_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, stream));
-    hb = wgw_host.data();
-  }
+  home.finish();
   if (log_ez) HIPCHK(hipMemcpyAsync(log_ez, zw.log_ez(), sizeof(double), hipMemcpyDefault, stream));
   sync();
-  for (int k = 0; k < 4; ++k) {
-    if (scores[k] && !is_device_ptr(scores[k])) std::memcpy(scores[k], hb + off_s[k], (size_t)C * sizeof(double));
-    if (grads[k] && !is_device_ptr(grads[k])) std::memcpy(grads[k], hb + off_g[k], (size_t)C * d * sizeof(double));
-  }
+  home.scatter();
   return BOBE_OK;
 }
 

@@ -2,7 +2,9 @@
 // libbobe_gp.so:
 //   gp_factor.hip     K(X,X) assembly, blocked Cholesky + launch plan, triangular inverse, alpha, MLL value / gradient
 //                     (single evaluation, evaluation slots, lock-step batch, graph replay), state restore
-//   gp_sweep.hip      prediction / acquisition sweep, score and posterior gradients, rank-b append
+//   gp_sweep.hip      prediction / acquisition sweep, score and posterior gradients, rank-b append.  (Its few-candidate
+//                     gradient chain and gp_criteria.hip's share wg_front, the device code of wg_kernels.hpp and the host
+//                     staging below: wg_candidates, WgFront, WgOut, WG_MAX_N.)
 //   gp_consumers.hip  HMC / NUTS / constrained random walks on the surrogate, EI / LogEI, the classifier gate, GP.kernel,
 //                     device clone.  (What its chain kernels share with gp_paths.hip's - the rows' homes, the one-point
 //                     evaluation, the HMC transition - is chain_common.hpp; the host staging of a chain call is ChainStage,
@@ -419,16 +421,17 @@ struct bobe_gp {
   DBuf X, y, XsT, A, Linv, Tmp, alpha, w, part, gpart, res, info, probs, diag;
   int num_cus = 0;
   // sweep / predict workspace
-  DBuf wg_ws;     // workspace of bobe_gp_wip_grad's few-candidates path
-  DBuf wgw_ws, wgw_out;   // workspace and staged outputs of bobe_gp_wip_grad_w / bobe_gp_wip_grad_zvar
-  std::vector<double> wgw_host;   // where the one copy of the staged outputs lands before they go to the caller's arrays
+  // the few-candidate chains (bobe_gp_wip_grad's few path, bobe_gp_wip_grad_w, bobe_gp_wip_grad_zvar): their workspace, their
+  // staged outputs and where the one copy of those lands before they go to the caller's arrays (WgOut)
+  DBuf wg_ws, wg_out;
+  std::vector<double> wg_host;
   DBuf in_stage, z_stage, CsT, ZsT, kXC, kXZ, VZ, WZ, basez, sc, qpart, pv, ps, o_mean, o_var, o_wipv, o_wipstd,
       o_misc, kin_a, kin_b, kout, vxc, vxc2;
   // the inverse's problem table (probs) by depth: whole levels, and their leading / trailing parts (tri_split.hpp)
   std::vector<bobe::Depth> depths, lead_depths, trail_depths;
   int tri_mid = 0;
   double* h_res = nullptr;  // pinned, 128 doubles
-  double* h_in = nullptr;   // pinned, 16 x MAX_D doubles: host coordinates of bobe_gp_wip_grad's few-candidate path
+  double* h_in = nullptr;   // pinned, 16 x MAX_D doubles: host coordinates of the few-candidate chains (wg_candidates)
 
   // ---- classifier gate (gp_consumers.hip): support vectors SoA + dual coefficients (SVM) or the transformed L and the
   // centre (ellipsoid) on the device
@@ -638,6 +641,81 @@ struct bobe_gp {
     HIPCHK(hipMemcpyAsync(user, stage.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
   }
 
+  // ---- what the few-candidate chains share on the host (wip_grad's few path in gp_sweep.hip, wip_grad_chain in gp_criteria.hip)
+  static constexpr int64_t WG_MAX_N = 4096;       // the chains' limit on N: the cross kernels keep v in N doubles of LDS
+  // The candidates of a call.  One group (C <= 16) of host coordinates goes through the pinned block h_in: the first stage
+  // reads them there (first) and leaves the device copy (dev) that the later stages read (later) - no copy command in front of
+  // the chain.  Anything else is fetch()'s: dev is null and first == later.
+  struct WgCand {
+    const double* first;
+    double* dev;
+    const double* later;
+  };
+  WgCand wg_candidates(const double* cand, int64_t C, bool one_group) {
+    if (!one_group || bobe::is_device_ptr(cand)) {
+      const double* cin = fetch(cand, (size_t)C * d, in_stage);
+      return {cin, nullptr, cin};
+    }
+    const size_t cap = (size_t)16 * bobe::MAX_D * sizeof(double);
+    if (!h_in) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_in), cap, hipHostMallocDefault));
+    std::memcpy(h_in, cand, (size_t)C * d * sizeof(double));
+    in_stage.ensure(cap);
+    return {h_in, in_stage.d(), in_stage.d()};
+  }
+  // wg_front's six vectors (k_c, v, u and the refinement step's three temporaries), n_vec doubles each, carved from p
+  struct WgFront {
+    double *kc, *vv, *uu, *t1, *t2, *t3, *end;      // end: what follows them
+    WgFront(double* p, size_t n_vec)
+        : kc(p), vv(kc + n_vec), uu(vv + n_vec), t1(uu + n_vec), t2(t1 + n_vec), t3(t2 + n_vec), end(t3 + n_vec) {}
+  };
+  // The outputs of a call.  A device pointer is written directly and NULL stays NULL (the last stage skips it); the requested
+  // HOST arrays share one block, back to back in the order they were added: the pinned result block h_res (128 doubles), which
+  // the last stage writes itself - no copy command -, when there is no device output, one group and they fit, else a staged
+  // block that ONE copy brings home.  add every output (dev receives its device pointer at place()), place, launch, finish
+  // (the copy command), sync, scatter (into the caller's arrays).
+  struct WgOut {
+    bobe_gp& g;
+    struct Item {
+      double* user;
+      double** dev;
+      size_t off, n;
+    } items[8];
+    int n_items = 0;
+    size_t n_host = 0;
+    bool any_dev = false, packed = false;
+    const double* home = nullptr;
+    explicit WgOut(bobe_gp& g_) : g(g_) {}
+    void add(double* user, size_t n, double*& dev) {
+      dev = user;
+      if (!user) return;
+      if (bobe::is_device_ptr(user)) {
+        any_dev = true;
+        return;
+      }
+      items[n_items++] = {user, &dev, n_host, n};
+      n_host += n;
+    }
+    void place(bool one_group) {
+      packed = one_group && n_host <= 128 && !any_dev;
+      double* base = g.h_res;
+      if (!packed && n_host) {
+        g.wg_out.ensure(n_host * sizeof(double));
+        base = g.wg_out.d();
+      }
+      for (int i = 0; i < n_items; ++i) *items[i].dev = base + items[i].off;
+      home = g.h_res;
+    }
+    void finish() {
+      if (packed || !n_host) return;
+      g.wg_host.resize(n_host);
+      HIPCHK(hipMemcpyAsync(g.wg_host.data(), g.wg_out.p, n_host * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+      home = g.wg_host.data();
+    }
+    void scatter() const {
+      for (int i = 0; i < n_items; ++i) std::memcpy(items[i].user, home + items[i].off, items[i].n * sizeof(double));
+    }
+  };
+
   // ---- gp_factor.hip
   void build_probs();
   void alloc_for_n();
@@ -729,9 +807,9 @@ struct bobe_gp {
   void sweep(const bobe::SweepReq& r);
   void wip_grad(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, double* wipv, double* wipstd,
                 double* dwipv, double* dwipstd);
-  // the front of the few-candidate chains: k_wg_col, solve_alpha and - refine_v - the vector refinement step
-  void wg_front(const double* cfirst, double* cdev, int64_t C, double* kc, double* vv, double* uu, double* t1, double* t2,
-                double* t3);
+  // the front of the few-candidate chains for the C candidates from c0 on: k_wg_col, solve_alpha and - refine_v - the vector
+  // refinement step
+  void wg_front(const WgCand& cc, int64_t c0, int64_t C, const WgFront& f);
   void predict_grad(const double* Xq, int64_t C, double* mean, double* var, double* dmean, double* dvar);
   // predict_grad's full-mode launches, the gate included, on device pointers (cin: C x d; d_mean may be null): nothing is
   // copied home and nothing waits for the stream - what predict_grad and acq_ei_grad share
@@ -794,8 +872,7 @@ struct bobe_gp {
                             int n_batch, int64_t* picks, double* pick_scores, double* stage_scores);
   int wip_select_batch_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                          int n_batch, int criterion, int64_t* picks, double* pick_scores, double* stage_scores);
-  // values and input gradients of the four scores through the few-candidate chain, in groups of 16 (WGW_MAX_N: its limit on N)
-  static constexpr int64_t WGW_MAX_N = 4096;      // (k_wg_cross_w keeps v in N doubles of LDS)
+  // values and input gradients of the four scores through the few-candidate chain, in groups of 16 (WG_MAX_N: its limit on N)
   int wip_grad_w(const double* cand, int64_t C, const double* Z, int64_t M, double y_std, const double* logw,
                  double* const scores[4], double* const grads[4]);
   // value and input gradient of the evidence-variance score through the same chain, the same limit on N

@@ -321,18 +321,19 @@ void bobe_gp::sweep(const SweepReq& r) {
   }
 }
 
-// The front of the few-candidate chains (bobe_gp_wip_grad, bobe_gp_wip_grad_w): k_c = k(X, c) into kc (cfirst may be pinned
-// host memory; cdev then receives the device copy of the coordinates), v = Linv k_c, u = Linv^T v and - refine_v - one step of
-// iterative refinement in vector form.  C vectors of Np each; t1 .. t3: the refinement's temporaries.
-void bobe_gp::wg_front(const double* cfirst, double* cdev, int64_t C, double* kc, double* vv, double* uu, double* t1,
-                       double* t2, double* t3) {
+// The front of the few-candidate chains (bobe_gp_wip_grad, bobe_gp_wip_grad_w, bobe_gp_wip_grad_zvar) for candidates c0 ..
+// c0 + C: k_c = k(X, c) into f.kc (cc.first may be pinned host memory; cc.dev then receives the device copy of the
+// coordinates), v = Linv k_c, u = Linv^T v and - refine_v - one step of iterative refinement in vector form.  C vectors of Np
+// each; f.t1 .. f.t3: the refinement's temporaries.
+void bobe_gp::wg_front(const WgCand& cc, int64_t c0, int64_t C, const WgFront& f) {
   const Hyper& h = hyp;
   const size_t n_vec = (size_t)C * Np;
+  double *kc = f.kc, *vv = f.vv, *uu = f.uu, *t1 = f.t1, *t2 = f.t2, *t3 = f.t3;
   part.ensure((size_t)C * nb * Np * sizeof(double));
   const double* li = Linv.d();
   with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
     hipLaunchKernelGGL((k_wg_col<KE, DC>), dim3((unsigned)(Np / 256 + 1), (unsigned)C), dim3(256), 0, stream,
-                       (const double*)XsT.d(), Np, N, Np, cfirst, h, kc, cdev);
+                       (const double*)XsT.d(), Np, N, Np, cc.first + c0 * d, h, kc, cc.dev);
   });
   solve_alpha(li, vv, uu, part.d(), (int)C, 0, Np, (int64_t)nb * Np, (const double*)kc, Np);
   if (refine_v) {   // one step of iterative refinement in vector form: v += Linv (k - L v), u += Linv^T of the same
@@ -356,10 +357,9 @@ void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M
   use();
   const int64_t Mp = round_up(M, TILE), CH = std::min<int64_t>(chunk, 1024);
   const double kself = hyp.kvar + hyp.noise;
-  const bool few_path = C <= 16 && N <= 4096;
-  // (the few-candidate path reads host coordinates through the pinned block h_in: no copy command in front of its chain)
-  const bool cand_pinned = few_path && !is_device_ptr(cand);
-  const double* cin = cand_pinned ? nullptr : fetch(cand, (size_t)C * d, in_stage);
+  const bool few_path = C <= 16 && N <= WG_MAX_N;
+  const WgCand cc = wg_candidates(cand, C, few_path);
+  const double* cin = cc.later;
   prepare_z(Z, M, Mp, true);                             // ZsT, V_Z, W_Z = K^-1 K(X,Z), base_z
   CsT.ensure((size_t)d * std::max<int64_t>(CH, chunk) * sizeof(double));
   kXC.ensure((size_t)Np * std::max<int64_t>(CH, chunk) * sizeof(double));
@@ -367,72 +367,45 @@ void bobe_gp::wip_grad(const double* cand, int64_t C, const double* Z, int64_t M
   ps.ensure((size_t)Np * CH * sizeof(double));           // U = K^-1 k_c
   qpart.ensure((size_t)nb * std::max<int64_t>(std::max<int64_t>(CH, chunk), Mp) * sizeof(double));
   sc.ensure((size_t)std::max<int64_t>(CH, chunk) * sizeof(double));
-  double* d_v = out_dev(wipv, C, o_wipv);
-  double* d_s = out_dev(wipstd, C, o_wipstd);
-  double* d_dv = out_dev(dwipv, (size_t)C * d, o_mean);
-  double* d_ds = out_dev(dwipstd, (size_t)C * d, o_var);
   if (few_path) {
-    double* cdev = nullptr;                        // device copy of pinned-host coordinates, written by the first stage
-    if (cand_pinned) {
-      if (!h_in) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_in), 16 * MAX_D * sizeof(double), hipHostMallocDefault));
-      std::memcpy(h_in, cand, (size_t)C * d * sizeof(double));
-      in_stage.ensure((size_t)16 * MAX_D * sizeof(double));
-      cdev = in_stage.d();
-    }
-    const double* cfirst = cand_pinned ? (const double*)h_in : cin;   // what the first stage reads
-    if (cand_pinned) cin = cdev;                                      // what the later stages read
     // A handful of candidates (the L-BFGS refinement sends one): matrix-vector stages spread over the chip instead of
     // 128-column tile passes and one workgroup per candidate (kernels.hpp, "the same for a HANDFUL of candidates").
     const int nzw = (int)(Mp / 64), nnw = (int)((N + WG_ROWS - 1) / WG_ROWS);
     const size_t n_vec = (size_t)C * Np, n_a = (size_t)C * Mp;
-    wg_ws.ensure((6 * n_vec + 2 * n_a + (size_t)C * nzw * WG_ZS + (size_t)C * nnw * WG_NS) * sizeof(double));
-    part.ensure((size_t)C * nb * Np * sizeof(double));
-    double* kc = wg_ws.d();
-    double* vv = kc + n_vec;
-    double* uu = vv + n_vec;
-    double* a1 = uu + n_vec;
-    double* b1 = a1 + n_a;
-    double* pz = b1 + n_a;
+    wg_ws.ensure((6 * n_vec + 2 * n_a + (size_t)C * nzw * WG_ZS + (size_t)C * nnw * 3 * MAX_D) * sizeof(double));
+    const WgFront f(wg_ws.d(), n_vec);
+    double* a1 = f.end;                            // the two weight vectors [2][C][Mp]: k_wg_rows' wv
+    double* pz = a1 + 2 * n_a;
     double* pn = pz + (size_t)C * nzw * WG_ZS;
-    double* t1 = pn + (size_t)C * nnw * WG_NS;     // three more vectors per candidate: the refinement step's temporaries
-    double* t2 = t1 + n_vec;
-    double* t3 = t2 + n_vec;
+    WgOut out(*this);
+    double *d_v, *d_s, *d_dv, *d_ds;
+    out.add(wipv, (size_t)C, d_v);
+    out.add(wipstd, (size_t)C, d_s);
+    out.add(dwipv, (size_t)C * d, d_dv);
+    out.add(dwipstd, (size_t)C * d, d_ds);
+    out.place(true);
     const Hyper& h = hyp;
-    wg_front(cfirst, cdev, C, kc, vv, uu, t1, t2, t3);
+    wg_front(cc, 0, C, f);
     with_kern_dcap(h.kern, d, [&](auto KE, auto DC) {
       hipLaunchKernelGGL((k_wg_cross<KE, DC>), dim3((unsigned)nzw, (unsigned)C), dim3(256), (size_t)N * sizeof(double),
-                         stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)kc,
-                         (const double*)vv, cin, h, kself, (const double*)basez.d(), y_std * y_std, a1, b1, Mp, pz);
-      hipLaunchKernelGGL((k_wg_rows<KE, DC>), dim3((unsigned)nnw, (unsigned)C), dim3(256), 0, stream,
-                         (const double*)XsT.d(), Np, N, Np, cin, h, (const double*)WZ.d(), Mp, Mp, (const double*)a1,
-                         (const double*)b1, Mp, (const double*)uu, pn);
+                         stream, (const double*)ZsT.d(), Mp, M, (const double*)VZ.d(), Mp, N, Np, (const double*)f.kc,
+                         (const double*)f.vv, cin, h, kself, (const double*)basez.d(), y_std * y_std, a1, a1 + n_a, Mp, pz);
+      hipLaunchKernelGGL((k_wg_rows<KE, DC, 2>), dim3((unsigned)nnw, (unsigned)C), dim3(256), 0, stream,
+                         (const double*)XsT.d(), Np, N, Np, cin, h, (const double*)WZ.d(), Mp, Mp, (const double*)a1, Mp, C,
+                         (const double*)f.uu, pn);
     });
-    const size_t n_out = (size_t)C * (2 + 2 * d);
-    const bool packed = n_out <= 96 && !(wipv && is_device_ptr(wipv)) && !(wipstd && is_device_ptr(wipstd)) &&
-                        !(dwipv && is_device_ptr(dwipv)) && !(dwipstd && is_device_ptr(dwipstd));
-    if (packed) {                                  // the last stage writes the pinned result block itself: no copy command
-      double* ob = h_res;
-      hipLaunchKernelGGL(k_wg_final, dim3((unsigned)C), dim3(256), 0, stream, (const double*)pz, nzw, (const double*)pn,
-                         nnw, h, M, ob, ob + C, ob + 2 * C, ob + 2 * C + C * d);
-      LAUNCH_CHECK();
-      sync();
-      const double* hr = h_res;
-      if (wipv) std::memcpy(wipv, hr, (size_t)C * sizeof(double));
-      if (wipstd) std::memcpy(wipstd, hr + C, (size_t)C * sizeof(double));
-      if (dwipv) std::memcpy(dwipv, hr + 2 * C, (size_t)C * d * sizeof(double));
-      if (dwipstd) std::memcpy(dwipstd, hr + 2 * C + C * d, (size_t)C * d * sizeof(double));
-      return;
-    }
     hipLaunchKernelGGL(k_wg_final, dim3((unsigned)C), dim3(256), 0, stream, (const double*)pz, nzw, (const double*)pn,
                        nnw, h, M, d_v, d_s, d_dv, d_ds);
     LAUNCH_CHECK();
-    out_finish(wipv, C, o_wipv);
-    out_finish(wipstd, C, o_wipstd);
-    out_finish(dwipv, (size_t)C * d, o_mean);
-    out_finish(dwipstd, (size_t)C * d, o_var);
+    out.finish();
     sync();
+    out.scatter();
     return;
   }
+  double* d_v = out_dev(wipv, C, o_wipv);
+  double* d_s = out_dev(wipstd, C, o_wipstd);
+  double* d_dv = out_dev(dwipv, (size_t)C * d, o_mean);
+  double* d_ds = out_dev(dwipstd, (size_t)C * d, o_var);
   for (int64_t c0 = 0; c0 < C; c0 += CH) {
     const int64_t nc = std::min<int64_t>(CH, C - c0), ncp = round_up(nc, TILE);
     scale(cin + c0 * d, nc, ncp, hyp, CsT.d(), CH);

@@ -1,6 +1,8 @@
-// Kernels of the acquisition sweep and of the posterior / score gradients (gfx950).  Included by gp_sweep.hip only.
+// Kernels of the acquisition sweep and of the posterior / score gradients (gfx950).  Included by gp_sweep.hip only.  (The
+// few-candidate chain at the end of the file takes its rows stage and its cross kernel's front from wg_kernels.hpp.)
 #pragma once
 #include "kernels_common.hpp"
+#include "wg_kernels.hpp"
 
 namespace bobe {
 
@@ -685,8 +687,9 @@ __global__ __launch_bounds__(256) void k_wip_grad(const double* __restrict__ XsT
 // gradient is rearranged so that no stage costs more than O(N M):
 //   sum_z a_z sum_n W[n][z] T[j][n]  =  sum_n T[j][n] q_n,   q = W a      (a_z: the weight of d cross_z in the score)
 // Stages (blockIdx.y / .z = candidate): k_wg_col -> k_gemv_lower (v = Linv k_c) -> k_gemv_t_part + k_colsum_parts
-// (u = Linv^T v) -> k_wg_cross (s, cross_z, the weights, the z-side sums) -> k_wg_rows (q, q', the n-side sums) ->
-// k_wg_final.  All sums in a fixed order.
+// (u = Linv^T v) -> k_wg_cross (s, cross_z, the weights, the z-side sums) -> k_wg_rows<., ., 2> (q, q', the n-side sums) ->
+// k_wg_final.  All sums in a fixed order.  What the chain shares with the weighted scores' (criteria_kernels.hpp) - the cross
+// kernels' front and the rows stage - is wg_kernels.hpp.
 template <int KERN, int DCAP>
 __global__ __launch_bounds__(256) void k_wg_col(const double* __restrict__ XsT, int64_t ldx, int64_t n, int64_t np,
                                                 const double* __restrict__ cand, Hyper h, double* __restrict__ kc,
@@ -706,9 +709,8 @@ __global__ __launch_bounds__(256) void k_wg_col(const double* __restrict__ XsT, 
 }
 
 constexpr int WG_ZS = 4 + 2 * MAX_D;     // doubles per k_wg_cross partial: sum var+, sum sqrt, sum a2, sum b2, Dv[j], Ds[j]
-constexpr int WG_NS = 3 * MAX_D;         // doubles per k_wg_rows partial: Qv[j], Qs[j], ds[j]
 
-// one workgroup = 64 integration points (lane) x 4 interleaved quarters of the training points (wave)
+// one workgroup = 64 integration points (lane) x 4 interleaved quarters of the training points (wave): wg_cross_front
 template <int KERN, int DCAP>
 __global__ __launch_bounds__(256) void k_wg_cross(const double* __restrict__ ZsT, int64_t ldz, int64_t m,
                                                   const double* __restrict__ VZ, int64_t ldw, int64_t n, int64_t np,
@@ -719,38 +721,12 @@ __global__ __launch_bounds__(256) void k_wg_cross(const double* __restrict__ ZsT
                                                   double* __restrict__ partZ) {
   extern __shared__ double kcs[];                 // [n]: v = L^-1 k_c (the cross term is VZ^T v, as in the sweep)
   __shared__ double red[4], redz[4][64];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t c = blockIdx.y;
-  v += c * np;
-  double sq = 0.0;
-  for (int64_t i = t; i < n; i += 256) {
-    const double vi = v[i];
-    kcs[i] = vi;
-    sq += vi * vi;
-  }
-  sq = wave_sum(sq);
-  if (lane == 0) red[wave] = sq;
-  __syncthreads();
-  const double s = kself - ((red[0] + red[1]) + (red[2] + red[3]));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t c = blockIdx.y, z = (int64_t)blockIdx.x * 64 + lane;
+  double wk;
+  const double s = wg_cross_front(v + c * np, n, VZ, ldw, z, kself, kcs, red, redz, wk);
   const bool sbad = !(s >= 0.0);
-  const int64_t z = (int64_t)blockIdx.x * 64 + lane;
-  double acc = 0.0;
-  {
-    const double* wp = VZ + z;
-    int64_t i = wave;
-    for (; i + 28 < n; i += 32) {                 // eight rows in flight per thread
-      double w8[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) w8[q] = wp[(i + 4 * q) * ldw];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc = __builtin_fma(w8[q], kcs[i + 4 * q], acc);
-    }
-    for (; i < n; i += 4) acc = __builtin_fma(wp[i * ldw], kcs[i], acc);
-  }
-  redz[wave][lane] = acc;
-  __syncthreads();
   if (wave != 0) return;
-  const double wk = (redz[0][lane] + redz[1][lane]) + (redz[2][lane] + redz[3][lane]);
   double sv = 0.0, ss = 0.0, w1 = 0.0, w2 = 0.0, u1 = 0.0, u2 = 0.0, gz = 0.0, dz[DCAP];
 #pragma unroll
   for (int j = 0; j < DCAP; ++j) dz[j] = 0.0;
@@ -763,16 +739,11 @@ __global__ __launch_bounds__(256) void k_wg_cross(const double* __restrict__ ZsT
     }
     const double kz = kern_eval<KERN>(r2, h.kvar);
     gz = kern_grad_factor<KERN>(r2, h.kvar, kz);
-    const double cross = kz - wk;
-    double vp = basez[z] - (cross * cross) / s;
-    bool floored = sbad;
-    if (vp != vp) floored = true;
-    if (vp < NOISE_FLOOR) floored = true;
-    if (floored) vp = NOISE_FLOOR;
-    const double vs = vp * ystd2, sr = sqrt(vs);
+    const WgVplus f = wg_vplus(kz, wk, s, sbad, basez[z]);
+    const double cross = f.cross, vs = f.vp * ystd2, sr = sqrt(vs);
     sv = vs;
     ss = sr;
-    if (!floored) {
+    if (!f.floored) {
       w1 = -2.0 * cross / s * ystd2;
       w2 = (cross * cross) / (s * s) * ystd2;
       u1 = w1 / (2.0 * sr);
@@ -801,63 +772,6 @@ __global__ __launch_bounds__(256) void k_wg_cross(const double* __restrict__ ZsT
   }
 }
 
-// one workgroup = WG_ROWS training points, one per wave; lanes run over the integration points.
-// (Sixteen per wave - 64 per workgroup - left a refinement step at N = 400 on seven CUs for 41 of its 90 us.)
-constexpr int WG_ROWS = 4;
-template <int KERN, int DCAP>
-__global__ __launch_bounds__(256) void k_wg_rows(const double* __restrict__ XsT, int64_t ldx, int64_t n, int64_t np,
-                                                 const double* __restrict__ cand, Hyper h,
-                                                 const double* __restrict__ W, int64_t ldw, int64_t mp,
-                                                 const double* __restrict__ a1, const double* __restrict__ b1,
-                                                 int64_t lda, const double* __restrict__ u,
-                                                 double* __restrict__ partN) {
-  __shared__ double red[4][3][DCAP];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t c = blockIdx.y;
-  a1 += c * lda;
-  b1 += c * lda;
-  u += c * np;
-  const double xl = (lane < h.d) ? cand[c * h.d + lane] / h.ls[lane] : 0.0;      // this lane's coordinate (lane = j)
-  double xc[DCAP];                                                                 // the candidate, scaled (every lane)
-#pragma unroll
-  for (int j = 0; j < DCAP; ++j) xc[j] = (j < h.d) ? cand[c * h.d + j] / h.ls[j] : 0.0;
-  double aq = 0.0, as = 0.0, au = 0.0;
-  for (int r = 0; r < WG_ROWS / 4; ++r) {
-    const int64_t i = (int64_t)blockIdx.x * WG_ROWS + wave + 4 * r;
-    if (i >= n) break;                            // uniform per wave
-    double q = 0.0, qs = 0.0;
-    for (int64_t z = lane; z < mp; z += 64) {
-      const double w = W[i * ldw + z];
-      q = __builtin_fma(a1[z], w, q);
-      qs = __builtin_fma(b1[z], w, qs);
-    }
-    q = chain_wave_sum(q);
-    qs = chain_wave_sum(qs);
-    double r2 = 0.0;
-#pragma unroll
-    for (int j = 0; j < DCAP; ++j) {
-      const double df = (j < h.d) ? XsT[j * ldx + i] - xc[j] : 0.0;
-      r2 += df * df;
-    }
-    const double kv = kern_eval<KERN>(r2, h.kvar);
-    const double tj = (lane < h.d) ? kern_grad_factor<KERN>(r2, h.kvar, kv) * (XsT[lane * ldx + i] - xl) : 0.0;
-    aq = __builtin_fma(q, tj, aq);
-    as = __builtin_fma(qs, tj, as);
-    au = __builtin_fma(u[i], tj, au);
-  }
-  if (lane < DCAP) {
-    red[wave][0][lane] = aq;
-    red[wave][1][lane] = as;
-    red[wave][2][lane] = au;
-  }
-  __syncthreads();
-  if (t < 3 * DCAP) {
-    const int k = t / DCAP, j = t % DCAP;
-    partN[(c * gridDim.x + blockIdx.x) * WG_NS + k * MAX_D + j] =
-        (red[0][k][j] + red[1][k][j]) + (red[2][k][j] + red[3][k][j]);
-  }
-}
-
 // the partial sums of k_wg_cross (nzw of them) and k_wg_rows (nnw) -> scores and gradients of candidate blockIdx.x.
 // 256 threads: thread (j = t & 31, part = t >> 5) adds the partials part, part + 8, ... of coordinate j, the eight parts are
 // combined in order.
@@ -869,7 +783,8 @@ __global__ __launch_bounds__(256) void k_wg_final(const double* __restrict__ par
   const int t = threadIdx.x, j = t & 31, part = t >> 5;
   const int64_t c = blockIdx.x;
   const double* pz = partZ + c * nzw * WG_ZS;
-  const double* pn = partN + c * nnw * WG_NS;
+  constexpr int NS = 3 * MAX_D;                   // k_wg_rows<., ., 2>'s partial: Qv[j], Qs[j], ds[j]
+  const double* pn = partN + c * nnw * NS;
   double sv = 0.0, ss = 0.0, a2 = 0.0, b2 = 0.0, dv = 0.0, dsd = 0.0, qv = 0.0, qs = 0.0, ds = 0.0;
   for (int w = part; w < nzw; w += 8) {
     sv += pz[w * WG_ZS];
@@ -879,10 +794,28 @@ __global__ __launch_bounds__(256) void k_wg_final(const double* __restrict__ par
     dv += pz[w * WG_ZS + 4 + j];
     dsd += pz[w * WG_ZS + 4 + MAX_D + j];
   }
-  for (int w = part; w < nnw; w += 8) {
-    qv += pn[w * WG_NS + j];
-    qs += pn[w * WG_NS + MAX_D + j];
-    ds += pn[w * WG_NS + 2 * MAX_D + j];
+  {
+    // (k_wg_final_w's form: the three rows of four partials are loaded before any is added - one partial per trip leaves the
+    // stage waiting on nnw / 8 load latencies in a row.  Each row's sum keeps its order.)
+    int w = part;
+    for (; w + 24 < nnw; w += 32) {
+      double x[4][3];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) x[q][r] = pn[(w + 8 * q) * NS + r * MAX_D + j];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        qv += x[q][0];
+        qs += x[q][1];
+        ds += x[q][2];
+      }
+    }
+    for (; w < nnw; w += 8) {
+      qv += pn[w * NS + j];
+      qs += pn[w * NS + MAX_D + j];
+      ds += pn[w * NS + 2 * MAX_D + j];
+    }
   }
   const double mine[9] = {sv, ss, a2, b2, dv, dsd, qv, qs, ds};
 #pragma unroll

@@ -36,7 +36,8 @@ def adapt(eps):
 
 
 def solve_entries(gp, tag, cand, Z, few, q):
-    """the entries that go through solve_v (and the few-candidate chain): sweep, wip_grad on both paths, predict_grad"""
+    """the entries that go through solve_v (and the few-candidate chains): sweep, wip_grad on both paths and its two siblings,
+    predict_grad"""
     gp._lib.bobe_gp_set_chunk(gp._h, 128)
     r = gp.wip_sweep(cand, Z, want_mean_var=True)                # 300 candidates at chunk 128: three chunks, k_wip_score
     out[f"sweep_{tag}"] = cat(r["wipv"], r["wipstd"], r["mean"], r["var"], [r["argmin_v"], r["argmin_s"], r["min_v"], r["min_s"]])
@@ -44,6 +45,11 @@ def solve_entries(gp, tag, cand, Z, few, q):
     out[f"sweepz_{tag}"] = cat(rz["wipv"], rz["wipstd"], [rz["argmin_v"], rz["argmin_s"]])
     gp._lib.bobe_gp_set_chunk(gp._h, 0)
     out[f"wgfew_{tag}"] = cat(*gp.wip_grad(few, Z))              # 3 candidates: the matrix-vector path
+    lw = 1.5 * np.random.default_rng(Z.shape[0]).normal(size=Z.shape[0])   # its two siblings, log-weights given
+    rw = gp.wip_grad_w(few, Z, log_weights=lw)
+    out[f"wgw_{tag}"] = cat(*[rw[k] for k in gp.CRITERIA], *[rw["d" + k] for k in gp.CRITERIA])
+    rv = gp.wip_grad_zvar(few, Z, log_weights=lw)
+    out[f"wgzv_{tag}"] = cat(rv["zvar"], rv["dzvar"], [rv["log_ez"]])
     out[f"wgtile_{tag}"] = cat(*gp.wip_grad(cand[:40], Z))       # 40: the tile path
     out[f"pg_{tag}"] = cat(*gp.predict_grad(q))
     out[f"pgm_{tag}"] = cat(*gp.predict_grad(q, mean_only=True))
